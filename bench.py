@@ -6,13 +6,17 @@ A "step" is one pass of the hot path = one predictor-corrector iteration (src/so
 residuals, Sigma update, condensed-KKT assembly (SYRK), Cholesky, two solves with residual check,
 step lengths, iterate update, model evaluation) on a synthetic dense QP generated in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 50000] [--m 20000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 50000] [--m 20000] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes what the last step computed when --dump-outputs is given, and
+prints the line.  --full also measures what stands beside the headline: the other max_ncorr setting, one whole solve,
+BASELINE configs[1] and [3], the CPU port, and with N > 1 the independent-QPs leg.
 
 N > 1, one rank per GPU: ONE QP of that size is shared by all GPUs on a P x Q grid -- 2-D block-cyclic distributed
 assembly, Cholesky and triangular solves over RCCL (csrc/dist.hip): strong scaling, value = iterations /
-max-over-ranks time.  The independent-QPs rate (every rank its own instance, no data-path collective: BASELINE
-configs[3] style weak scaling) is measured first and reported beside it (`independent_qps`); `--kkt local` makes it the
-headline.  Rank 0 prints ONE JSON line.
+max-over-ranks time.  With --full the independent-QPs rate (every rank its own instance, no data-path collective:
+BASELINE configs[3] style weak scaling) is measured first and reported beside it (`independent_qps`); `--kkt local` makes
+it the headline.  Rank 0 prints ONE JSON line.
 
 How the N ranks come to be (`launch_plan`): under a launcher (`python -m torch.distributed.run --nproc-per-node N
 bench.py --gpus N ...`: WORLD_SIZE is set) this process IS one of them; a plain `python bench.py --gpus N` with N > 1
@@ -79,9 +83,18 @@ def parse():
                         "fit, the committed full-size record or the flop-scaled sample is reported and `kind` says so)")
     p.add_argument("--cpu-full", action="store_true",
                    help="only the CPU port at the FULL workload size: initialize + one iteration, timed (minutes); "
-                        "prints its own JSON line -- kept under profiles/ and quoted by the default run")
+                        "prints its own JSON line -- kept under profiles/ and quoted by a --full run")
     p.add_argument("--profile-all", action="store_true", help="time every kernel class (perturbs the "
                    "launch-bound ones); default times only the MFMA classes")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what stands beside the headline: the other max_ncorr setting (`max_ncorr_0`), "
+                        "`whole_solve`, `extras` (BASELINE configs[1] and [3]), `cpu_baseline` and, with N > 1, the "
+                        "independent-QPs leg (minutes).  Without it a run sets up, warms up, times --steps iterations "
+                        "and prints the line; the --no-* options above switch single legs of a --full run off")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the solver returns to a caller after the last of them -- "
+                        "solution, constraints, multipliers (y, z_L, z_U) and objective, unscaled, float64 -- as "
+                        "DIR/<name>.npy (rank 0's headline measurement; at most 64 MB, a fixed sample of longer arrays)")
     # ranks started by spawn_ranks() find their arguments in the environment: torch.distributed.run's own parser
     # would otherwise claim what it can abbreviate (`--m` is ambiguous between --max-restarts, --master-addr, ...)
     if os.environ.get("MADQP_BENCH_SPAWNED_BY") and os.environ.get("MADQP_BENCH_ARGV") and len(sys.argv) == 1:
@@ -170,7 +183,7 @@ def cpu_full_size(args, M, be):
     """SURVEY.md 8d / BASELINE.md section 3: the CPU port timed AT the metric size -- set-up with its start-point
     factorisation and two solves (src/solver.jl:127-182) and one full iteration (:259-343) of oracle/mpc.py on the
     same inputs bit for bit (generated on the device, copied to the host).  Takes minutes: run on its own
-    (`python bench.py --cpu-full`), the result is kept under profiles/ and quoted by the default run."""
+    (`python bench.py --cpu-full`), the result is kept under profiles/ and quoted by a --full run."""
     import numpy as np
     import torch
 
@@ -627,10 +640,39 @@ def solver_options(M, args, max_ncorr, mode):
                 driver=args.driver if mode == "local" else "python", kkt_system=args.kkt_system)
 
 
-def measure(args, F, be, world, seed, mode, max_ncorr=None, steps=None, warmup=None, progress=lambda: None):
+DUMP_BYTES = 60 * 10 ** 6  # all arrays together, under 64 MB with the .npy headers
+
+
+def solver_outputs(solver):
+    """What a caller of the timed path receives after its last step (MPCSolver.result(): unscaled solution, constraint
+    values, multipliers and objective), as float64 host arrays."""
+    import numpy as np
+
+    r = solver.result()
+    out = {k: np.ascontiguousarray(r[k], dtype=np.float64)
+           for k in ("solution", "constraints", "multipliers", "multipliers_L", "multipliers_U")}
+    out["objective"] = np.array([r["objective"]], dtype=np.float64)
+    return out
+
+
+def dump_outputs(directory, outputs):
+    """DIR/<name>.npy for every output; an array longer than its share of DUMP_BYTES is replaced by the entries at a
+    fixed set of positions (np.random.default_rng(0) over its length, sorted), so that two runs stay comparable."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // 8 // max(len(outputs), 1)
+    for name, a in outputs.items():
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def measure(args, F, be, world, seed, mode, max_ncorr=None, steps=None, warmup=None, progress=lambda: None,
+            outputs=False):
     """Warm-up + the timed region (barrier / sync on both sides, MAX over ranks) for one solver set-up.
     mode "local": this rank's own QP; "grid": ONE QP over all ranks on a P x Q grid (madqp_dist_* / madqp_dkkt_*,
-    SURVEY.md 8e)."""
+    SURVEY.md 8e).  ``outputs``: keep what the last step computed (solver_outputs) in res["outputs"]."""
     M = F.module()
     nx, m = args.nx, args.m
     max_ncorr = args.max_ncorr if max_ncorr is None else max_ncorr
@@ -670,6 +712,8 @@ def measure(args, F, be, world, seed, mode, max_ncorr=None, steps=None, warmup=N
                if solver.trace else None)
     if mode == "grid":
         res["layout"] = grid_layout(grid, dq)
+    if outputs:
+        res["outputs"] = solver_outputs(solver)
     solver.close()
     if grid is not None:
         grid.close()
@@ -973,21 +1017,25 @@ def main():
                                          "ms_per_step": r2["tmax"] / s2 * 1e3, "steps": s2,
                                          "factorizations": r2["nfact"], "solves": r2["prof"]["trsv"][1]}
 
+    dump = args.dump_outputs is not None and rank == 0
     if world == 1 or mode == "local":
-        res = measure(args, F, be, world, args.seed if mode != "local" else rank_seed(args.seed, rank), mode)
+        res = measure(args, F, be, world, args.seed if mode != "local" else rank_seed(args.seed, rank), mode,
+                      outputs=dump)
         if rank == 0:
             out = bench_line(args, res, world, F)
-        if mode == "local" and not args.no_second_ncorr:
+        if dump:
+            dump_outputs(args.dump_outputs, res["outputs"])
+        if args.full and mode == "local" and not args.no_second_ncorr:
             second_ncorr()
-        if rank == 0 and world == 1 and mode == "local" and not args.no_whole_solve:
+        if rank == 0 and world == 1 and mode == "local" and args.full and not args.no_whole_solve:
             try:
                 out["whole_solve"] = whole_solve(args, F, be)
             except Exception as e:  # the headline must not depend on it
                 out["whole_solve"] = {"error": f"{type(e).__name__}: {e}"[:300]}
             out["value_reference_definition"] = out["whole_solve"].get("iterations_per_s")
-        if rank == 0 and world == 1 and mode == "local" and not args.no_batch_extra and F.cuda:
+        if rank == 0 and world == 1 and mode == "local" and args.full and not args.no_batch_extra and F.cuda:
             out["extras"] = {"c2_nx5000_m2000": c2_extra(args, M, be), "batch_1024x512x256": batch_extra(M, be, args.seed)}
-        if rank == 0 and world == 1 and not args.no_cpu_baseline and F.cuda:
+        if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and F.cuda:
             out["cpu_baseline"] = cpu_baseline(args, nx, m, M, be)
         if rank == 0:
             emit_json(out)
@@ -1000,7 +1048,7 @@ def main():
         import threading
 
         weak = None
-        if not args.no_independent_leg:
+        if args.full and not args.no_independent_leg:
             weak = measure(args, F, be, world, rank_seed(args.seed, rank), "local", steps=max(1, min(args.steps, 5)),
                            warmup=min(args.warmup, 1))
         state = {"printed": False}
@@ -1035,12 +1083,14 @@ def main():
         # so it measures silence, not the length of the run
         dog = Watchdog(args.extra_timeout, bail)
         try:
-            res = measure(args, F, be, world, args.seed, mode, progress=dog.kick)
+            res = measure(args, F, be, world, args.seed, mode, progress=dog.kick, outputs=dump)
         except Exception as e:
             dog.stop()
             emit(fallback(f"{type(e).__name__}: {e}"[:400] + "; exit code 3"))
             os._exit(3)
         dog.stop()
+        if dump:
+            dump_outputs(args.dump_outputs, res["outputs"])
         if rank == 0:
             out = bench_line(args, res, world, F)
             comm = (out.get("comm") or {})

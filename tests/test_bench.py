@@ -164,7 +164,7 @@ def test_gpus_2_without_a_launcher_is_a_run_on_two_ranks():
     that line says n_gpus: 2 / scaling: strong and carries the communicator size."""
     import json
 
-    p = _run_bench(["--gpus", "2", *SMALL], {"MADQP_BENCH_TEST_DOUBLE": "bench_double:Double"})
+    p = _run_bench(["--gpus", "2", *SMALL, "--full"], {"MADQP_BENCH_TEST_DOUBLE": "bench_double:Double"})
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout
@@ -187,7 +187,8 @@ def test_the_drivers_n8_command_is_one_line_on_the_2x4_grid():
     import json
 
     p = _run_bench(["--gpus", "8", "--steps", "20", "--warmup", "5", "--nx", "48", "--m", "20", "--driver", "python",
-                    "--no-cpu-baseline", "--extra-timeout", "240"], {"MADQP_BENCH_TEST_DOUBLE": "bench_double:Double"},
+                    "--no-cpu-baseline", "--extra-timeout", "240", "--full"],
+                   {"MADQP_BENCH_TEST_DOUBLE": "bench_double:Double"},
                    timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -216,7 +217,8 @@ def test_one_gpu_line_has_the_reference_rate_definitions():
     (src/solver.jl:353,392; scripts/benchmarks_cpu.jl:52-55)."""
     import json
 
-    p = _run_bench(["--gpus", "1", *SMALL, "--no-second-ncorr"], {"MADQP_BENCH_TEST_DOUBLE": "bench_double:Double"})
+    p = _run_bench(["--gpus", "1", *SMALL, "--no-second-ncorr", "--full"],
+                   {"MADQP_BENCH_TEST_DOUBLE": "bench_double:Double"})
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -255,3 +257,59 @@ def test_under_an_external_launcher_the_process_is_one_of_the_ranks():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["n_gpus_requested"] == 2 and out["scaling"] == "strong"
     assert out["ranks"]["started_by"] == "an external launcher" and out["comm"]["world_size"] == 2
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_what_the_last_step_computed(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` sets up, warms up, times K steps and prints the line; the legs
+    beside the headline are --full's.  --dump-outputs DIR writes what the timed path returns to a caller after its last
+    step: the same arguments give the same arrays, and they are those of the solver driven through the same W + K
+    steps in this process."""
+    import json
+    import types
+
+    import numpy as np
+    from bench_double import Double
+
+    argv = ["--gpus", "1", "--steps", "4", "--warmup", "2", "--nx", "40", "--m", "16", "--driver", "python"]
+    lines, dumps = [], {}
+    for run in ("a", "b"):
+        p = _run_bench([*argv, "--dump-outputs", str(tmp_path / run)], {"MADQP_BENCH_TEST_DOUBLE": "bench_double:Double"})
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, p.stdout
+        dumps[run] = {f.stem: np.load(f) for f in (tmp_path / run).glob("*.npy")}
+    out = json.loads(lines[0])
+    assert out["steps"] == 4 and out["warmup"] == 2 and out["iterations_done"] == 6
+    assert abs(out["value"] - 4 / (out["ms_per_step"] * 4e-3)) < 1e-6 * out["value"]
+    assert out["unit"] == "iterations/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    for leg in ("max_ncorr_0", "whole_solve", "value_reference_definition", "extras", "cpu_baseline", "independent_qps"):
+        assert leg not in out, leg
+    shapes = {"solution": 40, "constraints": 16, "multipliers": 16, "multipliers_L": 40, "multipliers_U": 40, "objective": 1}
+    assert {k: v.shape for k, v in dumps["a"].items()} == {k: (n,) for k, n in shapes.items()}
+    assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in dumps["a"].values())
+    for k in shapes:
+        assert np.array_equal(dumps["a"][k], dumps["b"][k]), k
+
+    F = Double()
+    be = F.backend(0)
+    opts = bench.solver_options(M, types.SimpleNamespace(driver="python", kkt_system="condensed"), 3, "local")
+    s = M.MPCSolver(F.local_qp(be, 20250614 + 1, 40, 16), be, **opts)
+    s.initialize()
+    loop = bench.StepLoop(s)
+    for _ in range(6):
+        loop.step()
+    want = bench.solver_outputs(s)
+    for k in shapes:
+        np.testing.assert_allclose(dumps["a"][k], want[k], rtol=1e-9, atol=1e-12, err_msg=k)
+
+
+def test_dump_outputs_samples_long_arrays_at_fixed_positions(tmp_path, monkeypatch):
+    import numpy as np
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 8 * 100)  # 100 entries per array for two arrays
+    outputs = {"long": np.arange(1000, dtype=np.float64), "short": np.arange(7, dtype=np.float64)}
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), outputs)
+    a, b = np.load(tmp_path / "a" / "long.npy"), np.load(tmp_path / "b" / "long.npy")
+    assert a.shape == (100,) and np.array_equal(a, b) and np.all(np.diff(a) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "short.npy"), outputs["short"])

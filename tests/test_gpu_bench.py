@@ -21,8 +21,8 @@ def run_bench(argv, extra_env, timeout=900):
 
 
 def test_gpus_2_without_a_launcher_runs_two_ranks_of_the_hip_library():
-    p = run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--nx", "2000", "--m", "800", "--extra-timeout", "300"],
-                  {"MADQP_DIST_BACKEND": "gloo", "MADQP_DIST_SHARE_DEVICE": "1"})
+    p = run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--nx", "2000", "--m", "800", "--extra-timeout", "300",
+                   "--full"], {"MADQP_DIST_BACKEND": "gloo", "MADQP_DIST_SHARE_DEVICE": "1"})
     assert p.returncode == 0, (p.stdout[-1000:], p.stderr[-4000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout
@@ -55,7 +55,7 @@ def test_rehearsal_of_the_drivers_multi_gpu_command_on_a_2x2_grid(bcast):
         env["MADQP_DIST_BCAST"] = "p2p"
     t0 = time.time()
     p = run_bench(["--gpus", "4", "--steps", "20", "--warmup", "5", "--nx", "3000", "--m", "1200", "--extra-timeout", "300",
-                   "--no-cpu-baseline"], env)
+                   "--no-cpu-baseline", "--full"], env)
     assert p.returncode == 0, (p.stdout[-1000:], p.stderr[-4000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout
@@ -74,3 +74,40 @@ def test_the_test_double_is_refused_on_a_box_with_a_gpu():
                   {"MADQP_BENCH_TEST_DOUBLE": "bench_double:Double",
                    "PYTHONPATH": os.pathsep.join([os.path.join(ROOT, "tests"), ROOT])}, timeout=300)
     assert p.returncode == 2 and p.stdout.strip() == "" and "refused" in p.stderr
+
+
+def test_plain_one_gpu_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path, hip):
+    """The 1-GPU command without --full: set-up, warm-up, the timed steps and ONE line without the legs beside the
+    headline; --dump-outputs DIR holds what the solver returns after the last timed step -- the same arrays as the
+    library driven through the same warm-up + steps in this process."""
+    import types
+
+    import numpy as np
+
+    import bench
+    import madqp_jl_amd as M
+
+    p = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--nx", "2000", "--m", "800",
+                   "--dump-outputs", str(tmp_path)], {}, timeout=300)
+    assert p.returncode == 0, (p.stdout[-1000:], p.stderr[-4000:])
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    assert out["data"] == "synthetic" and out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    for leg in ("max_ncorr_0", "whole_solve", "extras", "cpu_baseline", "independent_qps"):
+        assert leg not in out, leg
+    got = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    args = types.SimpleNamespace(driver="native", kkt_system="condensed")
+    s = M.MPCSolver(M.DeviceQP.synthetic(hip, 20250614 + 1, 2000, 800), hip, **bench.solver_options(M, args, 3, "local"))
+    try:
+        s.initialize()
+        loop = bench.StepLoop(s)
+        for _ in range(4):
+            loop.step()
+        want = bench.solver_outputs(s)
+    finally:
+        s.close()
+    assert sorted(got) == sorted(want)
+    for k in want:
+        assert got[k].dtype == np.float64 and got[k].shape == want[k].shape, k
+        np.testing.assert_allclose(got[k], want[k], rtol=1e-7, atol=1e-9, err_msg=k)

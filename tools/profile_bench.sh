@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 BENCH_ARGS=("$@")
 run() { # name, rocprof args...
   local name=$1; shift
-  timeout -k 10 600 rocprofv3 "$@" --output-format csv -d $OUT/prof_${TAG}_$name -- python3 $ROOT/bench.py --no-cpu-baseline "${BENCH_ARGS[@]}" > $OUT/prof_${TAG}_$name.log 2>&1
+  timeout -k 10 600 rocprofv3 "$@" --output-format csv -d $OUT/prof_${TAG}_$name -- python3 $ROOT/bench.py --full --no-cpu-baseline "${BENCH_ARGS[@]}" > $OUT/prof_${TAG}_$name.log 2>&1
   echo "$name rc=$?"; grep -o '"value": [0-9.e+-]*' $OUT/prof_${TAG}_$name.log | head -1
 }
 run stats --kernel-trace --stats

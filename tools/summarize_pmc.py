@@ -125,7 +125,7 @@ for k in ("trsv_fwd_sweep_kernel", "trsv_bwd_sweep_kernel", "gemv_n_wave", "gemv
         rates[k] = e
 out["hbm_bound_kernels"] = rates
 bench_args = sys.argv[4] if len(sys.argv) > 4 else "(defaults: --steps 3 --warmup 1)"
-out["config"] = dict(nx=nx, m=m, command=f"rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --no-cpu-baseline {bench_args} "
+out["config"] = dict(nx=nx, m=m, command=f"rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --full --no-cpu-baseline {bench_args} "
                                          f"[nx={nx}, m={m}]; one pass per counter group (tools/profile_bench.sh)")
 json.dump(out, open(f"profiles/{tag}_pmc_summary.json", "w"), indent=1)
 for f in glob.glob(f"{PROF}/prof_{tag}_stats/*/*_kernel_stats.csv"):
