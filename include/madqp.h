@@ -507,7 +507,8 @@ int32_t madqp_mpc_readbacks(const madqp_mpc* mpc, int64_t* count);
 int32_t madqp_mpc_ahead_stats(const madqp_mpc* mpc, int64_t* queued, int64_t* used);
 
 /* ----------------------------------------- batches of small, equally shaped QPs */
-/* B problems with the same (nx, m) and the same bound / inequality pattern advance in lock step:
+/* B problems with the same (nx, m) advance in lock step -- with one bound / inequality pattern for the whole batch
+ * (madqp_batch_create) or a pattern of their own each (madqp_batch_create_patterns):
  * assembly and Cholesky are batched launches of the MFMA kernels, the rest of an iteration is one
  * workgroup per problem; scalars stay on the device, a finished problem is masked out by its status
  * word (csrc/batch.hip).  Options: every step rule and regularization of madqp_mpc_options, Gondzio corrections;
@@ -530,6 +531,18 @@ int32_t madqp_batch_create(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, int
                            const int64_t* ind_ineq_host, int64_t nlb, const int64_t* ind_lb, int64_t nub,
                            const int64_t* ind_ub, const madqp_batch_data* data, const madqp_mpc_options* opt,
                            madqp_batch** out);
+/* like madqp_batch_create, but every problem has its own index lists (CSR form, host arrays, copied):
+ * problem b: ind_ineq_host[ineq_ptr[b] .. ineq_ptr[b+1]), strictly increasing rows in [0, m);
+ * ind_lb_host[lb_ptr[b] .. lb_ptr[b+1]) and ind_ub_host[ub_ptr[b] .. ub_ptr[b+1]), strictly increasing in [0, n_b).
+ * Each *_ptr has B + 1 entries, starts at 0 and does not decrease.  ns_b = ineq_ptr[b+1] - ineq_ptr[b] <= m,
+ * n_b = nx + ns_b, n_max = nx + max_b ns_b.  data->x, xl, xu, zl, zu are [B][n_max]: problem b uses the first n_b
+ * entries; the library neither reads nor writes entries n_b .. n_max-1.  A malformed list returns MADQP_ERR_ARG.
+ * The condensed form needs delta_d < 0 as soon as one problem has an equality row.  madqp_batch_init / _iterate /
+ * _results / _destroy take either kind of handle. */
+int32_t madqp_batch_create_patterns(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, const int64_t* ineq_ptr,
+                                    const int64_t* ind_ineq_host, const int64_t* lb_ptr, const int64_t* ind_lb_host,
+                                    const int64_t* ub_ptr, const int64_t* ind_ub_host, const madqp_batch_data* data,
+                                    const madqp_mpc_options* opt, madqp_batch** out);
 int32_t madqp_batch_destroy(madqp_batch* b);
 /* src/solver.jl:162-179 for every problem: initialize!(kkt), model evaluation, norms, starting point */
 int32_t madqp_batch_init(madqp_batch* b, double mu_init, double bound_fac);

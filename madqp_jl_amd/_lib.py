@@ -167,6 +167,8 @@ _SIGNATURES = {
     "madqp_gen_wigner_cyclic": [vp, C.c_uint64, i64, f64, i64, i32, i32, i32, i32, i64, i64, vp, i64],
     "madqp_batch_create": [vp, i64, i64, i64, i64, pi64, i64, vp, i64, vp, C.POINTER(CBatchData),
                            C.POINTER(CMpcOptions), C.POINTER(vp)],
+    "madqp_batch_create_patterns": [vp, i64, i64, i64, pi64, pi64, pi64, pi64, pi64, pi64, C.POINTER(CBatchData),
+                                    C.POINTER(CMpcOptions), C.POINTER(vp)],
     "madqp_batch_destroy": [vp],
     "madqp_batch_init": [vp, f64, f64],
     "madqp_batch_iterate": [vp, i32, i32, pi32],

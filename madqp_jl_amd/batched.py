@@ -1,6 +1,8 @@
 """Lock-step solver for a batch of small, equally shaped QPs (BASELINE configs[3]; csrc/batch.hip).
 
-All problems share (nx, m) and the pattern of finite bounds / equality rows.  The one-off set-up of
+All problems share (nx, m).  By default they also share the pattern of finite bounds / equality rows; with
+``per_problem_patterns=True`` every problem has its own (``pack_patterns``: CSR index lists, the slack part of the
+stacked arrays padded to the largest number of slacks, ``madqp_batch_create_patterns``).  The one-off set-up of
 ``MPCSolver.initialize`` (src/solver.jl:127-159: bounds, interior push, scaling) runs here as
 elementwise torch ops over the stacked arrays; from ``madqp_batch_init`` on everything happens in
 ``libmadqp_hip.so``: a handful of launches per iteration for the whole batch, per-problem scalars on
@@ -19,13 +21,40 @@ from .options import IPMOptions
 from .solver import _push_interior, get_index_constraints, native_options
 
 
-class BatchedMPCSolver:
-    """``qps``: list of :class:`DeviceQP` with identical shapes and bound patterns."""
+def pack_patterns(lvar, uvar, lcon, ucon, fixed_variable_treatment="relax_bound"):
+    """Per-problem index lists of a batch (host, numpy; ``lvar``, ``uvar``: [B][nx], ``lcon``, ``ucon``: [B][m]):
+    ``get_index_constraints`` of every problem, concatenated in CSR form -- problem b's ind_ineq is
+    ``ind_ineq[ineq_ptr[b]:ineq_ptr[b+1]]``, likewise ind_lb / ind_ub (indices into its own n_b = nx + ns_b variables).
+    ``gather`` / ``mask`` ([B][ns_max]): slack k of problem b belongs to row ``gather[b, k]`` where ``mask[b, k]``; the
+    padding (mask False) points at row 0."""
+    lvar, uvar, lcon, ucon = (np.asarray(a, dtype=np.float64) for a in (lvar, uvar, lcon, ucon))
+    B = lvar.shape[0]
+    ics = [get_index_constraints(lvar[b], uvar[b], lcon[b], ucon[b], fixed_variable_treatment) for b in range(B)]
+    csr = lambda key: (np.concatenate([[0], np.cumsum([len(ic[key]) for ic in ics])]).astype(np.int64),
+                       np.concatenate([np.asarray(ic[key], dtype=np.int64) for ic in ics] + [np.zeros(0, np.int64)]))
+    ineq_ptr, ind_ineq = csr("ind_ineq")
+    lb_ptr, ind_lb = csr("ind_lb")
+    ub_ptr, ind_ub = csr("ind_ub")
+    ns = np.diff(ineq_ptr)
+    ns_max = int(ns.max()) if B else 0
+    mask = np.arange(ns_max)[None, :] < ns[:, None]
+    gather = np.zeros((B, ns_max), dtype=np.int64)
+    gather[mask] = ind_ineq
+    return dict(ineq_ptr=ineq_ptr, ind_ineq=ind_ineq, lb_ptr=lb_ptr, ind_lb=ind_lb, ub_ptr=ub_ptr, ind_ub=ind_ub,
+                ns=ns, ns_max=ns_max, gather=gather, mask=mask, any_eq=bool((ns < lcon.shape[1]).any()))
 
-    def __init__(self, qps, backend, **opts):
+
+class BatchedMPCSolver:
+    """``qps``: list of :class:`DeviceQP` with identical shapes and -- unless ``per_problem_patterns`` -- identical bound
+    patterns (which variables have a finite lower / upper bound, which rows are equalities)."""
+
+    def __init__(self, qps, backend, per_problem_patterns=False, **opts):
         if not qps:
             raise ValueError("empty batch")
         self.be, self.qps = backend, list(qps)
+        self.per_problem = bool(per_problem_patterns)
+        if any((q.nvar, q.ncon) != (qps[0].nvar, qps[0].ncon) for q in self.qps):
+            raise ValueError("all problems of a batch must have the same (nx, m)")
         self.opt = IPMOptions(**opts)
         if self.opt.kkt_system not in ("condensed", "normal") or self.opt.check_residual:
             raise ValueError("the batched driver supports the condensed KKT system and the normal equations, on one GPU")
@@ -36,28 +65,36 @@ class BatchedMPCSolver:
         st = lambda name: torch.stack([getattr(q, name) for q in self.qps]).contiguous()
         self.lvar, self.uvar, self.lcon, self.ucon = st("lvar"), st("uvar"), st("lcon"), st("ucon")
         host = lambda t: t.detach().cpu().numpy()
-        ic = get_index_constraints(host(self.lvar[0]), host(self.uvar[0]), host(self.lcon[0]), host(self.ucon[0]),
-                                   self.opt.fixed_variable_treatment or "relax_bound")
-        same = lambda a: bool((torch.isfinite(a) == torch.isfinite(a[0])).all())
-        if not (same(self.lvar) and same(self.uvar) and same(self.lcon) and same(self.ucon)
-                and bool(((self.lcon == self.ucon) == (self.lcon[0] == self.ucon[0])).all())):
-            raise ValueError("all problems of a batch must share the pattern of finite bounds and equality rows")
+        fvt = self.opt.fixed_variable_treatment or "relax_bound"
+        if self.per_problem:
+            self.pat = pack_patterns(host(self.lvar), host(self.uvar), host(self.lcon), host(self.ucon), fvt)
+            has_eq = self.pat["any_eq"]
+            self.ns = self.pat["ns_max"]
+        else:
+            self.pat = None
+            ic = get_index_constraints(host(self.lvar[0]), host(self.uvar[0]), host(self.lcon[0]), host(self.ucon[0]), fvt)
+            same = lambda a: bool((torch.isfinite(a) == torch.isfinite(a[0])).all())
+            if not (same(self.lvar) and same(self.uvar) and same(self.lcon) and same(self.ucon)
+                    and bool(((self.lcon == self.ucon) == (self.lcon[0] == self.ucon[0])).all())):
+                raise ValueError("all problems of a batch must share the pattern of finite bounds and equality rows "
+                                 "(per_problem_patterns=True lifts this)")
+            self.ind_ineq, self.ind_eq = ic["ind_ineq"], ic["ind_eq"]
+            has_eq = len(self.ind_eq) > 0
+            self.ns = len(self.ind_ineq)
+            self.ind_lb = torch.as_tensor(ic["ind_lb"], dtype=torch.int64, device=dev)
+            self.ind_ub = torch.as_tensor(ic["ind_ub"], dtype=torch.int64, device=dev)
+            self.nlb, self.nub = self.ind_lb.numel(), self.ind_ub.numel()
         if any(q.H is not None and q.H.dim() != 2 for q in self.qps) or any(not torch.is_tensor(q.A) for q in self.qps):
             raise ValueError("the batched driver takes dense H and dense A")
         if any((q.H is None) != (q0.H is None) for q in self.qps):
             raise ValueError("all problems of a batch must be QPs or all LPs")
-        self.ind_ineq, self.ind_eq = ic["ind_ineq"], ic["ind_eq"]
-        self.ns = len(self.ind_ineq)
-        self.n = self.nx + self.ns
-        self.ind_lb = torch.as_tensor(ic["ind_lb"], dtype=torch.int64, device=dev)
-        self.ind_ub = torch.as_tensor(ic["ind_ub"], dtype=torch.int64, device=dev)
-        self.nlb, self.nub = self.ind_lb.numel(), self.ind_ub.numel()
+        self.n = self.nx + self.ns  # per_problem_patterns: n_max, the stride of x, xl, xu, zl, zu
         reg = self.opt.regularization
         self._copt = native_options(self.opt)
         self._copt.kkt_form = 1 if self.normal else 0
         if self.normal and q0.H is not None:
             raise ValueError("The KKT system NormalKKTSystem supports only linear programs.")  # normalkkt.jl:45-48
-        if not self.normal and len(self.ind_eq) and not (self._copt.regularization != 0 and reg.delta_d < 0.0):
+        if not self.normal and has_eq and not (self._copt.regularization != 0 and reg.delta_d < 0.0):
             raise ValueError("the condensed KKT system needs dual regularization delta_d < 0 "
                              "when the problem has equality constraints")
         self.H = None if q0.H is None else st("H")
@@ -66,19 +103,26 @@ class BatchedMPCSolver:
         self.x0, self.y0 = st("x0"), st("y0")
         self._h = None
         self.status = self.iters = self.scalars = None
+        self.pre_create_hook = None  # called with the solver after the torch set-up, before the library sees the arrays
 
     # ---- src/solver.jl:127-159, vectorised over the batch ----
     def initialize(self):
         opt, be, dev = self.opt, self.be, self.be.device
         B, nx, n, m = self.B, self.nx, self.n, self.m
         f64 = dict(dtype=torch.float64, device=dev)
-        ineq = torch.as_tensor(self.ind_ineq, dtype=torch.int64, device=dev)
         one = torch.ones((), **f64)
         x = torch.zeros((B, n), **f64)
         x[:, :nx] = self.x0
         y = self.y0.clone()
-        xl = torch.cat([self.lvar, self.lcon[:, ineq]], dim=1)
-        xu = torch.cat([self.uvar, self.ucon[:, ineq]], dim=1)
+        if self.pat is None:
+            ineq = torch.as_tensor(self.ind_ineq, dtype=torch.int64, device=dev)
+            rows = lambda a, pad: a[:, ineq]
+        else:  # slack k of problem b: row gather[b, k]; the padding gets -inf / +inf bounds, scale 1 (and x = 0)
+            gather = torch.as_tensor(self.pat["gather"], device=dev)
+            mask = torch.as_tensor(self.pat["mask"], device=dev)
+            rows = lambda a, pad: torch.where(mask, a.gather(1, gather), torch.full_like(gather, pad, dtype=a.dtype))
+        xl = torch.cat([self.lvar, rows(self.lcon, -np.inf)], dim=1)
+        xu = torch.cat([self.uvar, rows(self.ucon, np.inf)], dim=1)
         rhs = torch.where(self.lcon == self.ucon, self.lcon, torch.zeros_like(self.lcon))
         tol = opt.bound_relax_factor
         xl = torch.where(torch.isfinite(xl), xl - torch.maximum(one, xl.abs()) * tol, xl)
@@ -100,9 +144,10 @@ class BatchedMPCSolver:
             cs = self.con_scale
             y = y / cs
             rhs = rhs * cs
-            x[:, nx:] *= cs[:, ineq]
-            xl[:, nx:] *= cs[:, ineq]
-            xu[:, nx:] *= cs[:, ineq]
+            cs_s = rows(cs, 1.0)
+            x[:, nx:] *= cs_s
+            xl[:, nx:] *= cs_s
+            xu[:, nx:] *= cs_s
             A = (cs[:, :, None] * A).contiguous()
             H = None if H is None else (self.obj_scale[:, None, None] * H).contiguous()
             q = self.obj_scale[:, None] * q
@@ -114,11 +159,21 @@ class BatchedMPCSolver:
         data = CBatchData(H=ptr(self._H), A=ptr(self._A), q=ptr(self._q), rhs=ptr(self._rhs), c0=ptr(self._c0),
                           x=ptr(self.x), xl=ptr(self.xl), xu=ptr(self.xu), zl=ptr(self.zl), zu=ptr(self.zu),
                           y=ptr(self.y))
-        ineq_host = (C.c_int64 * max(1, self.ns))(*[int(i) for i in self.ind_ineq])
+        if self.pre_create_hook is not None:
+            self.pre_create_hook(self)
         h = C.c_void_p()
-        be._ck(be.lib.madqp_batch_create(be.ctx, B, nx, m, self.ns, ineq_host, self.nlb, ptr(self.ind_lb),
-                                         self.nub, ptr(self.ind_ub), C.byref(data), C.byref(self._copt),
-                                         C.byref(h)))
+        if self.pat is None:
+            ineq_host = (C.c_int64 * max(1, self.ns))(*[int(i) for i in self.ind_ineq])
+            be._ck(be.lib.madqp_batch_create(be.ctx, B, nx, m, self.ns, ineq_host, self.nlb, ptr(self.ind_lb),
+                                             self.nub, ptr(self.ind_ub), C.byref(data), C.byref(self._copt),
+                                             C.byref(h)))
+        else:
+            arr = {k: np.ascontiguousarray(self.pat[k], dtype=np.int64)
+                   for k in ("ineq_ptr", "ind_ineq", "lb_ptr", "ind_lb", "ub_ptr", "ind_ub")}
+            p64 = lambda k: arr[k].ctypes.data_as(C.POINTER(C.c_int64)) if arr[k].size else None
+            be._ck(be.lib.madqp_batch_create_patterns(be.ctx, B, nx, m, p64("ineq_ptr"), p64("ind_ineq"), p64("lb_ptr"),
+                                                      p64("ind_lb"), p64("ub_ptr"), p64("ind_ub"), C.byref(data),
+                                                      C.byref(self._copt), C.byref(h)))
         self._h = h
         be._ck(be.lib.madqp_batch_init(h, opt.mu_init, opt.bound_fac))
 

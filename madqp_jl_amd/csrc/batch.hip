@@ -18,6 +18,9 @@
 // rules, Gondzio's corrections and the x100 regularization retry of src/linear_solver.jl:6-17 (two extra, masked
 // assembly + Cholesky rounds per iteration that only the problems whose factorisation failed take part in) are in,
 // and so is the reference's own formulation: normal equations A Sigma^-1 A' of order m (opt.kkt_form = 1, LP only).
+// The problems share (nx, m); which bounds are finite and which rows are inequalities may differ from problem to problem
+// (madqp_batch_create_patterns): the MFMA work does not depend on it, the workgroup programs take problem b's counts and
+// list offsets from its row of the pattern table (BQ::pat), its [B][n] arrays at stride nx + max ns_b.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -39,11 +42,19 @@ static_assert(S_COUNT == MADQP_BATCH_SCALARS, "scalar block layout is part of th
 
 enum { ST_ACTIVE = 0, ST_SOLVED = 1, ST_MAXITER = 6, ST_STEP_ERROR = -3, ST_INTERNAL = -1 };
 
+// Per-problem pattern (PAT_LEN int64 per problem, bq.pat): problem b has its own number of slacks ns_b (n_b = nx + ns_b),
+// of finite lower / upper bounds, and offsets into the index lists and into the arrays of length nlb / nub.  A batch made by
+// madqp_batch_create has one list of each kind that every problem points at (list offsets 0, storage offsets b * nlb);
+// madqp_batch_create_patterns concatenates the problems' own lists (list offset == storage offset).
+enum { P_NS = 0, P_NLB, P_NUB, P_INEQ, P_LB, P_UB, P_LBS, P_UBS, P_SLOT, PAT_LEN };
+
 struct BQ {  // device view of the batch (by value in the kernel arguments); problem b at offset b * length
-    int64_t B, nx, m, ns, n, nlb, nub, ntot, ldk, npad, kpad, nblk;
+    // nst = nx + max_b ns_b: stride of the [B][n] arrays; ntst = max_b (n_b + m + nlb_b + nub_b): stride of d, p, w1, w2
+    int64_t B, nx, m, nst, ntst, ldk, npad, kpad, nblk;
     int64_t dim;     // order of the factorised matrix: nx (condensed) or m (normal equations)
     int32_t normal;  // 1: the reference's NormalKKTSystem (src/KKT/normalkkt.jl), LP only
-    const int64_t *ind_lb, *ind_ub, *ind_ineq, *slot;
+    const int64_t* pat;  // [B][PAT_LEN]
+    const int64_t *ind_lb, *ind_ub, *ind_ineq, *slot;  // slot: m entries per problem at pat[P_SLOT], -1 on equality rows
     const double *H, *A, *q, *rhs, *c0;
     double *x, *xl, *xu, *zl, *zu, *y;
     double *f, *c, *jacl, *reg, *pr_diag, *du_diag, *d, *p, *w1, *w2;
@@ -64,34 +75,37 @@ struct BQ {  // device view of the batch (by value in the kernel arguments); pro
     double mu_init, bound_fac;
 };
 
+// the pattern words are uniform across the workgroup: scalar loads, read once at the top of a program
 __device__ __forceinline__ madqp_state state_of(const BQ& q, int64_t b) {
+    const int64_t* pt = q.pat + b * PAT_LEN;
+    const int64_t nlb = pt[P_NLB], nub = pt[P_NUB], lbs = pt[P_LBS], ubs = pt[P_UBS];
     madqp_state s;
-    s.n = q.n;
+    s.n = q.nx + pt[P_NS];
     s.m = q.m;
-    s.nlb = q.nlb;
-    s.nub = q.nub;
-    s.ind_lb = q.ind_lb;
-    s.ind_ub = q.ind_ub;
-    s.x = q.x + b * q.n;
-    s.xl = q.xl + b * q.n;
-    s.xu = q.xu + b * q.n;
-    s.zl = q.zl + b * q.n;
-    s.zu = q.zu + b * q.n;
-    s.f = q.f + b * q.n;
+    s.nlb = nlb;
+    s.nub = nub;
+    s.ind_lb = q.ind_lb + pt[P_LB];
+    s.ind_ub = q.ind_ub + pt[P_UB];
+    s.x = q.x + b * q.nst;
+    s.xl = q.xl + b * q.nst;
+    s.xu = q.xu + b * q.nst;
+    s.zl = q.zl + b * q.nst;
+    s.zu = q.zu + b * q.nst;
+    s.f = q.f + b * q.nst;
     s.y = q.y + b * q.m;
     s.c = q.c + b * q.m;
-    s.jacl = q.jacl + b * q.n;
-    s.d = q.d + b * q.ntot;
-    s.p = q.p + b * q.ntot;
-    s.correction_lb = q.corr_lb + b * q.nlb;
-    s.correction_ub = q.corr_ub + b * q.nub;
-    s.reg = q.reg + b * q.n;
-    s.pr_diag = q.pr_diag + b * q.n;
+    s.jacl = q.jacl + b * q.nst;
+    s.d = q.d + b * q.ntst;
+    s.p = q.p + b * q.ntst;
+    s.correction_lb = q.corr_lb + lbs;
+    s.correction_ub = q.corr_ub + ubs;
+    s.reg = q.reg + b * q.nst;
+    s.pr_diag = q.pr_diag + b * q.nst;
     s.du_diag = q.du_diag + b * q.m;
-    s.l_diag = q.l_diag + b * q.nlb;
-    s.l_lower = q.l_lower + b * q.nlb;
-    s.u_diag = q.u_diag + b * q.nub;
-    s.u_lower = q.u_lower + b * q.nub;
+    s.l_diag = q.l_diag + lbs;
+    s.l_lower = q.l_lower + lbs;
+    s.u_diag = q.u_diag + ubs;
+    s.u_lower = q.u_lower + ubs;
     return s;
 }
 
@@ -101,9 +115,16 @@ struct Prob {
     double *theta, *t, *u, *K, *S, *winv, *tmp, *tn, *w1, *scal, *sym;
     double *hx, *raw_h, *raw_at, *at;
     double c0;
+    int64_t ns, ntot;  // slacks of this problem; length of its [x | y | zl | zu] (the used part of d, p, w1, w2)
+    const int64_t *ind_ineq, *slot;
 };
 __device__ __forceinline__ Prob prob_of(const BQ& q, int64_t b) {
+    const int64_t* pt = q.pat + b * PAT_LEN;
     Prob p;
+    p.ns = pt[P_NS];
+    p.ntot = q.nx + p.ns + q.m + pt[P_NLB] + pt[P_NUB];
+    p.ind_ineq = q.ind_ineq + pt[P_INEQ];
+    p.slot = q.slot + pt[P_SLOT];
     p.H = q.H ? q.H + b * q.nx * q.nx : nullptr;
     p.A = q.A + b * q.m * q.nx;
     p.qv = q.q + b * q.nx;
@@ -115,13 +136,13 @@ __device__ __forceinline__ Prob prob_of(const BQ& q, int64_t b) {
     p.S = q.S + b * q.kpad * q.npad;
     p.winv = q.winv + b * q.nblk * WBLK;
     p.tmp = q.tmp + b * q.npad;
-    p.tn = q.tn ? q.tn + b * q.n : nullptr;
+    p.tn = q.tn ? q.tn + b * q.nst : nullptr;
     p.sym = q.sym ? q.sym + b * q.sym_len : nullptr;
     p.hx = q.hx ? q.hx + b * q.nx : nullptr;
     p.raw_h = q.hx ? q.raw_h + b * q.nx : nullptr;
     p.raw_at = q.hx ? q.raw_at + b * q.nx : nullptr;
     p.at = q.at ? q.at + b * q.nx : nullptr;
-    p.w1 = q.w1 + b * q.ntot;
+    p.w1 = q.w1 + b * q.ntst;
     p.scal = q.scal + b * S_COUNT;
     p.c0 = q.c0[b];
     return p;
@@ -218,7 +239,7 @@ int32_t factor_all(madqp_batch* b, const int32_t* skip, bool retry = false) {
     }
     static const bool compact = !(getenv("MADQP_BATCH_RETRY_COMPACT") && atoi(getenv("MADQP_BATCH_RETRY_COMPACT")) == 0);
     const bool lst = retry && compact;
-    GemmBatch bt{lst ? RETRY_SLOTS : q.B, q.kpad * q.npad, q.kpad * q.npad, q.ldk * q.ldk, q.nx * q.nx, q.normal ? q.m : q.n,
+    GemmBatch bt{lst ? RETRY_SLOTS : q.B, q.kpad * q.npad, q.kpad * q.npad, q.ldk * q.ldk, q.nx * q.nx, q.normal ? q.m : q.nst,
                  lst ? nullptr : skip, lst ? q.retry_list : nullptr, lst ? q.retry_count : nullptr};
     int32_t r = madqp_gemm_tn(ctx, g, MADQP_PROF_SYRK, nullptr, 0, &bt);
     if (r) return r;
@@ -241,26 +262,46 @@ extern "C" int32_t madqp_batch_destroy(madqp_batch* b) {
     return MADQP_OK;
 }
 
-extern "C" int32_t madqp_batch_create(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, int64_t ns,
-                                      const int64_t* ind_ineq_host, int64_t nlb, const int64_t* ind_lb,
-                                      int64_t nub, const int64_t* ind_ub, const madqp_batch_data* data,
-                                      const madqp_mpc_options* opt, madqp_batch** out) {
-    if (!ctx) return MADQP_ERR_ARG;
-    ARG_TRY(ctx, out && data && opt && B >= 1 && B <= 65535 && nx >= 0 && m >= 0 && ns >= 0 && ns <= m);
-    ARG_TRY(ctx, nlb >= 0 && nub >= 0 && (nlb == 0 || ind_lb) && (nub == 0 || ind_ub) && (ns == 0 || ind_ineq_host));
-    ARG_TRY(ctx, (nx == 0 || (data->q && data->x && data->xl && data->xu && data->zl && data->zu)) &&
-                     (m == 0 || (data->A && data->rhs && data->y)) && data->c0);
-    ARG_TRY(ctx, opt->step_rule >= 0 && opt->step_rule <= 2 && opt->max_ncorr >= 0 && opt->regularization >= 0 &&
-                     opt->regularization <= 2);
+namespace {
+// What the two creation entry points hand to create_batch: the per-problem pattern table, the slack lists and slack maps
+// on the host, the bound lists on the device (borrowed, or copied by the caller into arrays the batch owns).
+struct PatternHost {
+    std::vector<int64_t> pat;       // [B][PAT_LEN]
+    std::vector<int64_t> ineq;      // every problem's ind_ineq, at pat[P_INEQ]
+    std::vector<int64_t> slot;      // m entries per distinct pattern, at pat[P_SLOT]
+    int64_t ns_max = 0, ntot_max = 0, nlb_total = 0, nub_total = 0;
+    bool any_eq = false;  // some problem has an equality row
+};
+
+// slot map of one problem's ind_ineq (strictly increasing rows in [0, m)): row -> slack index or -1
+bool append_slots(const int64_t* ineq, int64_t ns, int64_t m, std::vector<int64_t>& slot) {
+    const size_t base = slot.size();
+    slot.resize(base + (size_t)m, -1);
+    for (int64_t k = 0; k < ns; ++k) {
+        const int64_t r = ineq[k];
+        if (!(r >= 0 && r < m && (k == 0 || ineq[k - 1] < r))) return false;
+        slot[base + (size_t)r] = k;
+    }
+    return true;
+}
+
+int32_t create_batch(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, PatternHost& ph, const int64_t* ind_lb,
+                     const int64_t* ind_ub, std::vector<void*>&& owned, const madqp_batch_data* data,
+                     const madqp_mpc_options* opt, madqp_batch** out) {
     const int32_t normal = opt->kkt_form;
-    ARG_TRY(ctx, normal == 0 || normal == 1);
-    ARG_TRY(ctx, !normal || !data->H);  // NormalKKTSystem supports only linear programs (src/KKT/normalkkt.jl:45-48)
     // the condensed form needs delta_d < 0 on equality rows (conventions)
-    ARG_TRY(ctx, normal || ns == m || (opt->regularization != 0 && opt->delta_d < 0.0));
+    if (!normal && ph.any_eq && !(opt->regularization != 0 && opt->delta_d < 0.0)) {
+        for (void* p : owned) (void)hipFree(p);
+        return madqp_fail(ctx, MADQP_ERR_ARG, "bad argument: the condensed form needs delta_d < 0 on equality rows");
+    }
     *out = nullptr;
     madqp_batch* b = new (std::nothrow) madqp_batch();
-    if (!b) return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
+    if (!b) {
+        for (void* p : owned) (void)hipFree(p);
+        return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
+    }
     b->ctx = ctx;
+    b->owned = std::move(owned);
     // measured at (512, 256): 512 threads per problem are faster up to B = 512 and equal at 1024
     static const int wide_max = getenv("MADQP_BATCH_WIDE_MAX") ? atoi(getenv("MADQP_BATCH_WIDE_MAX")) : 1024;
     b->wide = B <= wide_max;
@@ -269,11 +310,8 @@ extern "C" int32_t madqp_batch_create(madqp_ctx* ctx, int64_t B, int64_t nx, int
     q.B = B;
     q.nx = nx;
     q.m = m;
-    q.ns = ns;
-    q.n = nx + ns;
-    q.nlb = nlb;
-    q.nub = nub;
-    q.ntot = q.n + m + nlb + nub;
+    q.nst = nx + ph.ns_max;
+    q.ntst = ph.ntot_max;
     q.normal = normal;
     q.dim = normal ? m : nx;
     q.npad = std::max<int64_t>(128, (q.dim + 127) / 128 * 128);
@@ -294,37 +332,30 @@ extern "C" int32_t madqp_batch_create(madqp_ctx* ctx, int64_t B, int64_t nx, int
     q.zu = data->zu;
     q.y = data->y;
     q.opt = *opt;
-    std::vector<int64_t> slot((size_t)std::max<int64_t>(m, 1), -1);
-    for (int64_t k = 0; k < ns; ++k) {
-        const int64_t r = ind_ineq_host[k];
-        if (!(r >= 0 && r < m && slot[r] < 0 && (k == 0 || ind_ineq_host[k - 1] < r))) {
-            delete b;
-            return madqp_fail(ctx, MADQP_ERR_ARG, "ind_ineq must be strictly increasing row indices");
-        }
-        slot[r] = k;
-    }
+    const int64_t nst = q.nst, ntst = q.ntst, nlbt = ph.nlb_total, nubt = ph.nub_total;
     int32_t r = MADQP_OK;
-    int64_t *d_ineq = nullptr, *d_slot = nullptr;
+    int64_t *d_pat = nullptr, *d_ineq = nullptr, *d_slot = nullptr;
 #define BALLOC(ptr, count, ...)                                   \
     if (r == MADQP_OK) r = dalloc(b, &(ptr), (count), ##__VA_ARGS__)
-    BALLOC(d_ineq, ns);
-    BALLOC(d_slot, m);
-    BALLOC(q.f, B * q.n);
+    BALLOC(d_pat, B * PAT_LEN);
+    BALLOC(d_ineq, (int64_t)ph.ineq.size());
+    BALLOC(d_slot, (int64_t)ph.slot.size());
+    BALLOC(q.f, B * nst);
     BALLOC(q.c, B * m);
-    BALLOC(q.jacl, B * q.n);
-    BALLOC(q.reg, B * q.n);
-    BALLOC(q.pr_diag, B * q.n);
+    BALLOC(q.jacl, B * nst);
+    BALLOC(q.reg, B * nst);
+    BALLOC(q.pr_diag, B * nst);
     BALLOC(q.du_diag, B * m);
-    BALLOC(q.d, B * q.ntot);
-    BALLOC(q.p, B * q.ntot);
-    BALLOC(q.w1, B * q.ntot);
-    BALLOC(q.w2, opt->max_ncorr > 0 ? B * q.ntot : 1);
-    BALLOC(q.l_diag, B * nlb);
-    BALLOC(q.l_lower, B * nlb);
-    BALLOC(q.u_diag, B * nub);
-    BALLOC(q.u_lower, B * nub);
-    BALLOC(q.corr_lb, B * nlb);
-    BALLOC(q.corr_ub, B * nub);
+    BALLOC(q.d, B * ntst);
+    BALLOC(q.p, B * ntst);
+    BALLOC(q.w1, B * ntst);
+    BALLOC(q.w2, opt->max_ncorr > 0 ? B * ntst : 1);
+    BALLOC(q.l_diag, nlbt);
+    BALLOC(q.l_lower, nlbt);
+    BALLOC(q.u_diag, nubt);
+    BALLOC(q.u_lower, nubt);
+    BALLOC(q.corr_lb, nlbt);
+    BALLOC(q.corr_ub, nubt);
     BALLOC(q.theta, B * m);
     BALLOC(q.t, B * m);
     BALLOC(q.u, B * m);
@@ -332,7 +363,7 @@ extern "C" int32_t madqp_batch_create(madqp_ctx* ctx, int64_t B, int64_t nx, int
     BALLOC(q.S, B * q.kpad * q.npad);
     BALLOC(q.winv, B * q.nblk * WBLK, true);  // potf2_inv_kernel writes the lower parts only
     BALLOC(q.tmp, B * q.npad);
-    if (normal) BALLOC(q.tn, B * q.n);
+    if (normal) BALLOC(q.tn, B * nst);
     {  // H products from the lower triangle (MADQP_BATCH_SYMV=0: full-matrix passes)
         static const bool symv = !(getenv("MADQP_BATCH_SYMV") && atoi(getenv("MADQP_BATCH_SYMV")) == 0);
         q.sym_len = (512 / 64 + 1) * 512;  // SYM_DOUBLES of the widest workgroup program
@@ -361,19 +392,140 @@ extern "C" int32_t madqp_batch_create(madqp_ctx* ctx, int64_t B, int64_t nx, int
     BALLOC(q.retry_count, 4, true);
     BALLOC(b->d_active, 1, true);
 #undef BALLOC
-    if (r == MADQP_OK && ns &&
-        hipMemcpy(d_ineq, ind_ineq_host, ns * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess)
-        r = madqp_fail(ctx, MADQP_ERR_HIP, "copy of ind_ineq failed");
-    if (r == MADQP_OK && m && hipMemcpy(d_slot, slot.data(), m * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess)
-        r = madqp_fail(ctx, MADQP_ERR_HIP, "copy of the slack map failed");
+    auto up = [&](int64_t* dst, const std::vector<int64_t>& src, const char* what) {
+        if (r == MADQP_OK && !src.empty() &&
+            hipMemcpy(dst, src.data(), src.size() * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess)
+            r = madqp_fail(ctx, MADQP_ERR_HIP, "copy of %s failed", what);
+    };
+    up(d_pat, ph.pat, "the pattern table");
+    up(d_ineq, ph.ineq, "ind_ineq");
+    up(d_slot, ph.slot, "the slack map");
     if (r != MADQP_OK) {
         madqp_batch_destroy(b);
         return r;
     }
+    q.pat = d_pat;
     q.ind_ineq = d_ineq;
     q.slot = d_slot;
     *out = b;
     return MADQP_OK;
+}
+
+int32_t check_common(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, const madqp_batch_data* data,
+                     const madqp_mpc_options* opt, madqp_batch** out) {
+    ARG_TRY(ctx, out && data && opt && B >= 1 && B <= 65535 && nx >= 0 && m >= 0);
+    ARG_TRY(ctx, (nx == 0 || (data->q && data->x && data->xl && data->xu && data->zl && data->zu)) &&
+                     (m == 0 || (data->A && data->rhs && data->y)) && data->c0);
+    ARG_TRY(ctx, opt->step_rule >= 0 && opt->step_rule <= 2 && opt->max_ncorr >= 0 && opt->regularization >= 0 &&
+                     opt->regularization <= 2);
+    ARG_TRY(ctx, opt->kkt_form == 0 || opt->kkt_form == 1);
+    ARG_TRY(ctx, !opt->kkt_form || !data->H);  // NormalKKTSystem supports only linear programs (src/KKT/normalkkt.jl:45-48)
+    return MADQP_OK;
+}
+}  // namespace
+
+extern "C" int32_t madqp_batch_create(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, int64_t ns,
+                                      const int64_t* ind_ineq_host, int64_t nlb, const int64_t* ind_lb,
+                                      int64_t nub, const int64_t* ind_ub, const madqp_batch_data* data,
+                                      const madqp_mpc_options* opt, madqp_batch** out) {
+    if (!ctx) return MADQP_ERR_ARG;
+    if (int32_t r = check_common(ctx, B, nx, m, data, opt, out)) return r;
+    ARG_TRY(ctx, ns >= 0 && ns <= m);
+    ARG_TRY(ctx, nlb >= 0 && nub >= 0 && (nlb == 0 || ind_lb) && (nub == 0 || ind_ub) && (ns == 0 || ind_ineq_host));
+    // one pattern: every problem points at the same lists and slack map, its nlb / nub arrays at b * nlb / b * nub
+    PatternHost ph;
+    if (!append_slots(ind_ineq_host, ns, m, ph.slot))
+        return madqp_fail(ctx, MADQP_ERR_ARG, "ind_ineq must be strictly increasing row indices");
+    ph.ineq.assign(ind_ineq_host, ind_ineq_host + ns);
+    ph.pat.resize((size_t)(B * PAT_LEN));
+    for (int64_t bb = 0; bb < B; ++bb) {
+        int64_t* pt = ph.pat.data() + bb * PAT_LEN;
+        pt[P_NS] = ns;
+        pt[P_NLB] = nlb;
+        pt[P_NUB] = nub;
+        pt[P_INEQ] = pt[P_LB] = pt[P_UB] = pt[P_SLOT] = 0;
+        pt[P_LBS] = bb * nlb;
+        pt[P_UBS] = bb * nub;
+    }
+    ph.ns_max = ns;
+    ph.ntot_max = nx + ns + m + nlb + nub;
+    ph.nlb_total = B * nlb;
+    ph.nub_total = B * nub;
+    ph.any_eq = ns < m;
+    return create_batch(ctx, B, nx, m, ph, ind_lb, ind_ub, {}, data, opt, out);
+}
+
+extern "C" int32_t madqp_batch_create_patterns(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, const int64_t* ineq_ptr,
+                                               const int64_t* ind_ineq_host, const int64_t* lb_ptr,
+                                               const int64_t* ind_lb_host, const int64_t* ub_ptr,
+                                               const int64_t* ind_ub_host, const madqp_batch_data* data,
+                                               const madqp_mpc_options* opt, madqp_batch** out) {
+    if (!ctx) return MADQP_ERR_ARG;
+    if (int32_t r = check_common(ctx, B, nx, m, data, opt, out)) return r;
+    ARG_TRY(ctx, ineq_ptr && lb_ptr && ub_ptr);
+    auto csr_ok = [&](const int64_t* ptr, const int64_t* list) {
+        if (ptr[0] != 0) return false;
+        for (int64_t bb = 0; bb < B; ++bb)
+            if (ptr[bb + 1] < ptr[bb]) return false;
+        return ptr[B] == 0 || list != nullptr;
+    };
+    if (!csr_ok(ineq_ptr, ind_ineq_host) || !csr_ok(lb_ptr, ind_lb_host) || !csr_ok(ub_ptr, ind_ub_host))
+        return madqp_fail(ctx, MADQP_ERR_ARG, "madqp_batch_create_patterns: a *_ptr array must start at 0 and not decrease"
+                                              " (and a non-empty list needs its array)");
+    PatternHost ph;
+    ph.pat.resize((size_t)(B * PAT_LEN));
+    ph.nlb_total = lb_ptr[B];
+    ph.nub_total = ub_ptr[B];
+    for (int64_t bb = 0; bb < B; ++bb) {
+        const int64_t ns = ineq_ptr[bb + 1] - ineq_ptr[bb], nlb = lb_ptr[bb + 1] - lb_ptr[bb],
+                      nub = ub_ptr[bb + 1] - ub_ptr[bb], n = nx + ns;
+        if (ns > m)
+            return madqp_fail(ctx, MADQP_ERR_ARG, "madqp_batch_create_patterns: problem %lld has %lld slacks > m = %lld",
+                              (long long)bb, (long long)ns, (long long)m);
+        if (!append_slots(ind_ineq_host + ineq_ptr[bb], ns, m, ph.slot))
+            return madqp_fail(ctx, MADQP_ERR_ARG,
+                              "madqp_batch_create_patterns: ind_ineq of problem %lld must be strictly increasing in [0, m)",
+                              (long long)bb);
+        auto inc = [&](const int64_t* l, int64_t len) {
+            for (int64_t k = 0; k < len; ++k)
+                if (!(l[k] >= 0 && l[k] < n && (k == 0 || l[k - 1] < l[k]))) return false;
+            return true;
+        };
+        if (!inc(ind_lb_host + lb_ptr[bb], nlb) || !inc(ind_ub_host + ub_ptr[bb], nub))
+            return madqp_fail(ctx, MADQP_ERR_ARG,
+                              "madqp_batch_create_patterns: ind_lb / ind_ub of problem %lld must be strictly increasing "
+                              "in [0, n_b)", (long long)bb);
+        int64_t* pt = ph.pat.data() + bb * PAT_LEN;
+        pt[P_NS] = ns;
+        pt[P_NLB] = nlb;
+        pt[P_NUB] = nub;
+        pt[P_INEQ] = ineq_ptr[bb];
+        pt[P_LB] = pt[P_LBS] = lb_ptr[bb];
+        pt[P_UB] = pt[P_UBS] = ub_ptr[bb];
+        pt[P_SLOT] = bb * m;
+        ph.ns_max = std::max(ph.ns_max, ns);
+        ph.ntot_max = std::max(ph.ntot_max, n + m + nlb + nub);
+        ph.any_eq = ph.any_eq || ns < m;
+    }
+    if (ineq_ptr[B]) ph.ineq.assign(ind_ineq_host, ind_ineq_host + ineq_ptr[B]);
+    // the bound lists: copied into arrays the batch owns
+    std::vector<void*> owned;
+    int64_t* d_lists[2] = {nullptr, nullptr};
+    const int64_t* hl[2] = {ind_lb_host, ind_ub_host};
+    const int64_t len[2] = {lb_ptr[B], ub_ptr[B]};
+    for (int k = 0; k < 2; ++k) {
+        const size_t bytes = (size_t)std::max<int64_t>(len[k], 1) * sizeof(int64_t);
+        hipError_t e = hipMalloc(&d_lists[k], bytes);
+        if (e == hipSuccess) {
+            owned.push_back(d_lists[k]);
+            if (len[k]) e = hipMemcpy(d_lists[k], hl[k], len[k] * sizeof(int64_t), hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) {
+            for (void* p : owned) (void)hipFree(p);
+            return madqp_fail(ctx, MADQP_ERR_HIP, "madqp_batch_create_patterns: bound lists: %s", hipGetErrorString(e));
+        }
+    }
+    return create_batch(ctx, B, nx, m, ph, d_lists[0], d_lists[1], std::move(owned), data, opt, out);
 }
 
 // src/solver.jl:162-179 for every problem (the caller has done :127-159: bounds, interior push, scaling)

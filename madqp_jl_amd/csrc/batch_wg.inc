@@ -372,7 +372,7 @@ __device__ __forceinline__ void wg_copy(int64_t len, const double* __restrict__ 
 // MadNLP.jtprod!(out, kkt, y): out = [A' y ; -y[ind_ineq]]   (src/KKT/normalkkt.jl:162-164)
 __device__ __forceinline__ void wg_jtprod(const BQ& q, const Prob& pb, const double* y, double* out, double* scr) {
     wg_gemv_t(q.m, q.nx, 1.0, pb.A, y, 0.0, out, scr);
-    wg::jt_slack_kernel(q.ns, q.ind_ineq, y, out + q.nx, 1.0, 0.0);
+    wg::jt_slack_kernel(pb.ns, pb.ind_ineq, y, out + q.nx, 1.0, 0.0);
     WG_SYNC();
 }
 
@@ -393,11 +393,11 @@ __device__ __forceinline__ void wg_kkt_solve(const BQ& q, const madqp_state& s, 
         if (q.m) {
             wg_gemv_n(q.m, q.nx, 1.0, pb.A, pb.tn, 0.0, pb.u);
             WG_SYNC();
-            wg::normal_rhs_kernel(q.m, q.slot, pb.u, pb.tn + q.nx, wy, wy);  // A_full r1 - r2
+            wg::normal_rhs_kernel(q.m, pb.slot, pb.u, pb.tn + q.nx, wy, wy);  // A_full r1 - r2
             WG_SYNC();
             wg_chol_solve(pb.K, q.ldk, pb.winv, q.m, wy, pb.tmp, lds);  // dy
             wg_gemv_t(q.m, q.nx, 1.0, pb.A, wy, 0.0, pb.tn, lds + 2 * NB);  // A_full' dy
-            if (q.ns) wg::jt_slack_kernel(q.ns, q.ind_ineq, wy, pb.tn + q.nx, 1.0, 0.0);
+            if (pb.ns) wg::jt_slack_kernel(pb.ns, pb.ind_ineq, wy, pb.tn + q.nx, 1.0, 0.0);
             WG_SYNC();
         } else {
             for (int64_t i = threadIdx.x; i < s.n; i += TPB) pb.tn[i] = 0.0;
@@ -410,7 +410,7 @@ __device__ __forceinline__ void wg_kkt_solve(const BQ& q, const madqp_state& s, 
         return;
     }
     if (q.m) {
-        wg::condense_kernel(q.m, q.nx, q.slot, s.pr_diag, pb.theta, wx, wy, pb.t, pb.u);
+        wg::condense_kernel(q.m, q.nx, pb.slot, s.pr_diag, pb.theta, wx, wy, pb.t, pb.u);
         WG_SYNC();
         wg_gemv_t(q.m, q.nx, 1.0, pb.A, pb.u, 1.0, wx, lds + 2 * NB);
         WG_SYNC();
@@ -425,7 +425,7 @@ __device__ __forceinline__ void wg_kkt_solve(const BQ& q, const madqp_state& s, 
             wg_gemv_n(q.m, q.nx, 1.0, pb.A, wx, 0.0, pb.u);
         WG_SYNC();
         BSTAMP(4);
-        wg::decondense_kernel(q.m, q.nx, q.slot, s.pr_diag, pb.theta, pb.t, pb.u, wx, wy);
+        wg::decondense_kernel(q.m, q.nx, pb.slot, s.pr_diag, pb.theta, pb.t, pb.u, wx, wy);
         WG_SYNC();
     }
     if (s.nlb || s.nub) wg::finish_aug_solve_kernel(s, w);
@@ -458,12 +458,12 @@ __device__ __forceinline__ void wg_kkt_mul(const BQ& q, const madqp_state& s, co
         WG_SYNC();
     }
     BSTAMP(7);
-    if (q.ns) wg::jt_slack_kernel(q.ns, q.ind_ineq, v + n, w + nx, alpha, beta);
+    if (pb.ns) wg::jt_slack_kernel(pb.ns, pb.ind_ineq, v + n, w + nx, alpha, beta);
     if (q.m) {
         if (!have_Av) wg_gemv_n(q.m, nx, 1.0, pb.A, v, 0.0, pb.u);
         WG_SYNC();
         BSTAMP(8);
-        wg::mul_rows_kernel(q.m, q.slot, pb.u, v + nx, w + n, alpha, beta);
+        wg::mul_rows_kernel(q.m, pb.slot, pb.u, v + nx, w + n, alpha, beta);
     }
     WG_SYNC();
     wg::kktmul_diag_kernel(s, w, v, alpha);
@@ -479,14 +479,14 @@ __device__ __forceinline__ void wg_kkt_mul(const BQ& q, const madqp_state& s, co
 template <bool NT = false>
 __device__ __forceinline__ bool wg_solve_system(const BQ& q, const madqp_state& s, const Prob& pb, double* lds, double* red,
                                                 bool keep = false) {
-    wg_copy(q.ntot, s.p, s.d);
+    wg_copy(pb.ntot, s.p, s.d);
     WG_SYNC();
     wg_kkt_solve<NT>(q, s, pb, s.d, lds);
-    wg_copy(q.ntot, s.p, pb.w1);
+    wg_copy(pb.ntot, s.p, pb.w1);
     WG_SYNC();
     wg_kkt_mul(q, s, pb, pb.w1, s.d, -1.0, 1.0, lds + 2 * NB, /*have_Av=*/!q.normal && q.m > 0, keep && pb.hx,
                /*have_At=*/NT && pb.at && !q.normal && q.m > 0);
-    wg::norm_inf3_kernel(q.ntot, pb.w1, s.p, s.d, red);
+    wg::norm_inf3_kernel(pb.ntot, pb.w1, s.p, s.d, red);
     WG_SYNC();
     const double ratio = red[0] / fmax(1.0, red[1]);
     WG_SYNC();
@@ -507,7 +507,7 @@ __device__ __forceinline__ double wg_eval_model(const BQ& q, const madqp_state& 
     if (q.m) {
         wg_gemv_n(q.m, q.nx, 1.0, pb.A, s.x, 0.0, s.c);
         WG_SYNC();
-        wg::eval_cons_kernel(q.m, q.slot, s.x + q.nx, pb.rhs, s.c);
+        wg::eval_cons_kernel(q.m, pb.slot, s.x + q.nx, pb.rhs, s.c);
         WG_SYNC();
     }
     BSTAMP(11);
@@ -536,7 +536,7 @@ __device__ __forceinline__ double wg_eval_model_incr(const BQ& q, const madqp_st
     const double obj = pb.c0 + red[0] + 0.5 * red[1];
     WG_SYNC();
     for (int64_t i = threadIdx.x; i < q.m; i += TPB) {
-        const int64_t k = q.slot[i];
+        const int64_t k = pb.slot[i];
         const double ds = k >= 0 ? s.d[q.nx + k] : 0.0;
         s.c[i] += alpha_p * (pb.u[i] - ds);
     }
@@ -624,7 +624,7 @@ __device__ __forceinline__ void wg_mehrotra_adaptive_step(const madqp_state& s, 
 __device__ __forceinline__ bool wg_gondzio(const BQ& q, int64_t b, const madqp_state& s, const Prob& pb,
                                                     double mu_curr, double* lds, double* red) {
     const double delta = 0.1, bmin = 0.1, bmax = 10.0, tau_g = 0.995;
-    double* w2 = q.w2 + b * q.ntot;
+    double* w2 = q.w2 + b * q.ntst;
     double ap, ad;
     wg_fraction_to_boundary(s, tau_g, red, ap, ad);
     for (int c = 0; c < q.opt.max_ncorr; ++c) {
@@ -634,13 +634,13 @@ __device__ __forceinline__ bool wg_gondzio(const BQ& q, int64_t b, const madqp_s
         wg::extra_correction_kernel(s, ta_p, ta_d, bmin * mu_g, bmax * mu_g, nullptr, nullptr);
         WG_SYNC();
         wg::rhs_kernel(s, 1, mu_g, nullptr);
-        wg_copy(q.ntot, s.d, w2);
+        wg_copy(pb.ntot, s.d, w2);
         WG_SYNC();
         if (!wg_solve_system(q, s, pb, lds, red)) return false;
         double ha_p, ha_d;
         wg_fraction_to_boundary(s, tau_g, red, ha_p, ha_d);
         if (ha_p < 1.005 * ap || ha_d < 1.005 * ad) {
-            wg_copy(q.ntot, w2, s.d);
+            wg_copy(pb.ntot, w2, s.d);
             WG_SYNC();
             break;
         }
@@ -657,7 +657,7 @@ __device__ __forceinline__ void wg_build_operands(const BQ& q, const madqp_state
         // GEMM operand is S[k, i] = sqrt(1/Sigma_k) A[i, k] (variable k major, kpad x npad), theta = the diagonal part
         wg::recip_kernel(s.n, s.pr_diag, pb.tn);
         WG_SYNC();
-        if (q.m) wg::slack_diag_kernel(q.m, q.nx, q.slot, pb.tn, pb.theta);
+        if (q.m) wg::slack_diag_kernel(q.m, q.nx, pb.slot, pb.tn, pb.theta);
         for (int64_t k = threadIdx.x; k < q.kpad; k += TPB) {  // a thread per variable: reads coalesced over k
             const double sk = (k < q.nx) ? sqrt(pb.tn[k]) : 0.0;
             for (int64_t i = 0; i < q.npad; ++i)
@@ -665,7 +665,7 @@ __device__ __forceinline__ void wg_build_operands(const BQ& q, const madqp_state
         }
         return;
     }
-    if (q.m) wg::theta_kernel(q.m, q.nx, q.slot, s.pr_diag, s.du_diag, pb.theta);
+    if (q.m) wg::theta_kernel(q.m, q.nx, pb.slot, s.pr_diag, s.du_diag, pb.theta);
     WG_SYNC();
     for (int64_t i = threadIdx.x; i < q.npad; i += TPB) {  // a thread per column, 8 rows in flight
         for (int64_t k0 = 0; k0 < q.kpad; k0 += 8) {
@@ -825,7 +825,7 @@ __global__ __launch_bounds__(TPB) void bq_iter_pre_kernel(BQ q) {
     if (q.incr_ok[b] & 1) {  // A' y of the new y = y + alpha_d dy from the product the last residual check formed
         const double ad = sc[S_ALPHA_D];
         for (int64_t j = threadIdx.x; j < q.nx; j += TPB) s.jacl[j] += ad * pb.raw_at[j];
-        wg::jt_slack_kernel(q.ns, q.ind_ineq, s.y, s.jacl + q.nx, 1.0, 0.0);
+        wg::jt_slack_kernel(pb.ns, pb.ind_ineq, s.y, s.jacl + q.nx, 1.0, 0.0);
         WG_SYNC();
     } else {
         wg_jtprod(q, pb, s.y, s.jacl, lds + 2 * NB);  // :259

@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """Batch of independent QPs (BASELINE configs[3]: 1024 x (n=512, m=256)) on one GPU / one rank.
 
-    python tools/bench_batch.py [--batch 128] [--nx 512] [--m 256] [--streams 16]
+    python tools/bench_batch.py [--batch 128] [--nx 512] [--m 256] [--streams 16] [--mixed-patterns [SEED]]
 
 Under torch.distributed.run each rank takes problems rank, rank+N, ... (no communication) and rank 0
 reports the aggregate.  Prints one JSON line: QPs/s and IPM iterations/s.
+
+--mixed-patterns: the same problems, each with a bound / row pattern of its own drawn from SEED (some variables free,
+lower-only or upper-only; some rows equalities or one-sided), through the engine's per-problem patterns -- timed in
+the same call, alternately with the problems under their one shared pattern; the line then holds both and the ratio
+of problem-iterations per second (the sum of per-problem iterations over wall time).
 """
 import argparse
 import json
@@ -33,6 +38,29 @@ def batch_roofline(nx, m, iters, seconds, max_ncorr=0):
     return {"flops_per_problem_iteration": flops, "algorithmic_bytes_per_problem_iteration": 8.0 * doubles,
             "achieved_TFLOPs": tf, "frac_of_fp64_mfma_peak": tf / bench.PEAK_F64_MFMA_TFLOPS,
             "achieved_GBps_algorithmic": gbs, "frac_of_hbm_peak": gbs / bench.PEAK_HBM_GBS}
+
+
+def mixed_patterns(qps, seed):
+    """Copies of ``qps`` (DeviceQP, same data) with a pattern of their own each, drawn from ``seed``: variables 10 % free,
+    15 % lower-only, 15 % upper-only, the rest boxed; rows 10 % equalities (at 0.1), 15 % lower-only, 15 % upper-only."""
+    import copy
+
+    import numpy as np
+    import torch
+
+    rng = np.random.default_rng(seed)
+    out = []
+    for dq in qps:
+        v = torch.as_tensor(rng.random(dq.nvar), device=dq.lvar.device)
+        r = torch.as_tensor(rng.random(dq.ncon), device=dq.lcon.device)
+        c = copy.copy(dq)
+        inf = float("inf")
+        c.lvar = torch.where((v < 0.10) | ((v >= 0.25) & (v < 0.40)), -inf, dq.lvar)
+        c.uvar = torch.where(v < 0.25, inf, dq.uvar)
+        c.lcon = torch.where(r < 0.10, 0.1, torch.where((r >= 0.25) & (r < 0.40), -inf, dq.lcon))
+        c.ucon = torch.where(r < 0.10, 0.1, torch.where((r >= 0.10) & (r < 0.25), inf, dq.ucon))
+        out.append(c)
+    return out
 
 
 def run_batched(M, be, batch, nx, m, seed, repeats=3, check_every=2, profile=False):
@@ -71,6 +99,9 @@ def main():
     p.add_argument("--check-every", type=int, default=2)
     p.add_argument("--repeats", type=int, default=3, help="timed solves (fresh solver each); the median is reported")
     p.add_argument("--profile", action="store_true", help="print ms / launches per kernel class (perturbs timing)")
+    p.add_argument("--mixed-patterns", type=int, nargs="?", const=1, default=None, metavar="SEED",
+                   help="also solve the problems with a pattern of their own each (per_problem_patterns=True), "
+                        "alternately with the shared pattern; reports both (batched engine only)")
     a = p.parse_args()
     import torch
 
@@ -81,6 +112,9 @@ def main():
     make = lambda be, i: M.DeviceQP.synthetic(be, a.seed + i, a.nx, a.m)
     opts = dict(max_iter=300, step_rule=M.AdaptiveStep(0.995), regularization=M.FixedRegularization(1e-8, -1e-8),
                 mu_min=1e-12, driver=a.driver)
+    mixed = None
+    if a.mixed_patterns is not None and (a.engine != "batched" or world > 1):
+        p.error("--mixed-patterns: the batched engine on one rank")
     if a.engine == "streams":
         M.solve_batch(make, mine[: min(len(mine), a.streams)], local_rank, a.streams, **opts)  # warm-up
         bench.dist_barrier(world)
@@ -97,25 +131,39 @@ def main():
         # instantiation, allocator growth -- that later ones do not: 187 vs 37 ms at 128 problems), then the median
         # of --repeats timed solves, each with a fresh solver: set-up (scaling, start point) + all iterations +
         # read-back are inside the timed region
-        warm = M.BatchedMPCSolver(qps, be, **opts)
-        warm.solve(check_every=a.check_every)
-        warm.close()
-        times = []
+        legs = {"shared": (qps, {})}
+        if a.mixed_patterns is not None:
+            legs["mixed"] = (mixed_patterns(qps, a.mixed_patterns), dict(per_problem_patterns=True))
+        for lq, kw in legs.values():
+            warm = M.BatchedMPCSolver(lq, be, **kw, **opts)
+            warm.solve(check_every=a.check_every)
+            warm.close()
+        all_times, all_res = {k: [] for k in legs}, {}
         for _ in range(max(1, a.repeats)):
-            solver = M.BatchedMPCSolver(qps, be, **opts)
-            if a.profile:
-                be.prof_enable(M._lib.PROF_CLASSES)
-                be.prof_reset()
-            bench.dist_barrier(world)
-            t0 = time.perf_counter()
-            res = solver.solve(check_every=a.check_every)
-            bench.dist_barrier(world)
-            times.append(bench.max_over_ranks(time.perf_counter() - t0, world, torch.device("cuda", local_rank)))
-            if a.profile and rank == 0:
-                print({k: (round(v[0], 2), v[1]) for k, v in be.prof_get().items() if v[1]}, flush=True)
-            solver.close()
+            for leg, (lq, kw) in legs.items():  # (the legs alternate: drifts of the clock or the heat hit both)
+                solver = M.BatchedMPCSolver(lq, be, **kw, **opts)
+                if a.profile:
+                    be.prof_enable(M._lib.PROF_CLASSES)
+                    be.prof_reset()
+                bench.dist_barrier(world)
+                t0 = time.perf_counter()
+                all_res[leg] = solver.solve(check_every=a.check_every)
+                bench.dist_barrier(world)
+                all_times[leg].append(bench.max_over_ranks(time.perf_counter() - t0, world, torch.device("cuda", local_rank)))
+                if a.profile and rank == 0:
+                    print(leg, {k: (round(v[0], 2), v[1]) for k, v in be.prof_get().items() if v[1]}, flush=True)
+                solver.close()
+        times, res = all_times["shared"], all_res["shared"]
         dt = sorted(times)[len(times) // 2]
         lockstep = int(max(r["iter"] for r in res))
+        mixed = None
+        if "mixed" in legs:
+            mt, mres = all_times["mixed"], all_res["mixed"]
+            mdt = sorted(mt)[len(mt) // 2]
+            mit = sum(r["iter"] for r in mres)
+            mixed = {"seed": a.mixed_patterns, "QP_per_s": a.batch / mdt, "problem_iterations_per_s": mit / mdt,
+                     "solved": sum(r["status"] == M.SOLVE_SUCCEEDED for r in mres),
+                     "lock_step_iterations": int(max(r["iter"] for r in mres)), "seconds": mdt, "all_seconds": mt}
     iters = sum(r["iter"] for r in res)
     ok = sum(r["status"] == M.SOLVE_SUCCEEDED for r in res)
     if world > 1:
@@ -125,7 +173,12 @@ def main():
         dist.all_reduce(t)
         iters, ok = int(t[0].item()), int(t[1].item())
     if rank == 0:
-        print(json.dumps({"metric": "independent QPs solved per second", "value": a.batch / dt, "unit": "QP/s",
+        extra = {}
+        if mixed is not None:
+            shared_ips = iters / dt
+            extra["mixed_patterns"] = dict(mixed, shared_problem_iterations_per_s=shared_ips,
+                                           ratio_problem_iterations_per_s=mixed["problem_iterations_per_s"] / shared_ips)
+        print(json.dumps({**extra, "metric": "independent QPs solved per second", "value": a.batch / dt, "unit": "QP/s",
                           "ipm_iterations_per_s": iters / dt, "n_gpus": world, "batch": a.batch,
                           "roofline": batch_roofline(a.nx, a.m, iters, dt),
                           "solved": ok, "config": {"workload": f"{a.batch} x synthetic dense QP nx={a.nx} m={a.m}",
