@@ -464,7 +464,10 @@ typedef struct madqp_mpc_options { /* src/utils.jl:69-103 */
     double mu_min;
     double tol_linear_solve;
     int32_t refine_steps;   /* extension, default 0 = the reference's solve_system!: steps of iterative refinement
-                               d += K^-1 (p - K d) with the residual src/linear_solver.jl:29-31 already forms */
+                               d += K^-1 (p - K d) with the residual src/linear_solver.jl:29-31 already forms.  Holds for
+                               madqp_mpc_* and madqp_batch_* alike (every solve of the batched engine refines: start point,
+                               both directions, each Gondzio trial); madqp_batch_create* refuses a negative value (the AUTO
+                               value -1 belongs to madqp_kkt_set_refine) */
     int32_t kkt_form;       /* madqp_batch_* only: 0 condensed K = H + Sigma_x + A' Theta A, 1 the reference's normal
                                equations A Sigma^-1 A' (NormalKKTSystem, LP only) */
 } madqp_mpc_options;
@@ -552,6 +555,19 @@ int32_t madqp_batch_iterate(madqp_batch* b, int32_t max_steps, int32_t check_eve
 /* per problem: status (0 active, 1 SOLVE_SUCCEEDED, 6 MAXIMUM_ITERATIONS_EXCEEDED,
  * -3 ERROR_IN_STEP_COMPUTATION, -1 INTERNAL_ERROR), iterations, MADQP_BATCH_SCALARS scalars */
 int32_t madqp_batch_results(madqp_batch* b, int32_t* status_host, int32_t* iters_host, double* scal_host);
+/* Optional per-iteration trace, written on the device by the loop head (where the reference prints its line,
+ * src/solver.jl:259-283): record k of problem b holds MADQP_BATCH_TRACE_LEN doubles -- obj, inf_pr, inf_du, inf_compl, mu,
+ * dnorm, del_w, alpha_p, alpha_d, residual_ratio -- as they stand when iteration k's residuals have been formed, for every
+ * problem that entered the head active (the pass in which it stops included: a problem that stops after k iterations has
+ * k + 1 records).  The first `capacity` records are kept, later ones dropped.  The x100 retry rounds write no record.
+ * madqp_batch_set_trace allocates [B][capacity][MADQP_BATCH_TRACE_LEN] doubles owned by the handle; valid once, after
+ * either madqp_batch_create* and before madqp_batch_init (MADQP_ERR_STATE otherwise); capacity < 1: MADQP_ERR_ARG; a failed
+ * allocation returns MADQP_ERR_ALLOC and leaves the handle usable without a trace.
+ * madqp_batch_trace copies the whole buffer to trace_host and, per problem, the number of records stored
+ * (min(records written, capacity)) to count_host; either may be NULL; MADQP_ERR_STATE when no trace was set. */
+#define MADQP_BATCH_TRACE_LEN 10
+int32_t madqp_batch_set_trace(madqp_batch* b, int64_t capacity);
+int32_t madqp_batch_trace(madqp_batch* b, double* trace_host, int32_t* count_host);
 
 #ifdef __cplusplus
 }

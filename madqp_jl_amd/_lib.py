@@ -56,6 +56,8 @@ class CBatchData(C.Structure):
 
 BATCH_SCALARS = ("mu", "alpha_p", "alpha_d", "obj", "inf_pr", "inf_du", "inf_compl", "dnorm", "norm_b", "norm_c",
                  "del_w", "del_c", "residual_ratio", "reg_p", "reg_d", "n_factorizations")
+# one record of madqp_batch_trace (MADQP_BATCH_TRACE_LEN doubles)
+BATCH_TRACE = ("obj", "inf_pr", "inf_du", "inf_compl", "mu", "dnorm", "del_w", "alpha_p", "alpha_d", "residual_ratio")
 
 
 class CMpcInfo(C.Structure):
@@ -173,6 +175,8 @@ _SIGNATURES = {
     "madqp_batch_init": [vp, f64, f64],
     "madqp_batch_iterate": [vp, i32, i32, pi32],
     "madqp_batch_results": [vp, pi32, pi32, pf64],
+    "madqp_batch_set_trace": [vp, i64],
+    "madqp_batch_trace": [vp, pf64, pi32],
     "madqp_mpc_create": [vp, pstate, vp, vp, vp, vp, f64, f64, f64, C.POINTER(CMpcOptions), C.POINTER(vp)],
     "madqp_mpc_destroy": [vp],
     "madqp_mpc_set_scalars": [vp, f64, f64, f64, f64, i64],

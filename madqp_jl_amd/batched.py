@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import BATCH_SCALARS, CBatchData, ptr
+from ._lib import BATCH_SCALARS, BATCH_TRACE, CBatchData, ptr
 from .options import IPMOptions
 from .solver import _push_interior, get_index_constraints, native_options
 
@@ -46,16 +46,27 @@ def pack_patterns(lvar, uvar, lcon, ucon, fixed_variable_treatment="relax_bound"
 
 class BatchedMPCSolver:
     """``qps``: list of :class:`DeviceQP` with identical shapes and -- unless ``per_problem_patterns`` -- identical bound
-    patterns (which variables have a finite lower / upper bound, which rows are equalities)."""
+    patterns (which variables have a finite lower / upper bound, which rows are equalities).
 
-    def __init__(self, qps, backend, per_problem_patterns=False, **opts):
+    ``trace``: ``True`` records every iteration of every problem on the device (``max_iter + 1`` records per problem), a
+    positive ``int`` the first that many, ``False`` (default) none -- the library is then called exactly as without the
+    keyword.  ``refine_steps`` (an :class:`IPMOptions` field): steps of iterative refinement in every solve, as in
+    :class:`MPCSolver`; ``None`` means 0 here (the AUTO rule is ``MPCSolver``'s)."""
+
+    def __init__(self, qps, backend, per_problem_patterns=False, trace=False, **opts):
         if not qps:
             raise ValueError("empty batch")
+        if trace is not True and trace is not False:
+            if isinstance(trace, bool) or not isinstance(trace, (int, np.integer)) or trace < 1:
+                raise ValueError("trace: True, False or a positive number of records per problem")
+        self._trace = trace if isinstance(trace, bool) else int(trace)
         self.be, self.qps = backend, list(qps)
         self.per_problem = bool(per_problem_patterns)
         if any((q.nvar, q.ncon) != (qps[0].nvar, qps[0].ncon) for q in self.qps):
             raise ValueError("all problems of a batch must have the same (nx, m)")
         self.opt = IPMOptions(**opts)
+        if self.opt.refine_steps is not None and int(self.opt.refine_steps) < 0:
+            raise ValueError("refine_steps must be >= 0 (None: 0 for the batched engine)")
         if self.opt.kkt_system not in ("condensed", "normal") or self.opt.check_residual:
             raise ValueError("the batched driver supports the condensed KKT system and the normal equations, on one GPU")
         self.normal = self.opt.kkt_system == "normal"
@@ -175,6 +186,11 @@ class BatchedMPCSolver:
                                                       p64("ind_lb"), p64("ub_ptr"), p64("ind_ub"), C.byref(data),
                                                       C.byref(self._copt), C.byref(h)))
         self._h = h
+        self.trace_capacity = 0
+        if self._trace is not False:
+            cap = opt.max_iter + 1 if self._trace is True else self._trace
+            be._ck(be.lib.madqp_batch_set_trace(h, cap))
+            self.trace_capacity = cap
         be._ck(be.lib.madqp_batch_init(h, opt.mu_init, opt.bound_fac))
 
     def iterate(self, max_steps=None, check_every=1) -> int:
@@ -195,8 +211,21 @@ class BatchedMPCSolver:
         self.scalars = np.frombuffer(scal, dtype=np.float64).reshape(B, len(BATCH_SCALARS)).copy()
         return self.status, self.iters, self.scalars
 
+    def fetch_trace(self):
+        """``(records, count)``: the device's trace buffer, [B][capacity][len(BATCH_TRACE)] (``_lib.BATCH_TRACE`` names the
+        columns; ``obj`` still scaled), and how many records of each problem are stored."""
+        if not self.trace_capacity:
+            raise ValueError("the solver was made without trace=")
+        B, cap, L = self.B, self.trace_capacity, len(BATCH_TRACE)
+        buf = np.empty((B, cap, L), dtype=np.float64)
+        count = np.empty(B, dtype=np.int32)
+        self.be._ck(self.be.lib.madqp_batch_trace(self._h, buf.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  count.ctypes.data_as(C.POINTER(C.c_int32))))
+        return buf, count
+
     def solve(self, check_every=1):
-        """Returns one result dict per problem (same keys as :meth:`MPCSolver.result`, no trace)."""
+        """Returns one result dict per problem (same keys as :meth:`MPCSolver.result`; ``trace`` -- one record per
+        iteration, the keys of ``MPCSolver.record`` plus ``residual_ratio`` -- when the solver was made with ``trace=``)."""
         self.initialize()
         self.iterate(check_every=check_every)
         return self.results()
@@ -215,10 +244,16 @@ class BatchedMPCSolver:
         c_pr, c_du, c_co, c_mu, c_dw, c_nf = (col[k] for k in ("inf_pr", "inf_du", "inf_compl", "mu", "del_w",
                                                                  "n_factorizations"))
         st, it, nf = status.tolist(), iters.tolist(), scal[:, c_nf].astype(np.int64).tolist()
-        return [dict(status=st[b], iter=it[b], objective=obj[b], solution=x[b], multipliers=y[b],
-                     multipliers_L=zl[b], multipliers_U=zu[b], inf_pr=scal[b, c_pr], inf_du=scal[b, c_du],
-                     inf_compl=scal[b, c_co], mu=scal[b, c_mu], del_w=scal[b, c_dw], n_factorizations=nf[b])
-                for b in range(self.B)]
+        out = [dict(status=st[b], iter=it[b], objective=obj[b], solution=x[b], multipliers=y[b],
+                    multipliers_L=zl[b], multipliers_U=zu[b], inf_pr=scal[b, c_pr], inf_du=scal[b, c_du],
+                    inf_compl=scal[b, c_co], mu=scal[b, c_mu], del_w=scal[b, c_dw], n_factorizations=nf[b])
+               for b in range(self.B)]
+        if self.trace_capacity:
+            buf, count = self.fetch_trace()
+            buf[:, :, BATCH_TRACE.index("obj")] /= h(self.obj_scale)[:, None]
+            for b, r in enumerate(out):  # (only the stored records become Python objects: the buffer has max_iter + 1 slots)
+                r["trace"] = [dict(zip(BATCH_TRACE, rec), k=k) for k, rec in enumerate(buf[b, :count[b]].tolist())]
+        return out
 
     def close(self):
         if self._h is not None:

@@ -39,6 +39,9 @@ enum {
     S_DEL_W, S_DEL_C, S_RATIO, S_REG_P, S_REG_D, S_NFACT, S_COUNT
 };
 static_assert(S_COUNT == MADQP_BATCH_SCALARS, "scalar block layout is part of the ABI");
+// one record of the per-iteration trace (madqp_batch_set_trace)
+enum { T_OBJ = 0, T_INF_PR, T_INF_DU, T_INF_COMPL, T_MU, T_DNORM, T_DEL_W, T_ALPHA_P, T_ALPHA_D, T_RATIO, T_COUNT };
+static_assert(T_COUNT == MADQP_BATCH_TRACE_LEN, "trace record layout is part of the ABI");
 
 enum { ST_ACTIVE = 0, ST_SOLVED = 1, ST_MAXITER = 6, ST_STEP_ERROR = -3, ST_INTERNAL = -1 };
 
@@ -71,6 +74,11 @@ struct BQ {  // device view of the batch (by value in the kernel arguments); pro
     double* scal;
     int32_t *status, *iters, *info, *retry_skip;
     int32_t *retry_list, *retry_count;  // the problems of the current x100-retry round, compacted (bq_retry_kernel appends)
+    // per-iteration trace (madqp_batch_set_trace; nullptr: none): [B][trace_cap][T_COUNT], written by bq_iter_pre_kernel;
+    // trace_count[b]: records of problem b that are stored
+    double* trace;
+    int32_t* trace_count;
+    int64_t trace_cap;
     madqp_mpc_options opt;
     double mu_init, bound_fac;
 };
@@ -185,6 +193,7 @@ struct madqp_batch {
     hipEvent_t evIn = nullptr, evOut = nullptr;
     int graph_state = 0;  // 0 not tried, 1 ready, -1 unavailable
     bool wide;  // 512 threads per problem (small batches)
+    bool started = false;  // madqp_batch_init has run: BQ has gone into kernels (and soon into the graph) by value
 };
 
 namespace {
@@ -419,6 +428,7 @@ int32_t check_common(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, const mad
     ARG_TRY(ctx, opt->step_rule >= 0 && opt->step_rule <= 2 && opt->max_ncorr >= 0 && opt->regularization >= 0 &&
                      opt->regularization <= 2);
     ARG_TRY(ctx, opt->kkt_form == 0 || opt->kkt_form == 1);
+    ARG_TRY(ctx, opt->refine_steps >= 0);  // (the AUTO value -1 belongs to madqp_kkt_set_refine)
     ARG_TRY(ctx, !opt->kkt_form || !data->H);  // NormalKKTSystem supports only linear programs (src/KKT/normalkkt.jl:45-48)
     return MADQP_OK;
 }
@@ -532,6 +542,7 @@ extern "C" int32_t madqp_batch_create_patterns(madqp_ctx* ctx, int64_t B, int64_
 extern "C" int32_t madqp_batch_init(madqp_batch* b, double mu_init, double bound_fac) {
     if (!b) return MADQP_ERR_ARG;
     madqp_ctx* ctx = b->ctx;
+    b->started = true;
     b->q.mu_init = mu_init;
     b->q.bound_fac = bound_fac;
     {
@@ -545,10 +556,15 @@ extern "C" int32_t madqp_batch_init(madqp_batch* b, double mu_init, double bound
     int32_t r = factor_all(b, b->q.status);
     if (r) return r;
     ProfScope ps(ctx, MADQP_PROF_VEC);
-    if (b->wide)
-        hipLaunchKernelGGL(wg512::bq_init_post_kernel, dim3((unsigned)b->q.B), dim3(512), 0, ctx->stream, b->q);
+    const bool rf = b->q.opt.refine_steps > 0;  // refinement is a template parameter, like GONDZIO below
+    if (b->wide && rf)
+        hipLaunchKernelGGL(wg512::bq_init_post_kernel<true>, dim3((unsigned)b->q.B), dim3(512), 0, ctx->stream, b->q);
+    else if (b->wide)
+        hipLaunchKernelGGL(wg512::bq_init_post_kernel<false>, dim3((unsigned)b->q.B), dim3(512), 0, ctx->stream, b->q);
+    else if (rf)
+        hipLaunchKernelGGL(wg256::bq_init_post_kernel<true>, dim3((unsigned)b->q.B), dim3(256), 0, ctx->stream, b->q);
     else
-        hipLaunchKernelGGL(wg256::bq_init_post_kernel, dim3((unsigned)b->q.B), dim3(256), 0, ctx->stream, b->q);
+        hipLaunchKernelGGL(wg256::bq_init_post_kernel<false>, dim3((unsigned)b->q.B), dim3(256), 0, ctx->stream, b->q);
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }
@@ -580,15 +596,21 @@ static int32_t launch_iteration(madqp_batch* b) {
         if ((r = factor_all(b, q.retry_skip, true))) return r;
     }
     ProfScope ps(ctx, MADQP_PROF_VEC);
-    const bool gz = q.opt.max_ncorr > 0;
-    if (b->wide && gz)
-        hipLaunchKernelGGL(wg512::bq_iter_post_kernel<true>, dim3((unsigned)q.B), dim3(512), 0, ctx->stream, q);
-    else if (b->wide)
-        hipLaunchKernelGGL(wg512::bq_iter_post_kernel<false>, dim3((unsigned)q.B), dim3(512), 0, ctx->stream, q);
-    else if (gz)
-        hipLaunchKernelGGL(wg256::bq_iter_post_kernel<true>, dim3((unsigned)q.B), dim3(256), 0, ctx->stream, q);
-    else
-        hipLaunchKernelGGL(wg256::bq_iter_post_kernel<false>, dim3((unsigned)q.B), dim3(256), 0, ctx->stream, q);
+    const bool gz = q.opt.max_ncorr > 0, rf = q.opt.refine_steps > 0;
+#define POST(NS, T, G, R) \
+    hipLaunchKernelGGL((NS::bq_iter_post_kernel<G, R>), dim3((unsigned)q.B), dim3(T), 0, ctx->stream, q)
+    if (b->wide) {
+        if (gz && rf) POST(wg512, 512, true, true);
+        else if (gz) POST(wg512, 512, true, false);
+        else if (rf) POST(wg512, 512, false, true);
+        else POST(wg512, 512, false, false);
+    } else {
+        if (gz && rf) POST(wg256, 256, true, true);
+        else if (gz) POST(wg256, 256, true, false);
+        else if (rf) POST(wg256, 256, false, true);
+        else POST(wg256, 256, false, false);
+    }
+#undef POST
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }
@@ -681,6 +703,48 @@ extern "C" int32_t madqp_batch_results(madqp_batch* b, int32_t* status_host, int
     if (scal_host)
         HIP_TRY(ctx, hipMemcpyAsync(scal_host, q.scal, q.B * S_COUNT * sizeof(double), hipMemcpyDeviceToHost,
                                     ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return MADQP_OK;
+}
+
+// Per-iteration trace (include/madqp.h): the pointer goes into the kernels inside BQ, by value, and the first
+// madqp_batch_iterate captures the launches into a graph -- so it has to be set before anything is launched.
+extern "C" int32_t madqp_batch_set_trace(madqp_batch* b, int64_t capacity) {
+    if (!b) return MADQP_ERR_ARG;
+    madqp_ctx* ctx = b->ctx;
+    ARG_TRY(ctx, capacity >= 1);
+    if (b->started || b->q.trace)
+        return madqp_fail(ctx, MADQP_ERR_STATE, "madqp_batch_set_trace: once, and before madqp_batch_init");
+    BQ& q = b->q;
+    double* tr = nullptr;
+    int32_t* cnt = nullptr;
+    const size_t before = b->owned.size();
+    int32_t r = dalloc(b, &tr, q.B * capacity * T_COUNT, true);
+    if (r == MADQP_OK) r = dalloc(b, &cnt, q.B, true);
+    if (r != MADQP_OK) {  // the handle stays usable, without a trace
+        while (b->owned.size() > before) {
+            (void)hipFree(b->owned.back());
+            b->owned.pop_back();
+        }
+        (void)hipGetLastError();
+        return r;
+    }
+    q.trace = tr;
+    q.trace_count = cnt;
+    q.trace_cap = capacity;
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_batch_trace(madqp_batch* b, double* trace_host, int32_t* count_host) {
+    if (!b) return MADQP_ERR_ARG;
+    madqp_ctx* ctx = b->ctx;
+    const BQ& q = b->q;
+    if (!q.trace) return madqp_fail(ctx, MADQP_ERR_STATE, "madqp_batch_trace: no trace was set (madqp_batch_set_trace)");
+    if (trace_host)
+        HIP_TRY(ctx, hipMemcpyAsync(trace_host, q.trace, (size_t)(q.B * q.trace_cap * T_COUNT) * sizeof(double),
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    if (count_host)
+        HIP_TRY(ctx, hipMemcpyAsync(count_host, q.trace_count, q.B * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return MADQP_OK;
 }

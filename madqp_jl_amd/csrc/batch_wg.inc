@@ -476,7 +476,13 @@ __device__ __forceinline__ void wg_kkt_mul(const BQ& q, const madqp_state& s, co
 }
 
 // solve_system! (src/linear_solver.jl:19-45); returns false for MadNLP.SolveException
-template <bool NT = false>
+// REFINE: q.opt.refine_steps (> 0) steps of d += K^-1 (p - K d) with the residual just formed, operation for operation
+// MPCSolver.solve_system (solver.py).  A template parameter like GONDZIO: the instantiations without it are the parent's
+// programs.  What is kept "of the LAST solve's d" (pb.u = A dx, pb.raw_h = H dx, pb.raw_at = A' dy: wg_eval_model_incr and
+// the head of the next iteration consume them) then comes from the mul! of the LAST step, whose operand is the refined d:
+// that mul! forms all its products itself (have_Av = have_At = false -- pb.u and pb.at hold products of the correction's
+// solve by then), and the earlier ones keep nothing.
+template <bool NT = false, bool REFINE = false>
 __device__ __forceinline__ bool wg_solve_system(const BQ& q, const madqp_state& s, const Prob& pb, double* lds, double* red,
                                                 bool keep = false) {
     wg_copy(pb.ntot, s.p, s.d);
@@ -484,8 +490,19 @@ __device__ __forceinline__ bool wg_solve_system(const BQ& q, const madqp_state& 
     wg_kkt_solve<NT>(q, s, pb, s.d, lds);
     wg_copy(pb.ntot, s.p, pb.w1);
     WG_SYNC();
-    wg_kkt_mul(q, s, pb, pb.w1, s.d, -1.0, 1.0, lds + 2 * NB, /*have_Av=*/!q.normal && q.m > 0, keep && pb.hx,
+    wg_kkt_mul(q, s, pb, pb.w1, s.d, -1.0, 1.0, lds + 2 * NB, /*have_Av=*/!q.normal && q.m > 0, !REFINE && keep && pb.hx,
                /*have_At=*/NT && pb.at && !q.normal && q.m > 0);
+    if constexpr (REFINE) {
+        for (int step = 0; step < q.opt.refine_steps; ++step) {
+            wg_kkt_solve<false>(q, s, pb, pb.w1, lds);
+            wg::axpy_kernel(pb.ntot, 1.0, pb.w1, s.d);
+            WG_SYNC();
+            wg_copy(pb.ntot, s.p, pb.w1);
+            WG_SYNC();
+            wg_kkt_mul(q, s, pb, pb.w1, s.d, -1.0, 1.0, lds + 2 * NB, /*have_Av=*/false,
+                       keep && pb.hx && step + 1 == q.opt.refine_steps, /*have_At=*/false);
+        }
+    }
     wg::norm_inf3_kernel(pb.ntot, pb.w1, s.p, s.d, red);
     WG_SYNC();
     const double ratio = red[0] / fmax(1.0, red[1]);
@@ -621,6 +638,7 @@ __device__ __forceinline__ void wg_mehrotra_adaptive_step(const madqp_state& s, 
 }
 
 // gondzio_correction_direction! (src/solver.jl:200-251); false for MadNLP.SolveException
+template <bool REFINE>
 __device__ __forceinline__ bool wg_gondzio(const BQ& q, int64_t b, const madqp_state& s, const Prob& pb,
                                                     double mu_curr, double* lds, double* red) {
     const double delta = 0.1, bmin = 0.1, bmax = 10.0, tau_g = 0.995;
@@ -636,7 +654,7 @@ __device__ __forceinline__ bool wg_gondzio(const BQ& q, int64_t b, const madqp_s
         wg::rhs_kernel(s, 1, mu_g, nullptr);
         wg_copy(pb.ntot, s.d, w2);
         WG_SYNC();
-        if (!wg_solve_system(q, s, pb, lds, red)) return false;
+        if (!wg_solve_system<false, REFINE>(q, s, pb, lds, red)) return false;
         double ha_p, ha_d;
         wg_fraction_to_boundary(s, tau_g, red, ha_p, ha_d);
         if (ha_p < 1.005 * ap || ha_d < 1.005 * ad) {
@@ -698,6 +716,7 @@ __global__ __launch_bounds__(TPB) void bq_init_pre_kernel(BQ q) {
     if (threadIdx.x == 0) {
         q.status[b] = ST_ACTIVE;
         q.iters[b] = 0;
+        if (q.trace) q.trace_count[b] = 0;
     }
     // MadNLP.initialize!(kkt) (src/KKT/normalkkt.jl:136-147)
     wg_fill(s.n, 1.0, s.reg);
@@ -742,6 +761,7 @@ __global__ __launch_bounds__(TPB) void bq_init_pre_kernel(BQ q) {
 }
 
 // ---- second half of init_starting_point! (src/solver.jl:25-123) ---------------------------------
+template <bool REFINE>
 __global__ __launch_bounds__(TPB) void bq_init_post_kernel(BQ q) {
     __shared__ double red[32];
     __shared__ double lds[LDS_DOUBLES];
@@ -753,14 +773,14 @@ __global__ __launch_bounds__(TPB) void bq_init_post_kernel(BQ q) {
     if (status == ST_ACTIVE) {
         wg::rhs_kernel(s, 2, 0.0, nullptr);  // set_initial_primal_rhs! :25
         WG_SYNC();
-        if (!wg_solve_system(q, s, pb, lds, red)) status = ST_STEP_ERROR;
+        if (!wg_solve_system<false, REFINE>(q, s, pb, lds, red)) status = ST_STEP_ERROR;
     }
     if (status == ST_ACTIVE) {
         wg::axpy_kernel(s.n, 1.0, s.d, s.x);  // :28
         WG_SYNC();
         wg::rhs_kernel(s, 3, 0.0, nullptr);  // set_initial_dual_rhs! :31
         WG_SYNC();
-        if (!wg_solve_system(q, s, pb, lds, red)) status = ST_STEP_ERROR;
+        if (!wg_solve_system<false, REFINE>(q, s, pb, lds, red)) status = ST_STEP_ERROR;
     }
     if (status == ST_ACTIVE) {
         wg_copy(s.m, s.d + s.n, s.y);  // :33
@@ -860,6 +880,23 @@ __global__ __launch_bounds__(TPB) void bq_iter_pre_kernel(BQ q) {
     }
     WG_SYNC();
     if (threadIdx.x == 0) {
+        // the reference's print_iter line (src/structure.jl:178-195; MPCSolver.record): record number iters[b], before
+        // update_regularization! replaces del_w below -- also in the pass that ends the problem
+        const int64_t k = q.iters[b];
+        if (q.trace && k < q.trace_cap) {
+            double* tr = q.trace + (b * q.trace_cap + k) * T_COUNT;
+            tr[T_OBJ] = sc[S_OBJ];
+            tr[T_INF_PR] = inf_pr;
+            tr[T_INF_DU] = inf_du;
+            tr[T_INF_COMPL] = inf_compl;
+            tr[T_MU] = sc[S_MU];
+            tr[T_DNORM] = (k == 0) ? 0.0 : sc[S_DNORM];
+            tr[T_DEL_W] = sc[S_DEL_W];
+            tr[T_ALPHA_P] = sc[S_ALPHA_P];
+            tr[T_ALPHA_D] = sc[S_ALPHA_D];
+            tr[T_RATIO] = sc[S_RATIO];
+            q.trace_count[b] = (int32_t)(k + 1);
+        }
         sc[S_INF_PR] = inf_pr;
         sc[S_INF_DU] = inf_du;
         sc[S_INF_COMPL] = inf_compl;
@@ -918,7 +955,8 @@ __global__ __launch_bounds__(TPB) void bq_retry_kernel(BQ q) {
 // ---- the rest of the iteration after factorize!: src/solver.jl:294-343 ------------------------
 // GONDZIO is a template parameter: the correction loop costs the common max_ncorr = 0 instantiation
 // 130 VGPRs and 864 B of scratch per lane if it is merely branched around.
-template <bool GONDZIO>
+// REFINE likewise (wg_solve_system): at refine_steps == 0 the programs are the ones without it.
+template <bool GONDZIO, bool REFINE>
 __global__ __launch_bounds__(TPB) void bq_iter_post_kernel(BQ q) {
     __shared__ double red[32];
     __shared__ double lds[LDS_DOUBLES];
@@ -934,7 +972,7 @@ __global__ __launch_bounds__(TPB) void bq_iter_post_kernel(BQ q) {
     if (status == ST_ACTIVE) {
         wg::rhs_kernel(s, 0, 0.0, nullptr);  // set_predictive_rhs! :294
         WG_SYNC();
-        if (!wg_solve_system<!GONDZIO>(q, s, pb, lds, red)) status = ST_STEP_ERROR;
+        if (!wg_solve_system<!GONDZIO, REFINE>(q, s, pb, lds, red)) status = ST_STEP_ERROR;
     }
     if (status == ST_ACTIVE) {
         double a_aff_p, a_aff_d;
@@ -951,10 +989,10 @@ __global__ __launch_bounds__(TPB) void bq_iter_post_kernel(BQ q) {
         mu = fmax(q.opt.mu_min, sigma * mu_curr);
         wg::rhs_kernel(s, 1, mu, nullptr);  // set_correction_rhs! :307
         WG_SYNC();
-        if (!wg_solve_system<!GONDZIO>(q, s, pb, lds, red, /*keep=*/!GONDZIO)) status = ST_STEP_ERROR;
+        if (!wg_solve_system<!GONDZIO, REFINE>(q, s, pb, lds, red, /*keep=*/!GONDZIO)) status = ST_STEP_ERROR;
         // gondzio_correction_direction! (src/solver.jl:200-251)
         if constexpr (GONDZIO) {
-            if (status == ST_ACTIVE && q.opt.max_ncorr > 0 && !wg_gondzio(q, b, s, pb, mu_curr, lds, red))
+            if (status == ST_ACTIVE && q.opt.max_ncorr > 0 && !wg_gondzio<REFINE>(q, b, s, pb, mu_curr, lds, red))
                 status = ST_STEP_ERROR;
         }
     }

@@ -79,7 +79,7 @@ def native_options(opt) -> CMpcOptions:
     rule, reg = opt.step_rule, opt.regularization
     c = CMpcOptions(tol=opt.tol, max_iter=opt.max_iter, max_ncorr=opt.max_ncorr, mu_min=opt.mu_min,
                     check_residual=int(bool(opt.check_residual)), tol_linear_solve=opt.tol_linear_solve,
-                    refine_steps=int(opt.refine_steps or 0))  # (None: AUTO, resolved by MPCSolver; the batched engine does not refine)
+                    refine_steps=int(opt.refine_steps or 0))  # (None: AUTO, resolved by MPCSolver; 0 for the batched engine)
     if isinstance(rule, ConservativeStep):
         c.step_rule, c.step_param = 0, rule.tau
     elif isinstance(rule, AdaptiveStep):

@@ -2,6 +2,7 @@
 """Batch of independent QPs (BASELINE configs[3]: 1024 x (n=512, m=256)) on one GPU / one rank.
 
     python tools/bench_batch.py [--batch 128] [--nx 512] [--m 256] [--streams 16] [--mixed-patterns [SEED]]
+                                [--refine-steps N] [--trace]
 
 Under torch.distributed.run each rank takes problems rank, rank+N, ... (no communication) and rank 0
 reports the aggregate.  Prints one JSON line: QPs/s and IPM iterations/s.
@@ -10,6 +11,9 @@ reports the aggregate.  Prints one JSON line: QPs/s and IPM iterations/s.
 lower-only or upper-only; some rows equalities or one-sided), through the engine's per-problem patterns -- timed in
 the same call, alternately with the problems under their one shared pattern; the line then holds both and the ratio
 of problem-iterations per second (the sum of per-problem iterations over wall time).
+
+--refine-steps N / --trace: passed through to BatchedMPCSolver (N steps of iterative refinement in every solve; the
+per-iteration trace, recorded on the device and read back inside the timed region); the line names both.
 """
 import argparse
 import json
@@ -102,6 +106,9 @@ def main():
     p.add_argument("--mixed-patterns", type=int, nargs="?", const=1, default=None, metavar="SEED",
                    help="also solve the problems with a pattern of their own each (per_problem_patterns=True), "
                         "alternately with the shared pattern; reports both (batched engine only)")
+    p.add_argument("--refine-steps", type=int, default=None, metavar="N",
+                   help="refine_steps of the batched engine (default: the solver's own default, 0)")
+    p.add_argument("--trace", action="store_true", help="record the per-iteration trace (batched engine)")
     a = p.parse_args()
     import torch
 
@@ -115,6 +122,8 @@ def main():
     mixed = None
     if a.mixed_patterns is not None and (a.engine != "batched" or world > 1):
         p.error("--mixed-patterns: the batched engine on one rank")
+    if (a.refine_steps is not None or a.trace) and a.engine != "batched":
+        p.error("--refine-steps / --trace: the batched engine")
     if a.engine == "streams":
         M.solve_batch(make, mine[: min(len(mine), a.streams)], local_rank, a.streams, **opts)  # warm-up
         bench.dist_barrier(world)
@@ -125,6 +134,10 @@ def main():
         lockstep = None
     else:
         opts.pop("driver")
+        if a.refine_steps is not None:
+            opts["refine_steps"] = a.refine_steps
+        if a.trace:
+            opts["trace"] = True
         be = M.HipBackend(local_rank)
         qps = [make(be, i) for i in mine]  # data generation is not part of the timed solve
         # warm-up with the full batch (a first solver of a given size pays one-time costs -- kernel load, graph
@@ -183,7 +196,9 @@ def main():
                           "roofline": batch_roofline(a.nx, a.m, iters, dt),
                           "solved": ok, "config": {"workload": f"{a.batch} x synthetic dense QP nx={a.nx} m={a.m}",
                                                    "engine": a.engine, "streams_per_gpu": a.streams if a.engine == "streams" else None,
-                                                   "lock_step_iterations": lockstep}, "seconds": dt,
+                                                   "lock_step_iterations": lockstep,
+                                                   "refine_steps": a.refine_steps or 0, "trace": bool(a.trace)},
+                          "seconds": dt,
                           "all_seconds": times if a.engine == "batched" else [dt]}), flush=True)
 
 
