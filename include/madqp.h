@@ -62,6 +62,49 @@ int32_t madqp_ctx_sync(madqp_ctx* ctx);
  * reported as the numerical failure MadNLP.SolveException stands for (src/linear_solver.jl:41-43).
  * madqp_debug_inject_fault sets the word (tests). */
 int32_t madqp_debug_inject_fault(madqp_ctx* ctx);
+/* Debug only (tests/test_gpu_gemm_paths.py): ONE call of the library's internal fp64 MFMA product
+ *     C[i + j*ldc] = alpha * sum_k X[i + k*ldx] Y[j + k*ldy] + beta * Cin[i + j*ldcin]  (+ dvec[j] where i + diag_off == j)
+ * with every argument of the internal dispatcher (csrc/common.h: GemmArgs, GemmBatch) in the caller's hands, and a report
+ * of the launch form the dispatcher chose.  Pointers are DEVICE pointers except the two *_host arrays.  Asynchronous on the
+ * context's stream.  Not part of the solver's interface: the fields follow the dispatcher and may change with it. */
+typedef struct madqp_debug_gemm {
+    const double* X;
+    int64_t ldx;
+    const double* Y;
+    int64_t ldy;
+    double* C;
+    int64_t ldc;
+    const double* Cin; /* optional (may alias C); when given, beta * Cin is computed as written, also for beta = 0 */
+    int64_t ldcin;
+    const double* dvec; /* optional */
+    double alpha, beta;
+    int64_t M, N, K;
+    int64_t Mread, Nread; /* rows of X / Y that may be read (0 = M, N) */
+    int64_t diag_off;
+    int64_t lower_only;            /* 1: only entries with i + diag_off >= j are written */
+    const int64_t* tile_row0_host; /* optional, ceil(N / 128) entries: first computed 128-row tile of each tile column */
+    const int64_t* cols_host;      /* optional, ncols ranges [cols[2r], cols[2r+1]) of computed columns */
+    int64_t ncols;
+    int64_t B; /* 0: a single product; >= 1: a batch of B problems (B slots with list / count) at the strides below */
+    int64_t sX, sY, sC, sCin, sD;
+    const int32_t* skip;  /* optional, B words: problems with a non-zero word are left untouched */
+    const int32_t* list;  /* optional compacted form: slot y works off problems list[y], list[y + B], .. < *count */
+    const int32_t* count;
+    int64_t cap_slots; /* > 0: workgroup slots to leave free during this call (the persistent launch of csrc/dist.hip) */
+} madqp_debug_gemm;
+typedef struct madqp_debug_gemm_info {
+    int64_t ntiles;     /* active 128 x 128 output tiles */
+    int64_t ksplit;     /* > 1: every tile of the launch is cut into that many chunks of K */
+    int64_t kchunk;     /* length of a chunk of K (of a tail tile's chunks when tail_tiles > 0; K when nothing is split) */
+    int64_t tail_tiles; /* > 0: that many tiles of the last round are cut in K, the others run whole */
+    int64_t tail_split; /* chunks of K of a tail tile */
+    int64_t segments;   /* launches of the plain kernel over whole tiles (or over all chunks of a split launch) */
+    int64_t persistent_workgroups; /* > 0: one persistent launch of that many workgroups instead */
+    int64_t fast_ok;    /* operands allow the 16-byte LDS-DMA loop */
+    int64_t batch_xcd;  /* batch dealt to the XCDs problem by problem */
+    int64_t gemm_slots; /* resident workgroups the rules are computed from */
+} madqp_debug_gemm_info;
+int32_t madqp_debug_gemm_tn(madqp_ctx* ctx, const madqp_debug_gemm* args, madqp_debug_gemm_info* info);
 /* device memory helpers for hosts without their own allocator (Julia glue, C++) */
 int32_t madqp_malloc(madqp_ctx* ctx, size_t bytes, void** out);
 int32_t madqp_free(madqp_ctx* ctx, void* ptr);

@@ -68,6 +68,23 @@ class CMpcInfo(C.Structure):
                                       "del_c", "alpha_p", "alpha_d", "residual_ratio")]
                 + [("n_factorizations", i64), ("factor_info", i32)])
 
+class CDebugGemm(C.Structure):
+    """``madqp_debug_gemm`` of include/madqp.h (test seam into the fp64 MFMA product)."""
+
+    _fields_ = [("X", vp), ("ldx", i64), ("Y", vp), ("ldy", i64), ("C", vp), ("ldc", i64), ("Cin", vp), ("ldcin", i64),
+                ("dvec", vp), ("alpha", f64), ("beta", f64), ("M", i64), ("N", i64), ("K", i64), ("Mread", i64),
+                ("Nread", i64), ("diag_off", i64), ("lower_only", i64), ("tile_row0_host", pi64), ("cols_host", pi64),
+                ("ncols", i64), ("B", i64), ("sX", i64), ("sY", i64), ("sC", i64), ("sCin", i64), ("sD", i64),
+                ("skip", vp), ("list", vp), ("count", vp), ("cap_slots", i64)]
+
+
+class CDebugGemmInfo(C.Structure):
+    """``madqp_debug_gemm_info`` of include/madqp.h."""
+
+    _fields_ = [(k, i64) for k in ("ntiles", "ksplit", "kchunk", "tail_tiles", "tail_split", "segments",
+                                   "persistent_workgroups", "fast_ok", "batch_xcd", "gemm_slots")]
+
+
 # name -> argtypes (every function returns int32 unless listed in _RESTYPE)
 _SIGNATURES = {
     "madqp_version": [],
@@ -76,6 +93,7 @@ _SIGNATURES = {
     "madqp_last_error": [vp],
     "madqp_ctx_sync": [vp],
     "madqp_debug_inject_fault": [vp],
+    "madqp_debug_gemm_tn": [vp, C.POINTER(CDebugGemm), C.POINTER(CDebugGemmInfo)],
     "madqp_malloc": [vp, C.c_size_t, C.POINTER(vp)],
     "madqp_free": [vp, vp],
     "madqp_memcpy_h2d": [vp, vp, vp, C.c_size_t],

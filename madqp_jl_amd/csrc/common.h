@@ -141,7 +141,9 @@ struct GemmArgs {
     int64_t ldy;
     double* C;        // out C[i + j*ldc]
     int64_t ldc;
-    const double* Cin;  // optional addend, same indexing with ldcin (may alias C)
+    const double* Cin;  // optional addend, same indexing with ldcin (may alias C).  When given, the kernel computes
+                        // alpha*acc + beta*Cin as written: beta = 0 does NOT ignore a NaN / Inf in Cin as BLAS would
+                        // (pass nullptr for "no addend")
     int64_t ldcin;
     const double* dvec;  // optional: added where (i + diag_off == j), indexed by j
     double alpha, beta;  // out = alpha*acc + beta*Cin (+ dvec)
@@ -169,8 +171,9 @@ struct GemmBatch {
     const int32_t* list = nullptr;
     const int32_t* count = nullptr;
 };
+// info: optional report of the launch form chosen (the test seam madqp_debug_gemm_tn; nullptr everywhere else)
 int32_t madqp_gemm_tn(madqp_ctx* ctx, const GemmArgs& a, int prof_cls, const int64_t* cols = nullptr,
-                      int64_t ncols = 0, const GemmBatch* batch = nullptr);
+                      int64_t ncols = 0, const GemmBatch* batch = nullptr, madqp_debug_gemm_info* info = nullptr);
 
 void madqp_gemm_release_tables(madqp_ctx* ctx);
 

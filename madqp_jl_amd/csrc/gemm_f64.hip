@@ -332,7 +332,11 @@ void madqp_gemm_release_tables(madqp_ctx* ctx) {
 }
 
 int32_t madqp_gemm_tn(madqp_ctx* ctx, const GemmArgs& a, int prof_cls, const int64_t* cols, int64_t ncols,
-                      const GemmBatch* batch) {
+                      const GemmBatch* batch, madqp_debug_gemm_info* info) {
+    if (info) {  // (test seam only, madqp_debug_gemm_tn: what this call launched)
+        *info = madqp_debug_gemm_info{};
+        info->gemm_slots = ctx ? ctx->gemm_slots : 0;
+    }
     ARG_TRY(ctx, a.M >= 0 && a.N >= 0 && a.K >= 0 && a.X && a.Y && a.C);
     if (a.M == 0 || a.N == 0) return MADQP_OK;
     const int64_t tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
@@ -469,6 +473,13 @@ int32_t madqp_gemm_tn(madqp_ctx* ctx, const GemmArgs& a, int prof_cls, const int
     }
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     ka.fast_ok = al16(a.X) && al16(a.Y) && (a.ldx % 2 == 0) && (a.ldy % 2 == 0);
+    if (info) {
+        info->ntiles = ka.ntiles;
+        info->ksplit = ka.ksplit;
+        info->kchunk = ka.kchunk;
+        info->fast_ok = ka.fast_ok;
+        info->batch_xcd = ka.batch_xcd;
+    }
 #ifdef MADQP_STAMPS
     extern unsigned long long* madqp_stamp_buffer;
     ka.stamps = madqp_stamp_buffer;
@@ -516,6 +527,7 @@ int32_t madqp_gemm_tn(madqp_ctx* ctx, const GemmArgs& a, int prof_cls, const int
         hipLaunchKernelGGL(gemm_tn_f64_persistent_kernel, dim3((unsigned)capped), dim3(NTHREADS), 0, ctx->stream, ka,
                            ctx->d_tickets);
         LAUNCH_CHECK(ctx);
+        if (info) info->persistent_workgroups = capped;
         return MADQP_OK;
     }
     for (int64_t off = 0; off < total; off += seg) {
@@ -525,6 +537,7 @@ int32_t madqp_gemm_tn(madqp_ctx* ctx, const GemmArgs& a, int prof_cls, const int
         ka.ntiles = (int32_t)cnt;
         hipLaunchKernelGGL(gemm_tn_f64_kernel, dim3(ka.ntiles, gy), dim3(NTHREADS), 0, ctx->stream, ka);
         LAUNCH_CHECK(ctx);
+        if (info) info->segments += 1;
         if (cnt == total - off) break;
     }
     if (tail_n) {  // the tiles of the last round, K-split
@@ -543,6 +556,11 @@ int32_t madqp_gemm_tn(madqp_ctx* ctx, const GemmArgs& a, int prof_cls, const int
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)tail_n), dim3(256), 0, ctx->stream, a, table0 + total,
                            (int32_t)tail_n, (int32_t)S, ka.work);
         LAUNCH_CHECK(ctx);
+        if (info) {
+            info->tail_tiles = tail_n;
+            info->tail_split = S;
+            info->kchunk = chunk;
+        }
         return MADQP_OK;
     }
     if (ka.ksplit > 1) {  // (a split launch is always a single segment: few tiles)
@@ -671,6 +689,40 @@ extern "C" int32_t madqp_syrk_assemble(madqp_ctx* ctx, int64_t n, int64_t kdim, 
                                        int64_t ldc) {
     ARG_TRY(ctx, ctx != nullptr);
     return syrk_assemble_impl(ctx, n, kdim, B, ldb, w, base, ldbase, dvec, C, ldc, 0, nullptr);
+}
+
+// Test seam: one call of madqp_gemm_tn with every argument in the caller's hands, and a report of the launch form the
+// dispatcher chose (tests/test_gpu_gemm_paths.py).  Not part of the solver's interface.
+extern "C" int32_t madqp_debug_gemm_tn(madqp_ctx* ctx, const madqp_debug_gemm* d, madqp_debug_gemm_info* info) {
+    if (!ctx) return MADQP_ERR_ARG;
+    ARG_TRY(ctx, d != nullptr && d->cap_slots >= 0 && d->ncols >= 0 && d->B >= 0);
+    GemmArgs g{};
+    g.X = d->X;
+    g.ldx = d->ldx;
+    g.Y = d->Y;
+    g.ldy = d->ldy;
+    g.C = d->C;
+    g.ldc = d->ldc;
+    g.Cin = d->Cin;
+    g.ldcin = d->ldcin;
+    g.dvec = d->dvec;
+    g.alpha = d->alpha;
+    g.beta = d->beta;
+    g.M = d->M;
+    g.N = d->N;
+    g.K = d->K;
+    g.Mread = d->Mread;
+    g.Nread = d->Nread;
+    g.diag_off = d->diag_off;
+    g.lower_only = d->lower_only ? 1 : 0;
+    g.tile_row0 = d->tile_row0_host;
+    const GemmBatch bt{d->B, d->sX, d->sY, d->sC, d->sCin, d->sD, d->skip, d->list, d->count};
+    const int64_t cap0 = ctx->gemm_cap_slots;
+    ctx->gemm_cap_slots = d->cap_slots;
+    const int32_t r = madqp_gemm_tn(ctx, g, MADQP_PROF_POTRF_GEMM, d->cols_host, d->cols_host ? d->ncols : 0,
+                                    d->B > 0 ? &bt : nullptr, info);
+    ctx->gemm_cap_slots = cap0;
+    return r;
 }
 
 // ------------------------------------------------------------------ hardware probe

@@ -39,6 +39,20 @@ def test_state_struct_layout_matches_header():
     assert ctypes.sizeof(CState) == 8 * len(names)
 
 
+def test_debug_gemm_struct_layouts_match_header():
+    """The test seam madqp_debug_gemm_tn: both structs hold 8-byte fields only, in the header's order."""
+    from madqp_jl_amd._lib import CDebugGemm, CDebugGemmInfo
+
+    hdr = open(os.path.join(ROOT, "include", "madqp.h")).read()
+    for name, cls in (("madqp_debug_gemm", CDebugGemm), ("madqp_debug_gemm_info", CDebugGemmInfo)):
+        body = hdr[hdr.index("typedef struct %s {" % name):hdr.index("} %s;" % name)]
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        names = re.findall(r"\*?\s*([A-Za-z_0-9]+)\s*[,;]", body.split("{", 1)[1])
+        assert [f[0] for f in cls._fields_] == names
+        assert ctypes.sizeof(cls) == 8 * len(names)
+        assert not re.search(r"\bint32_t\s+[a-z]|\bint\s+[a-z]", body.split("{", 1)[1])  # (no 4-byte scalar fields)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_no_cpu_fallback():
     with pytest.raises(M.MadQPError):
