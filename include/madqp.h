@@ -564,8 +564,8 @@ int32_t madqp_mpc_ahead_stats(const madqp_mpc* mpc, int64_t* queued, int64_t* us
                                   norm_b, norm_c, del_w, del_c, residual_ratio, reg state (2), number of factorisations */
 typedef struct madqp_batch madqp_batch;
 typedef struct madqp_batch_data { /* caller-owned device arrays, problem b at offset b * length; borrowed */
-    const double* H;   /* [B][nx][nx] symmetric, or NULL for LPs */
-    const double* A;   /* [B][m][nx], row k contiguous */
+    const double* H;   /* [B][nx][nx] symmetric, or NULL for LPs ([nx][nx] after madqp_batch_share_matrices(share_H)) */
+    const double* A;   /* [B][m][nx], row k contiguous ([m][nx] after madqp_batch_share_matrices(share_A)) */
     const double* q;   /* [B][nx] */
     const double* rhs; /* [B][m] */
     const double* c0;  /* [B] */
@@ -611,6 +611,14 @@ int32_t madqp_batch_results(madqp_batch* b, int32_t* status_host, int32_t* iters
 #define MADQP_BATCH_TRACE_LEN 10
 int32_t madqp_batch_set_trace(madqp_batch* b, int64_t capacity);
 int32_t madqp_batch_trace(madqp_batch* b, double* trace_host, int32_t* count_host);
+
+/* One H and / or one A for the whole batch (the parametric batch: one model, many right-hand sides).  Valid once, after
+ * either madqp_batch_create* and before madqp_batch_init (MADQP_ERR_STATE otherwise), like madqp_batch_set_trace.
+ * share_H / share_A != 0: data->H is ONE [nx][nx] matrix / data->A ONE [m][nx] matrix read by every problem.
+ * h_scale: device, [B], borrowed, or NULL (= 1): problem b uses fl(h_scale[b] * H[i][j]) wherever it reads H -- one IEEE
+ * product per entry, so the results are bitwise those of a batch that holds the B scaled copies.
+ * MADQP_ERR_ARG: share_H on a batch without H (LPs), or h_scale without share_H.  Without this call nothing changes. */
+int32_t madqp_batch_share_matrices(madqp_batch* b, int32_t share_H, int32_t share_A, const double* h_scale);
 
 #ifdef __cplusplus
 }

@@ -195,6 +195,7 @@ _SIGNATURES = {
     "madqp_batch_results": [vp, pi32, pi32, pf64],
     "madqp_batch_set_trace": [vp, i64],
     "madqp_batch_trace": [vp, pf64, pi32],
+    "madqp_batch_share_matrices": [vp, i32, i32, vp],
     "madqp_mpc_create": [vp, pstate, vp, vp, vp, vp, f64, f64, f64, C.POINTER(CMpcOptions), C.POINTER(vp)],
     "madqp_mpc_destroy": [vp],
     "madqp_mpc_set_scalars": [vp, f64, f64, f64, f64, i64],

@@ -51,9 +51,15 @@ class BatchedMPCSolver:
     ``trace``: ``True`` records every iteration of every problem on the device (``max_iter + 1`` records per problem), a
     positive ``int`` the first that many, ``False`` (default) none -- the library is then called exactly as without the
     keyword.  ``refine_steps`` (an :class:`IPMOptions` field): steps of iterative refinement in every solve, as in
-    :class:`MPCSolver`; ``None`` means 0 here (the AUTO rule is ``MPCSolver``'s)."""
+    :class:`MPCSolver`; ``None`` means 0 here (the AUTO rule is ``MPCSolver``'s).
 
-    def __init__(self, qps, backend, per_problem_patterns=False, trace=False, **opts):
+    ``shared_matrices=True``: the parametric batch -- one model, many right-hand sides.  Every problem's ``A`` (and ``H``,
+    unless all are LPs) must be the SAME tensor (equal ``data_ptr()``, shape and strides); ``q``, the bounds and the row
+    bounds are per problem.  Nothing of size ``B * nx * nx`` or ``B * m * nx`` is then made: ``A`` is scaled once, ``H`` stays
+    as the caller holds it and the library multiplies each entry by the problem's ``obj_scale`` as it reads it
+    (``madqp_batch_share_matrices``) -- the very product the stacked form stores, so the results are bitwise the same."""
+
+    def __init__(self, qps, backend, per_problem_patterns=False, trace=False, shared_matrices=False, **opts):
         if not qps:
             raise ValueError("empty batch")
         if trace is not True and trace is not False:
@@ -62,6 +68,7 @@ class BatchedMPCSolver:
         self._trace = trace if isinstance(trace, bool) else int(trace)
         self.be, self.qps = backend, list(qps)
         self.per_problem = bool(per_problem_patterns)
+        self.shared = bool(shared_matrices)
         if any((q.nvar, q.ncon) != (qps[0].nvar, qps[0].ncon) for q in self.qps):
             raise ValueError("all problems of a batch must have the same (nx, m)")
         self.opt = IPMOptions(**opts)
@@ -108,8 +115,19 @@ class BatchedMPCSolver:
         if not self.normal and has_eq and not (self._copt.regularization != 0 and reg.delta_d < 0.0):
             raise ValueError("the condensed KKT system needs dual regularization delta_d < 0 "
                              "when the problem has equality constraints")
-        self.H = None if q0.H is None else st("H")
-        self.A, self.q = st("A"), st("q")
+        if self.shared:
+            for name in ("A",) if q0.H is None else ("H", "A"):
+                t0 = getattr(q0, name)
+                for i, q in enumerate(self.qps):
+                    t = getattr(q, name)
+                    if (t.data_ptr(), t.shape, t.stride()) != (t0.data_ptr(), t0.shape, t0.stride()):
+                        raise ValueError(f"shared_matrices: problem {i} has a {name} of its own (every problem must hold "
+                                         f"the same tensor: equal data_ptr(), shape and strides)")
+            self.H = None if q0.H is None else q0.H.unsqueeze(0)  # [1, ...] views of the caller's tensors
+            self.A, self.q = q0.A.unsqueeze(0), st("q")
+        else:
+            self.H = None if q0.H is None else st("H")
+            self.A, self.q = st("A"), st("q")
         self.c0 = torch.as_tensor([q.c0 for q in self.qps], dtype=torch.float64, device=dev)
         self.x0, self.y0 = st("x0"), st("y0")
         self._h = None
@@ -142,14 +160,16 @@ class BatchedMPCSolver:
         H, A, q = self.H, self.A, self.q
         self.obj_scale = torch.ones(B, **f64)
         self.con_scale = torch.ones((B, m), **f64)
+        self.h_scale = None  # shared H: the per-problem factor the library applies as it reads H (None: 1)
         if opt.scaling and (m or nx):  # MadNLP.set_scaling!(..., 100)
-            if m and nx:
-                self.con_scale = torch.minimum(one, 100.0 / A.abs().amax(dim=2))
+            if m and nx:  # (shared A: one row of scales, the same for every problem)
+                self.con_scale = torch.minimum(one, 100.0 / A.abs().amax(dim=2)).expand(B, m).contiguous()
             g = q.clone()
             if H is not None and nx:
                 step = max(1, (1 << 27) // max(nx * nx, 1))  # bounded temporaries
+                Hb = H.expand(B, nx, nx)  # (shared H: a view -- the temporaries below have the stacked form's shape and layout)
                 for b0 in range(0, B, step):
-                    g[b0:b0 + step] += (H[b0:b0 + step] * x[b0:b0 + step, None, :nx]).sum(dim=2)
+                    g[b0:b0 + step] += (Hb[b0:b0 + step] * x[b0:b0 + step, None, :nx]).sum(dim=2)
             gmax = g.abs().amax(dim=1) if nx else torch.zeros(B, **f64)
             self.obj_scale = torch.where(gmax > 0, torch.minimum(one, 100.0 / gmax), one)
             cs = self.con_scale
@@ -159,10 +179,13 @@ class BatchedMPCSolver:
             x[:, nx:] *= cs_s
             xl[:, nx:] *= cs_s
             xu[:, nx:] *= cs_s
-            A = (cs[:, :, None] * A).contiguous()
-            H = None if H is None else (self.obj_scale[:, None, None] * H).contiguous()
+            A = (cs[:A.shape[0], :, None] * A).contiguous()  # (shared A: scaled once)
+            if self.shared and H is not None:
+                self.h_scale = self.obj_scale.contiguous()  # H itself stays unscaled: fl(obj_scale[b] * H[i][j]) on load
+            elif H is not None:
+                H = (self.obj_scale[:, None, None] * H).contiguous()
             q = self.obj_scale[:, None] * q
-        self._H, self._A, self._q = H, A.contiguous(), q.contiguous()
+        self._H, self._A, self._q = None if H is None else H.contiguous(), A.contiguous(), q.contiguous()
         self._rhs, self._c0 = rhs.contiguous(), (self.obj_scale * self.c0).contiguous()
         self.x, self.xl, self.xu, self.y = x.contiguous(), xl.contiguous(), xu.contiguous(), y.contiguous()
         self.zl, self.zu = torch.zeros((B, n), **f64), torch.zeros((B, n), **f64)
@@ -170,6 +193,7 @@ class BatchedMPCSolver:
         data = CBatchData(H=ptr(self._H), A=ptr(self._A), q=ptr(self._q), rhs=ptr(self._rhs), c0=ptr(self._c0),
                           x=ptr(self.x), xl=ptr(self.xl), xu=ptr(self.xu), zl=ptr(self.zl), zu=ptr(self.zu),
                           y=ptr(self.y))
+        self._data = data
         if self.pre_create_hook is not None:
             self.pre_create_hook(self)
         h = C.c_void_p()
@@ -186,6 +210,8 @@ class BatchedMPCSolver:
                                                       p64("ind_lb"), p64("ub_ptr"), p64("ind_ub"), C.byref(data),
                                                       C.byref(self._copt), C.byref(h)))
         self._h = h
+        if self.shared:
+            be._ck(be.lib.madqp_batch_share_matrices(h, int(self._H is not None), 1, ptr(self.h_scale)))
         self.trace_capacity = 0
         if self._trace is not False:
             cap = opt.max_iter + 1 if self._trace is True else self._trace

@@ -81,6 +81,11 @@ struct BQ {  // device view of the batch (by value in the kernel arguments); pro
     int64_t trace_cap;
     madqp_mpc_options opt;
     double mu_init, bound_fac;
+    // madqp_batch_share_matrices: doubles from problem b's H / A to problem b + 1's (0: ONE matrix read by every problem,
+    // else nx * nx / m * nx) and the per-problem factor of a shared H (nullptr: 1).  Read by the shared instantiations of the
+    // workgroup programs only (prob_of<true>); the others keep the natural strides as constants of their own.
+    int64_t sH, sA;
+    const double* h_scale;
 };
 
 // the pattern words are uniform across the workgroup: scalar loads, read once at the top of a program
@@ -123,9 +128,11 @@ struct Prob {
     double *theta, *t, *u, *K, *S, *winv, *tmp, *tn, *w1, *scal, *sym;
     double *hx, *raw_h, *raw_at, *at;
     double c0;
+    double hs;  // shared instantiations: problem b reads fl(hs * H[i][j]) wherever it reads H (batch_wg.inc: wg_hmul)
     int64_t ns, ntot;  // slacks of this problem; length of its [x | y | zl | zu] (the used part of d, p, w1, w2)
     const int64_t *ind_ineq, *slot;
 };
+template <bool SHARED>
 __device__ __forceinline__ Prob prob_of(const BQ& q, int64_t b) {
     const int64_t* pt = q.pat + b * PAT_LEN;
     Prob p;
@@ -133,8 +140,15 @@ __device__ __forceinline__ Prob prob_of(const BQ& q, int64_t b) {
     p.ntot = q.nx + p.ns + q.m + pt[P_NLB] + pt[P_NUB];
     p.ind_ineq = q.ind_ineq + pt[P_INEQ];
     p.slot = q.slot + pt[P_SLOT];
-    p.H = q.H ? q.H + b * q.nx * q.nx : nullptr;
-    p.A = q.A + b * q.m * q.nx;
+    if constexpr (SHARED) {
+        p.H = q.H ? q.H + b * q.sH : nullptr;
+        p.A = q.A + b * q.sA;
+        p.hs = q.h_scale ? q.h_scale[b] : 1.0;
+    } else {
+        p.H = q.H ? q.H + b * q.nx * q.nx : nullptr;
+        p.A = q.A + b * q.m * q.nx;
+        p.hs = 1.0;
+    }
     p.qv = q.q + b * q.nx;
     p.rhs = q.rhs + b * q.m;
     p.theta = q.theta + b * q.m;
@@ -159,6 +173,9 @@ __device__ __forceinline__ Prob prob_of(const BQ& q, int64_t b) {
 // The workgroup programs are compiled twice (batch_wg.inc): 256 threads per problem for large batches
 // (many problems per CU, HBM bound) and 512 threads per problem for small ones (1024 would spill), where the time of a
 // lock-step iteration is the serial time of ONE problem's vector work.
+// -- and each width once more for batches that share H / A (madqp_batch_share_matrices; WG_SHARED 1: strides and the factor
+// of H from BQ): the programs of a batch that shares nothing are compiled from the very text they always were.
+#define WG_SHARED 0
 #define TPB 256
 #define WGNS wg256
 #ifdef MADQP_BATCH_STAMPS
@@ -172,12 +189,49 @@ __device__ unsigned long long madqp_batch_stamps[32];  // [31] = last stamp; slo
 #include "batch_wg.inc"
 #undef TPB
 #undef WGNS
+#undef WG_SHARED
+#define WG_SHARED 1
+#define TPB 256
+#define WGNS wg256s
+#include "batch_wg.inc"
+#undef TPB
+#undef WGNS
+#define TPB 512
+#define WGNS wg512s
+#include "batch_wg.inc"
+#undef TPB
+#undef WGNS
+#undef WG_SHARED
 
 __global__ void bq_count_active_kernel(const int32_t* __restrict__ status, int64_t B, int32_t* out) {
     int cnt = 0;
     for (int64_t i = threadIdx.x; i < B; i += blockDim.x) cnt += (status[i] == ST_ACTIVE);
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
     if (threadIdx.x == 0) *out = cnt;
+}
+
+// Shared H: the addend of the assembly, fl(h_scale[b] * H), into the lower triangle of problem b's K (the entries the GEMM
+// reads where it writes: flat index i + j * nx of H for i >= j, as the stacked form's Cin), so that the assembly accumulates in
+// place.  Same masks as the GEMM launch behind it: skip[b] != 0 leaves problem b alone; list / count: slot blockIdx.y works
+// off list[y], list[y + slots], .. < *count.  grid.x: blocks of PW_COLS columns.
+constexpr int PW_COLS = 16;
+__global__ __launch_bounds__(256) void bq_prewrite_h_kernel(const double* __restrict__ H, const double* __restrict__ h_scale,
+                                                            int64_t nx, double* __restrict__ K, int64_t ldk, int64_t B,
+                                                            const int32_t* __restrict__ skip,
+                                                            const int32_t* __restrict__ list,
+                                                            const int32_t* __restrict__ count) {
+    const int64_t j0 = (int64_t)blockIdx.x * PW_COLS;
+    const int64_t j1 = (j0 + PW_COLS < nx) ? j0 + PW_COLS : nx;
+    const int64_t first = list ? (int64_t)blockIdx.y : 0, last = list ? (int64_t)*count : 1, step = list ? (int64_t)gridDim.y : 1;
+    for (int64_t pb = first; pb < last; pb += step) {
+        const int64_t b = list ? (int64_t)list[pb] : (int64_t)blockIdx.y;
+        if (b < 0 || b >= B) continue;
+        if (!list && skip && skip[b] != 0) continue;
+        const double hs = h_scale ? h_scale[b] : 1.0;
+        double* Kb = K + b * ldk * ldk;
+        for (int64_t j = j0; j < j1; ++j)
+            for (int64_t i = j + threadIdx.x; i < nx; i += 256) Kb[i + j * ldk] = hs * H[i + j * nx];
+    }
 }
 }  // namespace
 
@@ -194,6 +248,8 @@ struct madqp_batch {
     int graph_state = 0;  // 0 not tried, 1 ready, -1 unavailable
     bool wide;  // 512 threads per problem (small batches)
     bool started = false;  // madqp_batch_init has run: BQ has gone into kernels (and soon into the graph) by value
+    bool shared = false;    // madqp_batch_share_matrices has been called: the shared instantiations of the programs run
+    bool shared_H = false;  // ... with ONE H: factor_all writes fl(h_scale[b] * H) into K before every assembly
 };
 
 namespace {
@@ -235,6 +291,7 @@ int32_t factor_all(madqp_batch* b, const int32_t* skip, bool retry = false) {
     g.ldc = q.ldk;
     g.Cin = q.normal ? nullptr : q.H;
     g.ldcin = q.nx;
+    int64_t sCin = q.nx * q.nx;
     g.dvec = q.normal ? q.theta : q.pr_diag;  // normal equations: Sigma_s^-1 on the inequality rows
     g.alpha = 1.0;
     g.beta = 1.0;
@@ -248,7 +305,20 @@ int32_t factor_all(madqp_batch* b, const int32_t* skip, bool retry = false) {
     }
     static const bool compact = !(getenv("MADQP_BATCH_RETRY_COMPACT") && atoi(getenv("MADQP_BATCH_RETRY_COMPACT")) == 0);
     const bool lst = retry && compact;
-    GemmBatch bt{lst ? RETRY_SLOTS : q.B, q.kpad * q.npad, q.kpad * q.npad, q.ldk * q.ldk, q.nx * q.nx, q.normal ? q.m : q.nst,
+    if (b->shared_H && g.Cin) {
+        // ONE H for the batch: K_b <- fl(h_scale[b] * H) first (the double the stacked form keeps in memory), then the assembly
+        // adds to it in place as the updates of the factorisation do -- the GEMM, its sums and beta = 1 are the stacked form's.
+        // Before EVERY assembly: by the x100-retry rounds K holds what the failed factorisation left.
+        ProfScope ps(ctx, MADQP_PROF_SYRK);
+        hipLaunchKernelGGL(bq_prewrite_h_kernel, dim3((unsigned)((q.nx + PW_COLS - 1) / PW_COLS), (unsigned)(lst ? RETRY_SLOTS : q.B)),
+                           dim3(256), 0, ctx->stream, q.H, q.h_scale, q.nx, q.K, q.ldk, q.B, lst ? nullptr : skip,
+                           lst ? q.retry_list : nullptr, lst ? q.retry_count : nullptr);
+        LAUNCH_CHECK(ctx);
+        g.Cin = q.K;
+        g.ldcin = q.ldk;
+        sCin = q.ldk * q.ldk;
+    }
+    GemmBatch bt{lst ? RETRY_SLOTS : q.B, q.kpad * q.npad, q.kpad * q.npad, q.ldk * q.ldk, sCin, q.normal ? q.m : q.nst,
                  lst ? nullptr : skip, lst ? q.retry_list : nullptr, lst ? q.retry_count : nullptr};
     int32_t r = madqp_gemm_tn(ctx, g, MADQP_PROF_SYRK, nullptr, 0, &bt);
     if (r) return r;
@@ -341,6 +411,8 @@ int32_t create_batch(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, PatternHo
     q.zu = data->zu;
     q.y = data->y;
     q.opt = *opt;
+    q.sH = nx * nx;
+    q.sA = m * nx;
     const int64_t nst = q.nst, ntst = q.ntst, nlbt = ph.nlb_total, nubt = ph.nub_total;
     int32_t r = MADQP_OK;
     int64_t *d_pat = nullptr, *d_ineq = nullptr, *d_slot = nullptr;
@@ -538,6 +610,15 @@ extern "C" int32_t madqp_batch_create_patterns(madqp_ctx* ctx, int64_t B, int64_
     return create_batch(ctx, B, nx, m, ph, d_lists[0], d_lists[1], std::move(owned), data, opt, out);
 }
 
+// one workgroup program for the whole batch: 512 or 256 threads per problem, from namespace W / N
+#define WG_LAUNCH(b, W, N, ...)                                                                                   \
+    do {                                                                                                          \
+        if ((b)->wide)                                                                                            \
+            hipLaunchKernelGGL((W::__VA_ARGS__), dim3((unsigned)(b)->q.B), dim3(512), 0, (b)->ctx->stream, (b)->q); \
+        else                                                                                                      \
+            hipLaunchKernelGGL((N::__VA_ARGS__), dim3((unsigned)(b)->q.B), dim3(256), 0, (b)->ctx->stream, (b)->q); \
+    } while (0)
+
 // src/solver.jl:162-179 for every problem (the caller has done :127-159: bounds, interior push, scaling)
 extern "C" int32_t madqp_batch_init(madqp_batch* b, double mu_init, double bound_fac) {
     if (!b) return MADQP_ERR_ARG;
@@ -547,24 +628,24 @@ extern "C" int32_t madqp_batch_init(madqp_batch* b, double mu_init, double bound
     b->q.bound_fac = bound_fac;
     {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        if (b->wide)
-            hipLaunchKernelGGL(wg512::bq_init_pre_kernel, dim3((unsigned)b->q.B), dim3(512), 0, ctx->stream, b->q);
+        if (b->shared)
+            WG_LAUNCH(b, wg512s, wg256s, bq_init_pre_kernel);
         else
-            hipLaunchKernelGGL(wg256::bq_init_pre_kernel, dim3((unsigned)b->q.B), dim3(256), 0, ctx->stream, b->q);
+            WG_LAUNCH(b, wg512, wg256, bq_init_pre_kernel);
         LAUNCH_CHECK(ctx);
     }
     int32_t r = factor_all(b, b->q.status);
     if (r) return r;
     ProfScope ps(ctx, MADQP_PROF_VEC);
     const bool rf = b->q.opt.refine_steps > 0;  // refinement is a template parameter, like GONDZIO below
-    if (b->wide && rf)
-        hipLaunchKernelGGL(wg512::bq_init_post_kernel<true>, dim3((unsigned)b->q.B), dim3(512), 0, ctx->stream, b->q);
-    else if (b->wide)
-        hipLaunchKernelGGL(wg512::bq_init_post_kernel<false>, dim3((unsigned)b->q.B), dim3(512), 0, ctx->stream, b->q);
+    if (b->shared && rf)
+        WG_LAUNCH(b, wg512s, wg256s, bq_init_post_kernel<true>);
+    else if (b->shared)
+        WG_LAUNCH(b, wg512s, wg256s, bq_init_post_kernel<false>);
     else if (rf)
-        hipLaunchKernelGGL(wg256::bq_init_post_kernel<true>, dim3((unsigned)b->q.B), dim3(256), 0, ctx->stream, b->q);
+        WG_LAUNCH(b, wg512, wg256, bq_init_post_kernel<true>);
     else
-        hipLaunchKernelGGL(wg256::bq_init_post_kernel<false>, dim3((unsigned)b->q.B), dim3(256), 0, ctx->stream, b->q);
+        WG_LAUNCH(b, wg512, wg256, bq_init_post_kernel<false>);
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }
@@ -575,10 +656,10 @@ static int32_t launch_iteration(madqp_batch* b) {
     const BQ& q = b->q;
     {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        if (b->wide)
-            hipLaunchKernelGGL(wg512::bq_iter_pre_kernel, dim3((unsigned)q.B), dim3(512), 0, ctx->stream, q);
+        if (b->shared)
+            WG_LAUNCH(b, wg512s, wg256s, bq_iter_pre_kernel);
         else
-            hipLaunchKernelGGL(wg256::bq_iter_pre_kernel, dim3((unsigned)q.B), dim3(256), 0, ctx->stream, q);
+            WG_LAUNCH(b, wg512, wg256, bq_iter_pre_kernel);
         LAUNCH_CHECK(ctx);
     }
     int32_t r = factor_all(b, q.status);
@@ -587,29 +668,27 @@ static int32_t launch_iteration(madqp_batch* b) {
         HIP_TRY(ctx, hipMemsetAsync(q.retry_count, 0, sizeof(int32_t), ctx->stream));
         {
             ProfScope ps(ctx, MADQP_PROF_VEC);
-            if (b->wide)
-                hipLaunchKernelGGL(wg512::bq_retry_kernel, dim3((unsigned)q.B), dim3(512), 0, ctx->stream, q);
+            if (b->shared)
+                WG_LAUNCH(b, wg512s, wg256s, bq_retry_kernel);
             else
-                hipLaunchKernelGGL(wg256::bq_retry_kernel, dim3((unsigned)q.B), dim3(256), 0, ctx->stream, q);
+                WG_LAUNCH(b, wg512, wg256, bq_retry_kernel);
             LAUNCH_CHECK(ctx);
         }
         if ((r = factor_all(b, q.retry_skip, true))) return r;
     }
     ProfScope ps(ctx, MADQP_PROF_VEC);
     const bool gz = q.opt.max_ncorr > 0, rf = q.opt.refine_steps > 0;
-#define POST(NS, T, G, R) \
-    hipLaunchKernelGGL((NS::bq_iter_post_kernel<G, R>), dim3((unsigned)q.B), dim3(T), 0, ctx->stream, q)
-    if (b->wide) {
-        if (gz && rf) POST(wg512, 512, true, true);
-        else if (gz) POST(wg512, 512, true, false);
-        else if (rf) POST(wg512, 512, false, true);
-        else POST(wg512, 512, false, false);
-    } else {
-        if (gz && rf) POST(wg256, 256, true, true);
-        else if (gz) POST(wg256, 256, true, false);
-        else if (rf) POST(wg256, 256, false, true);
-        else POST(wg256, 256, false, false);
-    }
+#define POST(G, R)                                                      \
+    do {                                                                \
+        if (b->shared)                                                  \
+            WG_LAUNCH(b, wg512s, wg256s, bq_iter_post_kernel<G, R>);    \
+        else                                                            \
+            WG_LAUNCH(b, wg512, wg256, bq_iter_post_kernel<G, R>);      \
+    } while (0)
+    if (gz && rf) POST(true, true);
+    else if (gz) POST(true, false);
+    else if (rf) POST(false, true);
+    else POST(false, false);
 #undef POST
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
@@ -732,6 +811,24 @@ extern "C" int32_t madqp_batch_set_trace(madqp_batch* b, int64_t capacity) {
     q.trace = tr;
     q.trace_count = cnt;
     q.trace_cap = capacity;
+    return MADQP_OK;
+}
+
+// One H / one A for the whole batch (include/madqp.h).  Like the trace: strides and h_scale go into the kernels inside BQ, by
+// value, and into the captured graph -- once, and before madqp_batch_init.
+extern "C" int32_t madqp_batch_share_matrices(madqp_batch* b, int32_t share_H, int32_t share_A, const double* h_scale) {
+    if (!b) return MADQP_ERR_ARG;
+    madqp_ctx* ctx = b->ctx;
+    if (b->started || b->shared)
+        return madqp_fail(ctx, MADQP_ERR_STATE, "madqp_batch_share_matrices: once, and before madqp_batch_init");
+    BQ& q = b->q;
+    if (share_H && !q.H) return madqp_fail(ctx, MADQP_ERR_ARG, "madqp_batch_share_matrices: share_H on a batch without H");
+    if (h_scale && !share_H) return madqp_fail(ctx, MADQP_ERR_ARG, "madqp_batch_share_matrices: h_scale needs share_H");
+    b->shared = true;
+    b->shared_H = share_H != 0;
+    if (share_H) q.sH = 0;
+    if (share_A) q.sA = 0;
+    q.h_scale = h_scale;
     return MADQP_OK;
 }
 

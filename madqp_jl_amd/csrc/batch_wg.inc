@@ -1,4 +1,6 @@
-// Workgroup programs of batch.hip for TPB threads per problem (included once per TPB; needs TPB, WGNS).
+// Workgroup programs of batch.hip for TPB threads per problem (included once per TPB and WG_SHARED; needs TPB, WGNS, WG_SHARED).
+// WG_SHARED 1: the programs of a batch that shares H / A (madqp_batch_share_matrices) -- prob_of takes the strides from BQ,
+// and every entry of H is multiplied by the problem's factor as it is loaded (MS below).  WG_SHARED 0: none of that.
 namespace WGNS {
 namespace wg {
 #define MQ_KERNEL __device__ __forceinline__ void
@@ -129,9 +131,12 @@ __device__ __forceinline__ void wg_gemv_n_then_t(int64_t rows, int64_t cols, con
 // out(cols) = alpha * M' v + beta * out,  M row-major rows x cols: a thread per column; when the workgroup
 // is wider than the matrix, G thread groups split the rows and their partial sums meet in LDS (scr: TPB doubles)
 // raw (optional): the unscaled product M' v itself (what the incremental model evaluation keeps of the residual check)
+// MS: the matrix is ms * M, each entry rounded as it is loaded (a shared H under the problem's own scale)
+template <bool MS = false>
 __device__ __forceinline__ void wg_gemv_t(int64_t rows, int64_t cols, double alpha, const double* __restrict__ M,
                           const double* __restrict__ v, double beta, double* __restrict__ out, double* scr,
-                          double* __restrict__ raw = nullptr) {
+                          double* __restrict__ raw = nullptr, double ms = 1.0) {
+    auto ld = [&](int64_t idx) { return MS ? ms * M[idx] : M[idx]; };
     const int64_t cpad = (cols + 63) / 64 * 64;
     const int G = (cpad < TPB) ? (int)(TPB / cpad) : 1;
     if (G == 1) {
@@ -143,7 +148,7 @@ __device__ __forceinline__ void wg_gemv_t(int64_t rows, int64_t cols, double alp
             for (; k + 16 <= rows; k += 16) {  // 16 independent loads in flight per thread, 8 accumulation chains as before
                 double mv[16];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) mv[r] = M[(k + r) * cols + j];
+                for (int r = 0; r < 16; ++r) mv[r] = ld((k + r) * cols + j);
 #pragma unroll
                 for (int r = 0; r < 8; ++r) a[r] += mv[r] * v[k + r];
 #pragma unroll
@@ -151,9 +156,9 @@ __device__ __forceinline__ void wg_gemv_t(int64_t rows, int64_t cols, double alp
             }
             for (; k + 8 <= rows; k += 8) {
 #pragma unroll
-                for (int r = 0; r < 8; ++r) a[r] += M[(k + r) * cols + j] * v[k + r];
+                for (int r = 0; r < 8; ++r) a[r] += ld((k + r) * cols + j) * v[k + r];
             }
-            for (; k < rows; ++k) a[0] += M[k * cols + j] * v[k];
+            for (; k < rows; ++k) a[0] += ld(k * cols + j) * v[k];
             const double acc = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
             out[j] = (beta == 0.0) ? alpha * acc : alpha * acc + beta * out[j];
             if (raw) raw[j] = acc;
@@ -167,9 +172,9 @@ __device__ __forceinline__ void wg_gemv_t(int64_t rows, int64_t cols, double alp
         int64_t k = g;
         for (; k + 3 * G < rows; k += 4 * G) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) a[r] += M[(k + r * G) * cols + j] * v[k + r * G];
+            for (int r = 0; r < 4; ++r) a[r] += ld((k + r * G) * cols + j) * v[k + r * G];
         }
-        for (; k < rows; k += G) a[0] += M[k * cols + j] * v[k];
+        for (; k < rows; k += G) a[0] += ld(k * cols + j) * v[k];
     }
     WG_SYNC();
     if (g < G) scr[g * cpad + j] = (a[0] + a[1]) + (a[2] + a[3]);
@@ -192,9 +197,11 @@ constexpr int SYM_CH = 8, SYM_MAX = 64 * SYM_CH;
 constexpr int SYM_DOUBLES = (TPB / 64 + 1) * SYM_MAX;
 static_assert(SYM_MAX == 512 && SYM_DOUBLES <= (512 / 64 + 1) * 512, "batch.hip sizes the scratch for nx <= 512, 8 waves");
 
+// MS: the matrix is hs * H, each entry rounded as it is loaded
+template <bool MS = false>
 __device__ __forceinline__ void wg_symv_lower(int64_t n, double alpha, const double* __restrict__ H,
                                               const double* __restrict__ x, double beta, double* __restrict__ y,
-                                              double* __restrict__ sym, double* __restrict__ raw = nullptr) {
+                                              double* __restrict__ sym, double* __restrict__ raw = nullptr, double hs = 1.0) {
     constexpr int NW = TPB / 64, R = 4, UP = 2;  // R x UP loads in flight per lane (registers: the kernel keeps 4 waves per SIMD)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double col[SYM_CH];
@@ -227,6 +234,7 @@ __device__ __forceinline__ void wg_symv_lower(int64_t n, double alpha, const dou
                     for (int r = 0; r < R; ++r) {
                         const int kr = (int)((k0 + r < n) ? k0 + r : n - 1);
                         hv[uu][r] = Hr[r][(j < kr) ? j : kr];
+                        if constexpr (MS) hv[uu][r] *= hs;
                     }
                 }
 #pragma unroll
@@ -272,9 +280,9 @@ __device__ __forceinline__ void wg_symv_lower(int64_t n, double alpha, const dou
 __device__ __forceinline__ void wg_hmul(const BQ& q, const Prob& pb, double alpha, const double* x, double beta, double* y,
                                         double* scr, double* raw = nullptr) {
     if (pb.sym)
-        wg_symv_lower(q.nx, alpha, pb.H, x, beta, y, pb.sym, raw);
+        wg_symv_lower<WG_SHARED != 0>(q.nx, alpha, pb.H, x, beta, y, pb.sym, raw, pb.hs);
     else
-        wg_gemv_t(q.nx, q.nx, alpha, pb.H, x, beta, y, scr, raw);
+        wg_gemv_t<WG_SHARED != 0>(q.nx, q.nx, alpha, pb.H, x, beta, y, scr, raw, pb.hs);
 }
 // xs(128, LDS) = img * vs,  img: 128 x 128, fast index = output (the Wcm / Wrm images of chol.hip);
 // part: TPB doubles
@@ -712,7 +720,7 @@ __global__ __launch_bounds__(TPB) void bq_init_pre_kernel(BQ q) {
     __shared__ double lds[LDS_DOUBLES];
     const int64_t b = blockIdx.x;
     const madqp_state s = state_of(q, b);
-    const Prob pb = prob_of(q, b);
+    const Prob pb = prob_of<WG_SHARED != 0>(q, b);
     if (threadIdx.x == 0) {
         q.status[b] = ST_ACTIVE;
         q.iters[b] = 0;
@@ -767,7 +775,7 @@ __global__ __launch_bounds__(TPB) void bq_init_post_kernel(BQ q) {
     __shared__ double lds[LDS_DOUBLES];
     const int64_t b = blockIdx.x;
     const madqp_state s = state_of(q, b);
-    const Prob pb = prob_of(q, b);
+    const Prob pb = prob_of<WG_SHARED != 0>(q, b);
     int status = ST_ACTIVE;
     if (q.info[b] != 0) status = ST_INTERNAL;  // the start matrix (Sigma = 1) must be positive definite
     if (status == ST_ACTIVE) {
@@ -839,7 +847,7 @@ __global__ __launch_bounds__(TPB) void bq_iter_pre_kernel(BQ q) {
     const int64_t b = blockIdx.x;
     if (q.status[b] != ST_ACTIVE) return;
     const madqp_state s = state_of(q, b);
-    const Prob pb = prob_of(q, b);
+    const Prob pb = prob_of<WG_SHARED != 0>(q, b);
     double* sc = pb.scal;
     BSTAMP(12);  // since the end of the previous kernel of this problem: launch gap (post -> pre)
     if (q.incr_ok[b] & 1) {  // A' y of the new y = y + alpha_d dy from the product the last residual check formed
@@ -934,7 +942,7 @@ __global__ __launch_bounds__(TPB) void bq_retry_kernel(BQ q) {
     }
     if (!retry) return;
     const madqp_state s = state_of(q, b);
-    const Prob pb = prob_of(q, b);
+    const Prob pb = prob_of<WG_SHARED != 0>(q, b);
     double* sc = pb.scal;
     const double del_w = sc[S_DEL_W] * 100.0, del_c = sc[S_DEL_C] * 100.0;  // :14-15
     WG_SYNC();
@@ -963,7 +971,7 @@ __global__ __launch_bounds__(TPB) void bq_iter_post_kernel(BQ q) {
     const int64_t b = blockIdx.x;
     if (q.status[b] != ST_ACTIVE) return;
     const madqp_state s = state_of(q, b);
-    const Prob pb = prob_of(q, b);
+    const Prob pb = prob_of<WG_SHARED != 0>(q, b);
     double* sc = pb.scal;
     int status = ST_ACTIVE;
     if (q.info[b] != 0) status = ST_STEP_ERROR;  // still not factorized after the three trials of src/linear_solver.jl:7
