@@ -105,6 +105,71 @@ typedef struct madqp_debug_gemm_info {
     int64_t gemm_slots; /* resident workgroups the rules are computed from */
 } madqp_debug_gemm_info;
 int32_t madqp_debug_gemm_tn(madqp_ctx* ctx, const madqp_debug_gemm* args, madqp_debug_gemm_info* info);
+/* Debug only (tests/test_gpu_batched_ops.py): ONE dense helper of the batched engine's workgroup programs
+ * (csrc/batch_wg.inc) on caller-made operands, nprob workgroups of tpb threads, workgroup b on the slices at b * stride;
+ * nothing else is launched.  `shared` selects the instantiations of madqp_batch_share_matrices, where every entry of M is
+ * multiplied by ms as it is loaded (GEMV_T, SYMV_LOWER).  Matrices are row-major rows x cols as the engine holds H and A.
+ *   GEMV_N       y(rows) = alpha M x + beta y
+ *   GEMV_N_THEN_T y(rows) = M x, then at(cols) = M' dy with dy_i = theta_i (y_i - t_i); cols <= 512
+ *   GEMV_T       y(cols) = alpha M' x + beta y, x of length rows; raw (optional): M' x itself
+ *   SYMV_LOWER   y(rows) = alpha M x + beta y from the lower triangle of the symmetric rows x rows M, 1 <= rows <= 512;
+ *                sym: (tpb / 64 + 1) * 512 doubles of scratch per problem; raw (optional)
+ *   CHOL_SOLVE   y(rows) <- (L L')^-1 y, M = L (column-major, leading dimension ld >= rows), winv = the two 128 x 128 inverse
+ *                images per block (2 * 128 * 128 doubles each); the call allocates the solve's own work vector and waits
+ *   PREWRITE_H   bq_prewrite_h_kernel as the assembly launches it: lower triangle of y = K_b (ld x ld, stride ld * ld)
+ *                <- h_scale[b] * M (M = the ONE H, rows x rows); skip, or list / count with `slots` slots
+ * Every pointer is a DEVICE pointer.  Asynchronous on the context's stream (CHOL_SOLVE excepted).  Arguments that could
+ * make a helper read or write outside its operands are refused with MADQP_ERR_ARG before anything is launched.  Not
+ * part of the solver's interface: the fields follow the helpers and may change with them. */
+enum {
+    MADQP_DEBUG_OP_GEMV_N = 0,
+    MADQP_DEBUG_OP_GEMV_N_THEN_T,
+    MADQP_DEBUG_OP_GEMV_T,
+    MADQP_DEBUG_OP_SYMV_LOWER,
+    MADQP_DEBUG_OP_CHOL_SOLVE,
+    MADQP_DEBUG_OP_PREWRITE_H,
+    MADQP_DEBUG_OP_COUNT
+};
+typedef struct madqp_debug_batch_op_args {
+    int64_t op;     /* MADQP_DEBUG_OP_* */
+    int64_t tpb;    /* 256 | 512 threads per problem */
+    int64_t shared; /* 0 | 1 */
+    int64_t nprob;
+    int64_t rows, cols;
+    int64_t ld;
+    double alpha, beta, ms;
+    const double* M;
+    int64_t sM;
+    const double* x;
+    int64_t sx;
+    double* y;
+    int64_t sy;
+    double* raw;
+    int64_t sraw;
+    const double* theta;
+    const double* t;
+    int64_t st; /* stride of theta and t */
+    double* at;
+    int64_t sat;
+    const double* winv;
+    int64_t sW;
+    double* sym;
+    int64_t ssym;
+    const double* h_scale; /* optional, nprob factors (PREWRITE_H) */
+    const int32_t* skip;   /* optional (PREWRITE_H) */
+    const int32_t* list;   /* optional compacted form (PREWRITE_H): every entry in [0, nprob) */
+    const int32_t* count;
+    int64_t slots;
+} madqp_debug_batch_op_args;
+int32_t madqp_debug_batch_op(madqp_ctx* ctx, const madqp_debug_batch_op_args* args);
+/* Debug only: the engine's batched Cholesky (csrc/chol.hip: madqp_chol_factor_batched) with every argument in the caller's
+ * hands: B matrices of order n at A + b * sA (column-major, lda; the lower triangle is factored in place), the inverse
+ * images of their 128-column blocks at winv + b * sW (zero before the first call: only the lower parts are written), info[b] = 0
+ * or the 1-based first failing column.  skip[b] != 0 leaves problem b alone; list / count: `slots` slots work off the listed
+ * problems.  Asynchronous on the context's stream. */
+int32_t madqp_debug_chol_factor_batched(madqp_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t sA, double* winv,
+                                        int64_t sW, int32_t* info, int64_t B, const int32_t* skip, int64_t slots,
+                                        const int32_t* list, const int32_t* count);
 /* device memory helpers for hosts without their own allocator (Julia glue, C++) */
 int32_t madqp_malloc(madqp_ctx* ctx, size_t bytes, void** out);
 int32_t madqp_free(madqp_ctx* ctx, void* ptr);

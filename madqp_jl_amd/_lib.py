@@ -85,6 +85,19 @@ class CDebugGemmInfo(C.Structure):
                                    "persistent_workgroups", "fast_ok", "batch_xcd", "gemm_slots")]
 
 
+class CDebugBatchOp(C.Structure):
+    """``madqp_debug_batch_op_args`` of include/madqp.h (test seam into the workgroup helpers of the batched engine)."""
+
+    _fields_ = [("op", i64), ("tpb", i64), ("shared", i64), ("nprob", i64), ("rows", i64), ("cols", i64), ("ld", i64),
+                ("alpha", f64), ("beta", f64), ("ms", f64), ("M", vp), ("sM", i64), ("x", vp), ("sx", i64), ("y", vp),
+                ("sy", i64), ("raw", vp), ("sraw", i64), ("theta", vp), ("t", vp), ("st", i64), ("at", vp), ("sat", i64),
+                ("winv", vp), ("sW", i64), ("sym", vp), ("ssym", i64), ("h_scale", vp), ("skip", vp), ("list", vp),
+                ("count", vp), ("slots", i64)]
+
+
+DEBUG_OPS = ("gemv_n", "gemv_n_then_t", "gemv_t", "symv_lower", "chol_solve", "prewrite_h")  # MADQP_DEBUG_OP_*
+
+
 # name -> argtypes (every function returns int32 unless listed in _RESTYPE)
 _SIGNATURES = {
     "madqp_version": [],
@@ -94,6 +107,8 @@ _SIGNATURES = {
     "madqp_ctx_sync": [vp],
     "madqp_debug_inject_fault": [vp],
     "madqp_debug_gemm_tn": [vp, C.POINTER(CDebugGemm), C.POINTER(CDebugGemmInfo)],
+    "madqp_debug_batch_op": [vp, C.POINTER(CDebugBatchOp)],
+    "madqp_debug_chol_factor_batched": [vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp, vp],
     "madqp_malloc": [vp, C.c_size_t, C.POINTER(vp)],
     "madqp_free": [vp, vp],
     "madqp_memcpy_h2d": [vp, vp, vp, C.c_size_t],

@@ -846,6 +846,79 @@ extern "C" int32_t madqp_batch_trace(madqp_batch* b, double* trace_host, int32_t
     return MADQP_OK;
 }
 
+// Test seams (include/madqp.h; tests/test_gpu_batched_ops.py).  Not part of the solver's interface.
+// madqp_debug_batch_op: one dense helper of the workgroup programs, or the pre-write of a shared H exactly as factor_all
+// launches it.  Whatever could make a helper read or write outside its operands is refused before anything is launched.
+extern "C" int32_t madqp_debug_batch_op(madqp_ctx* ctx, const madqp_debug_batch_op_args* d) {
+    if (!ctx) return MADQP_ERR_ARG;
+    ARG_TRY(ctx, d != nullptr);
+    ARG_TRY(ctx, d->op >= 0 && d->op < MADQP_DEBUG_OP_COUNT && (d->tpb == 256 || d->tpb == 512) && (d->shared == 0 || d->shared == 1));
+    ARG_TRY(ctx, d->nprob >= 1 && d->nprob <= 65535 && d->rows >= 0 && d->cols >= 0);
+    ARG_TRY(ctx, d->M && d->y && d->sM >= 0 && d->sx >= 0 && d->sy >= 0 && d->sraw >= 0 && d->st >= 0 && d->sat >= 0 &&
+                     d->sW >= 0 && d->ssym >= 0);
+    if (d->op == MADQP_DEBUG_OP_PREWRITE_H) {
+        const bool lst = d->list != nullptr;
+        ARG_TRY(ctx, d->rows >= 1 && d->ld >= d->rows && (!lst || (d->count && d->slots >= 1 && d->slots <= 65535)));
+        ProfScope ps(ctx, MADQP_PROF_SYRK);
+        hipLaunchKernelGGL(bq_prewrite_h_kernel, dim3((unsigned)((d->rows + PW_COLS - 1) / PW_COLS), (unsigned)(lst ? d->slots : d->nprob)),
+                           dim3(256), 0, ctx->stream, d->M, d->h_scale, d->rows, d->y, d->ld, d->nprob, lst ? nullptr : d->skip,
+                           lst ? d->list : nullptr, lst ? d->count : nullptr);
+        LAUNCH_CHECK(ctx);
+        return MADQP_OK;
+    }
+    double* tmp = nullptr;
+    int64_t stmp = 0;
+    // an empty matrix is a case of the engine only as rows == 0 (wg_kkt_mul at m = 0); cols == 0 would divide by zero in wg_gemv_t
+    switch ((int)d->op) {
+        case MADQP_DEBUG_OP_GEMV_N:
+        case MADQP_DEBUG_OP_GEMV_T:
+            ARG_TRY(ctx, d->x && d->cols >= 1);
+            break;
+        case MADQP_DEBUG_OP_GEMV_N_THEN_T:  // a row of M in a wave's registers: 8 chunks of 64 columns; tot = cols <= LDS_DOUBLES
+            ARG_TRY(ctx, d->x && d->cols >= 1 && d->cols <= 512 && d->theta && d->t && d->at);
+            break;
+        case MADQP_DEBUG_OP_SYMV_LOWER:  // SYM_MAX; the loads are clamped to row / column n - 1
+            ARG_TRY(ctx, d->x && d->rows >= 1 && d->rows <= 512 && d->sym);
+            break;
+        case MADQP_DEBUG_OP_CHOL_SOLVE:
+            ARG_TRY(ctx, d->rows >= 1 && d->ld >= d->rows && d->winv);
+            stmp = (d->rows + NB - 1) / NB * NB;
+            HIP_TRY(ctx, hipMalloc(&tmp, (size_t)(d->nprob * stmp) * sizeof(double)));
+            break;
+        default:
+            break;
+    }
+    {
+        ProfScope ps(ctx, MADQP_PROF_VEC);
+        const dim3 grid((unsigned)d->nprob);
+        if (d->tpb == 512 && d->shared)
+            hipLaunchKernelGGL(wg512s::bq_debug_op_kernel, grid, dim3(512), 0, ctx->stream, *d, tmp, stmp);
+        else if (d->tpb == 512)
+            hipLaunchKernelGGL(wg512::bq_debug_op_kernel, grid, dim3(512), 0, ctx->stream, *d, tmp, stmp);
+        else if (d->shared)
+            hipLaunchKernelGGL(wg256s::bq_debug_op_kernel, grid, dim3(256), 0, ctx->stream, *d, tmp, stmp);
+        else
+            hipLaunchKernelGGL(wg256::bq_debug_op_kernel, grid, dim3(256), 0, ctx->stream, *d, tmp, stmp);
+    }
+    const hipError_t le = hipGetLastError();
+    hipError_t se = hipSuccess;
+    if (tmp) {  // the work vector is this call's own: wait, then give it back
+        se = hipStreamSynchronize(ctx->stream);
+        (void)hipFree(tmp);
+    }
+    if (le != hipSuccess) return madqp_fail(ctx, MADQP_ERR_HIP, "madqp_debug_batch_op: launch: %s", hipGetErrorString(le));
+    if (se != hipSuccess) return madqp_fail(ctx, MADQP_ERR_HIP, "madqp_debug_batch_op: %s", hipGetErrorString(se));
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_debug_chol_factor_batched(madqp_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t sA, double* winv,
+                                                   int64_t sW, int32_t* info, int64_t B, const int32_t* skip, int64_t slots,
+                                                   const int32_t* list, const int32_t* count) {
+    if (!ctx) return MADQP_ERR_ARG;
+    ARG_TRY(ctx, n >= 0 && sA >= 0 && sW >= 0 && B <= 65535 && slots <= 65535);
+    return madqp_chol_factor_batched(ctx, A, lda, n, sA, winv, sW, info, B, skip, slots, list, count);
+}
+
 #ifdef MADQP_BATCH_STAMPS
 extern "C" int32_t madqp_batch_read_stamps(unsigned long long* out32, int32_t reset) {
     if (hipMemcpyFromSymbol(out32, HIP_SYMBOL(madqp_batch_stamps), 32 * sizeof(unsigned long long)) != hipSuccess) return -1;

@@ -1044,4 +1044,35 @@ __global__ __launch_bounds__(TPB) void bq_iter_post_kernel(BQ q) {
     }
 }
 
+// ---- test seam (madqp_debug_batch_op, tests/test_gpu_batched_ops.py): ONE of the dense helpers above on caller-made
+// operands, workgroup b on the slices at b * stride, with the scratch areas the programs above hand them (tot = the whole
+// LDS area, scr = lds + 2 NB).  No program of the engine calls it.  tmp: the work vector of wg_chol_solve.
+__global__ __launch_bounds__(TPB) void bq_debug_op_kernel(madqp_debug_batch_op_args a, double* tmp, int64_t stmp) {
+    __shared__ double lds[LDS_DOUBLES];
+    const int64_t b = blockIdx.x;
+    const double* M = a.M + b * a.sM;
+    const double* x = a.x + b * a.sx;
+    double* y = a.y + b * a.sy;
+    double* raw = a.raw ? a.raw + b * a.sraw : nullptr;
+    switch ((int)a.op) {
+        case MADQP_DEBUG_OP_GEMV_N:
+            wg_gemv_n(a.rows, a.cols, a.alpha, M, x, a.beta, y);
+            break;
+        case MADQP_DEBUG_OP_GEMV_N_THEN_T:
+            wg_gemv_n_then_t<8>(a.rows, a.cols, M, x, a.theta + b * a.st, a.t + b * a.st, y, a.at + b * a.sat, lds);
+            break;
+        case MADQP_DEBUG_OP_GEMV_T:
+            wg_gemv_t<WG_SHARED != 0>(a.rows, a.cols, a.alpha, M, x, a.beta, y, lds + 2 * NB, raw, a.ms);
+            break;
+        case MADQP_DEBUG_OP_SYMV_LOWER:
+            wg_symv_lower<WG_SHARED != 0>(a.rows, a.alpha, M, x, a.beta, y, a.sym + b * a.ssym, raw, a.ms);
+            break;
+        case MADQP_DEBUG_OP_CHOL_SOLVE:
+            wg_chol_solve(M, a.ld, a.winv + b * a.sW, a.rows, y, tmp + b * stmp, lds);
+            break;
+        default:
+            break;
+    }
+}
+
 }  // namespace WGNS

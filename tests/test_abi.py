@@ -53,6 +53,22 @@ def test_debug_gemm_struct_layouts_match_header():
         assert not re.search(r"\bint32_t\s+[a-z]|\bint\s+[a-z]", body.split("{", 1)[1])  # (no 4-byte scalar fields)
 
 
+def test_debug_batch_op_struct_layout_matches_header():
+    """The test seam madqp_debug_batch_op: 8-byte fields only, in the header's order; the op names follow the enum."""
+    from madqp_jl_amd._lib import DEBUG_OPS, CDebugBatchOp
+
+    hdr = open(os.path.join(ROOT, "include", "madqp.h")).read()
+    name = "madqp_debug_batch_op_args"
+    body = hdr[hdr.index("typedef struct %s {" % name):hdr.index("} %s;" % name)]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).split("{", 1)[1]
+    names = re.findall(r"\*?\s*([A-Za-z_0-9]+)\s*[,;]", body)
+    assert [f[0] for f in CDebugBatchOp._fields_] == names
+    assert ctypes.sizeof(CDebugBatchOp) == 8 * len(names)
+    assert not re.search(r"\bint32_t\s+[a-z]|\bint\s+[a-z]", body)  # (no 4-byte scalar fields; int32_t* is a pointer)
+    enum = hdr[hdr.index("MADQP_DEBUG_OP_GEMV_N = 0"):hdr.index("MADQP_DEBUG_OP_COUNT")]
+    assert [e.lower() for e in re.findall(r"MADQP_DEBUG_OP_([A-Z_]+)", enum)] == list(DEBUG_OPS)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_no_cpu_fallback():
     with pytest.raises(M.MadQPError):
@@ -65,6 +81,8 @@ def test_usage_errors_are_return_codes_not_aborts():
     assert lib.madqp_ctx_destroy(None) == 0
     assert lib.madqp_gemv(None, 0, 1, 1, 1.0, None, 1, None, 0.0, None) == -1
     assert lib.madqp_chol_solve(None, None) == -1
+    assert lib.madqp_debug_batch_op(None, None) == -1
+    assert lib.madqp_debug_chol_factor_batched(None, None, 0, 0, 0, None, 0, None, 0, None, 0, None, None) == -1
     assert lib.madqp_last_error(None) == b"null context"
 
 
