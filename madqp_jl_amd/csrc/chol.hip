@@ -18,8 +18,11 @@
 // The inverse diagonal blocks W are kept (two images, 2 x n x 128 doubles) and turn the diagonal
 // solves of the two triangular sweeps into 128 x 128 mat-vecs; each sweep is ONE launch of
 // ticket-ordered workgroups handing the solved blocks on through a sentinel-tagged vector, HBM bound
-// (4 n^2 bytes); block rows longer than 64 tiles are streamed by several workgroups (SweepPlan).  Also here: the same factorisation for a batch of small matrices
-// (madqp_chol_factor_batched) and its pieces for the multi-GPU panel loop (madqp_chol_factor_panel, ...).
+// (4 n^2 bytes); block rows longer than 64 tiles are streamed by several workgroups (SweepPlan).
+// Host side: ONE left-looking driver (panel_update / factor_block / factor_range) on a CholTarget -- one matrix
+// (madqp_chol_factor), a batch of small matrices at fixed strides (madqp_chol_factor_batched) or a panel of the multi-GPU
+// loop (madqp_chol_factor_panel, ...); ONE panel solve of a 128-column block (madqp_chol_panel_solve), shared with the
+// mid-size schedule (factor_mid) and dist.hip; the A/B switches are read in one place (CholModes).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -1295,18 +1298,6 @@ __global__ __launch_bounds__(256) void panel_sub16_kernel(double* __restrict__ C
     }
     panel_sub16_body(C, ld, Lkk, ldl, Wcm, rows, rows_read);
 }
-// L[rows below, block] = C[..] L_kk^-T for the 128-column block whose factored diagonal block is Lkk (ldl) and whose inverse
-// image is Wcm; `rows_read`: rows of C that exist in memory (>= rows); B > 1: the same for B problems at fixed strides
-static int32_t panel_solve_sub16(madqp_ctx* ctx, double* C, int64_t ld, const double* Lkk, int64_t ldl, const double* Wcm,
-                                 int64_t rows, int64_t rows_read, int64_t B = 1, PanelBatch bt = PanelBatch{0, 0, 0, nullptr}) {
-    if (rows <= 0) return MADQP_OK;
-    ARG_TRY(ctx, B >= 1 && B <= 65535 && rows_read >= rows);
-    ProfScope ps(ctx, MADQP_PROF_POTRF_TRSM);
-    hipLaunchKernelGGL(panel_sub16_kernel, dim3((unsigned)((rows + 63) / 64), (unsigned)B), dim3(256), 0, ctx->stream, C, ld,
-                       Lkk, ldl, Wcm, rows, rows_read, bt);
-    LAUNCH_CHECK(ctx);
-    return MADQP_OK;
-}
 
 // ---- mid-size factorisation: right-looking, two launches per 128-column block ---------------------------------
 // Below n ~ 10 000 the left-looking schedule above is a chain of short dependent launches (per block: update with
@@ -1316,7 +1307,7 @@ static int32_t panel_solve_sub16(madqp_ctx* ctx, double* C, int64_t ld, const do
 //                         (K = 128 always, no split-K; a tile accumulates its updates in the order k = 0, 1, ..), and
 //                         the workgroup holding tile (k, k) goes on to factor and invert it without leaving the CU:
 //                         the updated tile passes from the accumulators to the LDS image of potf2_inv_body;
-//   panel times inverse   L_ik = C_ik W_k' (the GEMM kernel, as in factor_block).
+//   panel times inverse   L_ik = C_ik W_k' (the GEMM kernel, as in madqp_chol_panel_solve).
 // Workgroups have 512 threads and the diagonal kernel's LDS (one per CU).  That is schedule MODE 0 with two = 0, the
 // form of round 3 (still selectable); round 4 applies the SAME tile-panel products at other times: MODE 1 (default)
 // takes the units of a step from a plan (see "which trailing columns a block step visits" further down), MODE 0
@@ -1618,6 +1609,54 @@ __global__ __launch_bounds__(MID_THREADS) void chol_mid_step_kernel(MidArgs a) {
 
 }  // namespace
 
+// ---- the A/B switches of this file, read from the environment in ONE place ---------------
+struct CholModes {
+    bool panel_inv;    // MADQP_CHOL_PANEL=inv: panel solves multiply with the 128 x 128 inverse (rounds 1-3)
+    bool lite;         // MADQP_CHOL_LITE (1): factor-only diagonal kernels + one inversion launch per factorisation
+    bool pp;           // MADQP_CHOL_PP (1): panel times inverse by panel_inv_kernel; 0: the GEMM kernel
+    int sweep_diag;    // MADQP_SWEEP_DIAG: 1 (default), 2 = sub16, 0 = inv (see sweep_diag_mode)
+    bool sweep_upper;  // MADQP_SWEEP_UPPER (1): backward sweep of a mid-size factor on U = L'
+    int32_t sweep_chunk;      // MADQP_SWEEP_CHUNK (64): tiles of a block row per sweep job
+    int64_t mid_max;          // MADQP_CHOL_MID_MAX (13312): largest order of the mid-size schedule
+    bool mid_dsyrk, mid_two, mid_lazy;  // MADQP_CHOL_MID_DSYRK / _TWO / _LAZY (1): see factor_mid
+    int mid_cap;              // MADQP_CHOL_MID_CAP (0 = from the CU count; experiments)
+    int64_t wt_min, wt_max;   // MADQP_CHOL_WMIN / WMAX (6, 20): outer panel width in blocks
+};
+static CholModes chol_modes_from_env() {
+    auto is = [](const char* name, const char* v) { return getenv(name) && strcmp(getenv(name), v) == 0; };
+    auto num = [](const char* name, int64_t dflt) { return getenv(name) ? atoll(getenv(name)) : dflt; };
+    auto on = [&](const char* name) { return num(name, 1) != 0; };
+    CholModes m{};
+    m.panel_inv = is("MADQP_CHOL_PANEL", "inv");
+    m.lite = on("MADQP_CHOL_LITE");
+    m.pp = on("MADQP_CHOL_PP");
+    m.sweep_diag = is("MADQP_SWEEP_DIAG", "inv") ? 0 : is("MADQP_SWEEP_DIAG", "sub16") ? 2 : 1;
+    m.sweep_upper = on("MADQP_SWEEP_UPPER");
+    m.sweep_chunk = (int32_t)std::max<int64_t>(1, num("MADQP_SWEEP_CHUNK", 64));
+    m.mid_max = num("MADQP_CHOL_MID_MAX", 13312);
+    m.mid_dsyrk = on("MADQP_CHOL_MID_DSYRK");
+    // two panels per trailing pass (see the kernel): needs the diagonal workgroup's own SYRK
+    m.mid_two = m.mid_dsyrk && on("MADQP_CHOL_MID_TWO");
+    // planned visits (mid_plan_build) unless switched off; the two-panel schedule otherwise
+    m.mid_lazy = m.mid_dsyrk && on("MADQP_CHOL_MID_LAZY");
+    m.mid_cap = (int)num("MADQP_CHOL_MID_CAP", 0);
+    m.wt_min = num("MADQP_CHOL_WMIN", 6);
+    m.wt_max = num("MADQP_CHOL_WMAX", 20);
+    return m;
+}
+static const CholModes& chol_modes() {  // filled once, at the first use
+    static const CholModes m = chol_modes_from_env();
+    return m;
+}
+// factor-only diagonal kernels + one inversion launch per factorisation (round 4); MADQP_CHOL_LITE=0: factor and invert in
+// the diagonal kernel as before.  Needs the block-substitution panel solve (the product with the 128-inverse reads the image).
+static bool chol_lite() { return chol_modes().lite && !chol_modes().panel_inv; }
+// The diagonal step of the sweeps: 1 = unit block substitution with normalised images (default), 2 = plain block
+// substitution over the 16 x 16 sub-blocks (MADQP_SWEEP_DIAG=sub16), 0 = the product with the stored 128 x 128 inverse of
+// rounds 1-4 (MADQP_SWEEP_DIAG=inv; also whenever the diagonal kernels factor AND invert: MADQP_CHOL_LITE=0 /
+// MADQP_CHOL_PANEL=inv, whose images are full inverses).
+static int sweep_diag_mode() { return chol_lite() ? chol_modes().sweep_diag : 0; }
+
 extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out) {
     ARG_TRY(ctx, ctx && out && n >= 0);
     *out = nullptr;
@@ -1639,8 +1678,7 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
     // sweeps: block rows longer than `chunk` tiles are streamed by several workgroups (SweepPlan).  tmp holds the
     // intermediate vector (padded to whole blocks) followed by the partial-sum slots of both sweeps, so that one fill
     // per solve resets all of them.
-    s->sweep_chunk = 64;
-    if (const char* e_chunk = getenv("MADQP_SWEEP_CHUNK")) s->sweep_chunk = std::max(1, atoi(e_chunk));
+    s->sweep_chunk = chol_modes_from_env().sweep_chunk;  // (read per handle: the tests build job lists with several chunks)
     s->sweep_maxc = 0;
     s->sweep_njobs = 0;
     s->d_jobs = nullptr;
@@ -1710,9 +1748,7 @@ static int64_t outer_panel_width(int64_t rows, bool has_update, int64_t slots) {
     if (!has_update || mt <= 6) return NBO;
     int64_t best = NBO / NB;
     double best_eff = -1.0;
-    static const int64_t wt_max = getenv("MADQP_CHOL_WMAX") ? atoll(getenv("MADQP_CHOL_WMAX")) : 20;
-    static const int64_t wt_min = getenv("MADQP_CHOL_WMIN") ? atoll(getenv("MADQP_CHOL_WMIN")) : 6;
-    for (int64_t wt = wt_min; wt <= wt_max && wt <= mt; ++wt) {
+    for (int64_t wt = chol_modes().wt_min; wt <= chol_modes().wt_max && wt <= mt; ++wt) {
         const int64_t tiles = mt * wt - wt * (wt - 1) / 2;
         const int64_t rounds = (tiles + slots - 1) / slots;
         const double eff = (double)tiles / (double)(rounds * slots);
@@ -1724,58 +1760,61 @@ static int64_t outer_panel_width(int64_t rows, bool has_update, int64_t slots) {
     return best * NB;
 }
 
-static int32_t panel_update(madqp_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t row0,
-                            int64_t k0, int64_t width, int64_t kend = -1, double alpha = -1.0) {
+// What a factorisation works on: one matrix, or B equally sized ones at fixed strides (the batch part; every launch
+// then covers all problems, grid.y / grid.x = problem, and leaves those with skip[b] != 0 alone).
+struct CholTarget {
+    madqp_ctx* ctx;
+    double* A;
+    int64_t lda, n;
+    double* winv;   // n/128 blocks of WBLK doubles (per problem)
+    int32_t* info;  // one int (per problem)
+    bool lite;      // the diagonal kernel only factors (potf2_inv_kernel<1>); false: it factors and inverts (<0>)
+    bool batched = false;  // false: B = 1 and no batch part -- launches take no GemmBatch and the default Potf2Batch / PanelBatch
+    int64_t B = 1, sA = 0, sW = 0;  // problems (list: slots) and their strides in A and winv (doubles)
+    const int32_t* skip = nullptr;
+    const int32_t* list = nullptr;  // compacted form (GemmBatch::list)
+    const int32_t* count = nullptr;
+    int64_t npad() const { return (n + NB - 1) / NB * NB; }
+    // rows up to the padded order may be read when the leading dimension covers them (the KKT
+    // object allocates K that way): no partial tiles, stores stay masked
+    bool padded() const { return lda >= npad(); }
+};
+// a product of the factorisation on target t: operand Y and addend Cin of problem b at strides sY, sCin (X, C: t.sA)
+static int32_t target_gemm(const CholTarget& t, const GemmArgs& g, int cls, int64_t sY, int64_t sCin) {
+    if (!t.batched) return madqp_gemm_tn(t.ctx, g, cls);
+    const GemmBatch bt{t.B, t.sA, sY, t.sA, sCin, 0, t.skip, t.list, t.count};
+    return madqp_gemm_tn(t.ctx, g, cls, nullptr, 0, &bt);
+}
+
+static int32_t panel_update(const CholTarget& t, int64_t row0, int64_t k0, int64_t width, int64_t kend = -1,
+                            double alpha = -1.0) {
     // C[row0:n, row0:row0+width] += alpha L[row0:n, k0:kend] * L[row0:row0+width, k0:kend]'   (kend = row0
     // unless given: the distributed factorisation applies one received panel at a time; alpha = +1: the
     // columns of the positive block applied to the negative block of a quasi-definite matrix)
     if (kend < 0) kend = row0;
     GemmArgs g{};
-    g.X = A + row0 + k0 * lda;
-    g.ldx = lda;
+    g.X = t.A + row0 + k0 * t.lda;
+    g.ldx = t.lda;
     g.Y = g.X;
-    g.ldy = lda;
-    g.C = A + row0 + row0 * lda;
-    g.ldc = lda;
+    g.ldy = t.lda;
+    g.C = t.A + row0 + row0 * t.lda;
+    g.ldc = t.lda;
     g.Cin = g.C;
-    g.ldcin = lda;
+    g.ldcin = t.lda;
     g.alpha = alpha;
     g.beta = 1.0;
-    g.M = n - row0;
+    g.M = t.n - row0;
     g.N = width;
     g.K = kend - k0;
-    // rows up to the padded order may be read when the leading dimension covers them (the KKT
-    // object allocates K that way): no partial tiles, stores stay masked to M x N
-    const int64_t npad = (n + NB - 1) / NB * NB;
-    if (lda >= npad) {
-        g.Mread = npad - row0;
-        g.Nread = std::min<int64_t>(npad - row0, (width + NB - 1) / NB * NB);
+    if (t.padded()) {
+        g.Mread = t.npad() - row0;
+        g.Nread = std::min<int64_t>(t.npad() - row0, (width + NB - 1) / NB * NB);
     }
     g.diag_off = 0;
     g.lower_only = 1;
-    return madqp_gemm_tn(ctx, g, MADQP_PROF_POTRF_GEMM);
+    return target_gemm(t, g, MADQP_PROF_POTRF_GEMM, t.sA, t.sA);
 }
 
-// factor-only diagonal kernels + one inversion launch per factorisation (round 4); MADQP_CHOL_LITE=0: factor and invert in
-// the diagonal kernel as before.  Needs the block-substitution panel solve (the product with the 128-inverse reads the image).
-static bool panel_inv_mode();
-static bool chol_lite() {
-    static const bool on = !(getenv("MADQP_CHOL_LITE") && atoi(getenv("MADQP_CHOL_LITE")) == 0);
-    return on && !panel_inv_mode();
-}
-// The diagonal step of the sweeps: 1 = unit block substitution with normalised images (default), 2 = plain block
-// substitution over the 16 x 16 sub-blocks (MADQP_SWEEP_DIAG=sub16), 0 = the product with the stored 128 x 128 inverse of
-// rounds 1-4 (MADQP_SWEEP_DIAG=inv; also whenever the diagonal kernels factor AND invert: MADQP_CHOL_LITE=0 /
-// MADQP_CHOL_PANEL=inv, whose images are full inverses).
-static int sweep_diag_mode() {
-    static const int mode = [] {
-        const char* e = getenv("MADQP_SWEEP_DIAG");
-        if (e && strcmp(e, "inv") == 0) return 0;
-        if (e && strcmp(e, "sub16") == 0) return 2;
-        return 1;
-    }();
-    return chol_lite() ? mode : 0;
-}
 // what the factor-only diagonal kernels leave out of the serial spine, for all blocks j0/128 .. in ONE launch: the
 // off-diagonal parts of the sweep images
 static int32_t invert_blocks(madqp_chol* s, double* A, int64_t lda, int64_t j0, int64_t w) {
@@ -1808,79 +1847,90 @@ static void launch_sweep(bool bwd, unsigned grid, hipStream_t st, const double* 
         default: launch_sweep<1>(bwd, grid, st, L, ld, winv, in, out, n, ctl, fault, vec, plan); break;
     }
 }
-static bool panel_inv_mode() {
-    static const bool inv = getenv("MADQP_CHOL_PANEL") && strcmp(getenv("MADQP_CHOL_PANEL"), "inv") == 0;
-    return inv;
+
+// The panel solve of ONE block of w <= 128 columns: X (rows x w, leading dimension ldx; rows_read >= rows of them exist
+// in memory) <- X L^-T for the factored diagonal block L (ldl) whose inverse image is Wcm.  Three forms:
+//   block substitution with the 16 x 16 diagonal inverses (panel_sub16_kernel): the default, every whole block;
+//   MADQP_CHOL_PANEL=inv brings back the products with the 128 x 128 inverse of rounds 1-3 (for the A/B numbers in
+//   DESIGN.md) -- by panel_inv_kernel where the caller asks for it (inv = PANEL_INV_KERNEL: rows_read must be the rows
+//   up to the padded order) -- or by the GEMM kernel, which also serves a short last block.
+// batch: a batched target, for its batch part (the same solve for its B problems); nullptr: one matrix.
+int32_t madqp_chol_panel_solve(madqp_ctx* ctx, double* X, int64_t ldx, int64_t rows, int64_t rows_read, const double* L,
+                               int64_t ldl, const double* Wcm, int64_t w, PanelInvForm inv, const CholTarget* batch) {
+    if (rows <= 0) return MADQP_OK;
+    ARG_TRY(ctx, rows_read >= rows && (!batch || (batch->B >= 1 && batch->B <= 65535)));
+    if (w == NB && !chol_modes().panel_inv) {
+        ProfScope ps(ctx, MADQP_PROF_POTRF_TRSM);
+        const PanelBatch bt = batch ? PanelBatch{batch->sA, batch->sA, batch->sW, batch->skip, batch->list, batch->count}
+                                    : PanelBatch{0, 0, 0, nullptr};
+        hipLaunchKernelGGL(panel_sub16_kernel, dim3((unsigned)((rows + 63) / 64), (unsigned)(batch ? batch->B : 1)), dim3(256), 0,
+                           ctx->stream, X, ldx, L, ldl, Wcm, rows, rows_read, bt);
+        LAUNCH_CHECK(ctx);
+        return MADQP_OK;
+    }
+    // whole block and few rows below it (one register-heavy workgroup per CU: beyond ~24 000 rows -- 3 rounds -- the GEMM
+    // kernel's 128-row tiles, which read W once per 128 rows, are the faster form: n = 50 000 measured 1 316-1 319 against
+    // 1 311-1 315 ms per iteration with this kernel on every block)
+    if (w == NB && inv == PANEL_INV_KERNEL && !batch && rows_read % 32 == 0 && chol_modes().pp && rows <= 24576) {
+        ProfScope ps(ctx, MADQP_PROF_POTRF_TRSM);
+        hipLaunchKernelGGL(panel_inv_kernel, dim3((unsigned)(rows_read / 32)), dim3(256), 0, ctx->stream, X, ldx, Wcm, rows);
+        LAUNCH_CHECK(ctx);
+        return MADQP_OK;
+    }
+    // out[i,j] = sum_k C[i,k] W(j,k); in place: a single tile column, every workgroup reads
+    // exactly the rows it writes and finishes reading (K = w, all stages) before its stores.
+    GemmArgs g{};
+    g.X = X;
+    g.ldx = ldx;
+    g.Y = Wcm;  // Y[j + k*NB] = W(j,k)
+    g.ldy = NB;
+    g.C = X;
+    g.ldc = ldx;
+    g.alpha = 1.0;
+    g.beta = 0.0;
+    g.M = rows;
+    g.N = w;
+    g.K = w;
+    g.Mread = rows_read;  // (the GEMM kernel treats 0 and M alike)
+    g.Nread = NB;         // the inverse block image is always 128 x 128, zero padded
+    return batch ? target_gemm(*batch, g, MADQP_PROF_POTRF_TRSM, batch->sW, 0) : madqp_gemm_tn(ctx, g, MADQP_PROF_POTRF_TRSM);
 }
 
 // One 128-column block whose entries already carry every update from the columns to its left:
 // factor the diagonal block (and invert it), then L[below, jb] = C[below, jb] * W_jj'.
-static int32_t factor_block(madqp_chol* s, double* A, int64_t lda, int64_t jb, int64_t w) {
-    madqp_ctx* ctx = s->ctx;
-    const int64_t n = s->n;
-    double* Wcm = s->winv + (jb / NB) * WBLK;
-    double* Wrm = Wcm + NB * NB;
+static int32_t factor_block(const CholTarget& t, int64_t jb, int64_t w) {
+    madqp_ctx* ctx = t.ctx;
+    double* Ajj = t.A + jb + jb * t.lda;
+    double* Wcm = t.winv + (jb / NB) * WBLK;
     {
         ProfScope ps(ctx, MADQP_PROF_POTRF_DIAG);
-        if (chol_lite())
-            hipLaunchKernelGGL(potf2_inv_kernel<1>, dim3(1), dim3(P2_KTHREADS), 0, ctx->stream, A + jb + jb * lda, lda,
-                               (int)w, Wcm, Wrm, s->d_info, (int32_t)jb, Potf2Batch{0, 0, 0, nullptr});
-        else
-            hipLaunchKernelGGL(potf2_inv_kernel<0>, dim3(1), dim3(P2_KTHREADS), 0, ctx->stream, A + jb + jb * lda, lda,
-                               (int)w, Wcm, Wrm, s->d_info, (int32_t)jb, Potf2Batch{0, 0, 0, nullptr});
+        const Potf2Batch bt = t.batched ? Potf2Batch{t.sA, t.sW, 1, t.skip, t.list, t.count} : Potf2Batch{0, 0, 0, nullptr};
+        const auto diag_kernel = t.lite ? potf2_inv_kernel<1> : potf2_inv_kernel<0>;
+        hipLaunchKernelGGL(diag_kernel, dim3((unsigned)t.B), dim3(P2_KTHREADS), 0, ctx->stream, Ajj, t.lda, (int)w, Wcm,
+                           Wcm + NB * NB, t.info, (int32_t)jb, bt);
         LAUNCH_CHECK(ctx);
     }
-    static const bool pp_gemm = getenv("MADQP_CHOL_PP") && atoi(getenv("MADQP_CHOL_PP")) == 0;
-    const int64_t npad_b = (n + NB - 1) / NB * NB;
-    // the rows below the block: block substitution with the 16 x 16 diagonal inverses (panel_sub16_kernel); MADQP_CHOL_PANEL=inv
-    // brings back the products with the 128 x 128 inverse of rounds 1-3 (for the A/B numbers in DESIGN.md)
-    if (jb + w < n && w == NB && !panel_inv_mode())
-        return panel_solve_sub16(ctx, A + (jb + NB) + jb * lda, lda, A + jb + jb * lda, lda, Wcm, n - jb - NB,
-                                 lda >= npad_b ? npad_b - jb - NB : n - jb - NB);
-    // whole block and few rows below it (one register-heavy workgroup per CU: beyond ~24 000 rows -- 3 rounds -- the GEMM
-    // kernel's 128-row tiles, which read W once per 128 rows, are the faster form: n = 50 000 measured 1 316-1 319 against
-    // 1 311-1 315 ms per iteration with this kernel on every block)
-    if (jb + w < n && w == NB && lda >= npad_b && !pp_gemm && n - jb - NB <= 24576) {
-        ProfScope ps(ctx, MADQP_PROF_POTRF_TRSM);
-        hipLaunchKernelGGL(panel_inv_kernel, dim3((unsigned)((npad_b - jb - NB) / 32)), dim3(256), 0, ctx->stream,
-                           A + (jb + NB) + jb * lda, lda, Wcm, n - jb - NB);
-        LAUNCH_CHECK(ctx);
-        return MADQP_OK;
-    }
-    if (jb + w < n) {
-        // out[i,j] = sum_k C[i,k] W(j,k); in place: a single tile column, every workgroup reads
-        // exactly the rows it writes and finishes reading (K = w, all stages) before its stores.
-        GemmArgs g{};
-        g.X = A + (jb + w) + jb * lda;
-        g.ldx = lda;
-        g.Y = Wcm;  // Y[j + k*NB] = W(j,k)
-        g.ldy = NB;
-        g.C = A + (jb + w) + jb * lda;
-        g.ldc = lda;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.M = n - jb - w;
-        g.N = w;
-        g.K = w;
-        const int64_t npad = (n + NB - 1) / NB * NB;
-        if (lda >= npad) g.Mread = npad - jb - w;
-        g.Nread = NB;  // the inverse block image is always 128 x 128, zero padded
-        return madqp_gemm_tn(ctx, g, MADQP_PROF_POTRF_TRSM);
-    }
-    return MADQP_OK;
+    // the rows below the block; panel_inv_kernel serves one matrix with rows up to the padded order only
+    const int64_t rows = t.n - jb - w;
+    return madqp_chol_panel_solve(ctx, Ajj + w, t.lda, rows, t.padded() ? t.npad() - jb - w : rows, Ajj, t.lda, Wcm, w,
+                                  !t.batched && t.padded() ? PANEL_INV_KERNEL : PANEL_INV_GEMM, t.batched ? &t : nullptr);
 }
 
 // Recursive left-looking factorisation of the columns [j0, j0+w), which already carry the updates
 // of all columns < j0: factor the first half, apply it to the second half with ONE wide GEMM
 // (N = K = w/2), recurse.  Compared with a flat loop over 128-column blocks (N = 128, K up to
 // w - 128) this moves the in-panel flops into well-filled launches; only the leaves are narrow.
-static int32_t factor_range(madqp_chol* s, double* A, int64_t lda, int64_t j0, int64_t w) {
-    if (w <= NB) return factor_block(s, A, lda, j0, w);
+static int32_t factor_range(const CholTarget& t, int64_t j0, int64_t w) {
+    if (w <= NB) return factor_block(t, j0, w);
     const int64_t h = ((w + NB - 1) / NB + 1) / 2 * NB;  // first half, in whole blocks
-    int32_t r = factor_range(s, A, lda, j0, h);
+    int32_t r = factor_range(t, j0, h);
     if (r) return r;
-    if ((r = panel_update(s->ctx, A, lda, s->n, j0 + h, j0, w - h))) return r;
-    return factor_range(s, A, lda, j0 + h, w - h);
+    if ((r = panel_update(t, j0 + h, j0, w - h))) return r;
+    return factor_range(t, j0 + h, w - h);
+}
+// the one matrix of a handle as a target
+static CholTarget chol_target(madqp_chol* s, double* A, int64_t lda) {
+    return CholTarget{s->ctx, A, lda, s->n, s->winv, s->d_info, chol_lite()};
 }
 
 // ---- mid-size schedule: which trailing columns a block step visits (round 4) ---------------------------------------
@@ -1935,6 +1985,88 @@ static bool mid_plan_build(madqp_chol* s, int nblk, int cap) {
     return true;
 }
 
+// The mid-size schedule (chol_mid_step_kernel): right-looking, two launches per 128-column block, then the inverse images and
+// U = L'.  n > 128, s->npos == n, lda >= the padded order and even, A 16-byte aligned (chol_factor_enqueue checks).
+static int32_t factor_mid(madqp_chol* s, double* A, int64_t lda) {
+    madqp_ctx* ctx = s->ctx;
+    const int64_t n = s->n;
+    const CholModes& md = chol_modes();
+    const int64_t npad_m = (n + NB - 1) / NB * NB;
+    const int32_t nblk = (int32_t)(npad_m / NB);
+    // one timer scope for the whole factorisation (80 short launches: a scope each costs 0.7 ms per factorisation
+    // at n = 5 000); the scopes of the launches inside are switched off meanwhile
+    ProfScope ps_all(ctx, MADQP_PROF_POTRF_GEMM);
+    struct ProfMute {
+        madqp_ctx* c;
+        decltype(c->prof) saved;
+        explicit ProfMute(madqp_ctx* ctx_) : c(ctx_), saved(ctx_->prof) { c->prof = 0; }
+        ~ProfMute() { c->prof = saved; }
+    } mute(ctx);
+    const bool planned = md.mid_lazy && mid_plan_build(s, nblk, md.mid_cap > 0 ? md.mid_cap : ctx->gemm_slots / 2 - 1);
+    for (int32_t k = 0; k < nblk; ++k) {
+        if (planned) {
+            hipLaunchKernelGGL(chol_mid_step_kernel<1>, dim3((unsigned)(1 + s->mid_units[k])), dim3(MID_THREADS), 0,
+                               ctx->stream,
+                               MidArgs{A, lda, n, nblk, k, 1, 0, chol_lite() ? 1 : 0, 1, 0,
+                                       s->d_mid_plan + s->mid_units[nblk + k], s->winv, s->d_info});
+            LAUNCH_CHECK(ctx);
+        } else {
+            const int64_t rem = nblk - k;
+            int64_t nt, extra = 0;  // tiles shared out by pack/npair; workgroups before them besides the diagonal one
+            if (k == 0) {
+                nt = 0;
+            } else if (!md.mid_two) {
+                nt = rem * (rem + 1) / 2 - 1;
+            } else {
+                nt = rem - 1;  // column k below its diagonal tile, then columns k+2, k+4, ..
+                for (int64_t c = 1; 2 * c < rem; ++c) nt += rem - 2 * c;
+                extra = (k + 1 < nblk) ? 1 : 0;  // the next diagonal tile
+            }
+            // One workgroup per CU (LDS), one or two tiles each.  Up to a round of single tiles: singles; up to a round
+            // of pairs: pairs; beyond that -- two rounds -- as few pairs as two rounds of workgroups need, FIRST in the
+            // grid, singles behind them: a CU then works off three tiles (pair + single or three singles, 44 + 22 us)
+            // instead of four (two pairs, 88 us) whenever three per CU are enough (up to 765 tiles).
+            const int64_t cus = ctx->gemm_slots / 2 - 1 - extra;  // (the diagonal workgroup holds a CU)
+            int32_t pack = (nt > cus) ? 2 : 1, npair = 0;
+            unsigned grid = (unsigned)(1 + extra + (nt + pack - 1) / pack);
+            if (pack == 2) {
+                npair = (int32_t)((nt + 1) / 2);
+                if (nt > 2 * cus && nt - 2 * cus <= cus) {
+                    npair = (int32_t)(nt - 2 * cus);
+                    grid = (unsigned)(1 + extra + npair + (nt - 2 * (int64_t)npair));
+                }
+            }
+            hipLaunchKernelGGL(chol_mid_step_kernel<0>, dim3(grid), dim3(MID_THREADS), 0, ctx->stream,
+                               MidArgs{A, lda, n, nblk, k, pack, npair, chol_lite() ? 1 : 0, md.mid_dsyrk ? 1 : 0,
+                                       md.mid_two ? 1 : 0, nullptr, s->winv, s->d_info});
+            LAUNCH_CHECK(ctx);
+        }
+        // L[below, jb] = C[below, jb] L_kk^-T (the leading dimension is padded: panel_inv_kernel under MADQP_CHOL_PANEL=inv)
+        const int64_t jb = (int64_t)k * NB;
+        const int32_t r = madqp_chol_panel_solve(ctx, A + (jb + NB) + jb * lda, lda, n - jb - NB, npad_m - jb - NB,
+                                                 A + jb + jb * lda, lda, s->winv + (int64_t)k * WBLK, NB, PANEL_INV_KERNEL);
+        if (r) return r;
+    }
+    const int32_t ri = invert_blocks(s, A, lda, 0, n);  // the inverse images of all blocks, one launch (factor-only diagonal kernels)
+    if (ri) return ri;
+    // U = L' for the backward sweep (trsv_fwd_sweep_kernel<1, true>): one pass over the factor, 37 us at n = 5 000
+    if (md.sweep_upper && s->utmp && sweep_diag_mode() == 1) {
+        if (!s->upper) {
+            if (hipMalloc(&s->upper, (size_t)npad_m * npad_m * sizeof(double)) != hipSuccess) {
+                (void)hipGetLastError();
+                s->upper = nullptr;
+                return MADQP_OK;  // (no room for the copy: the backward sweep on L serves)
+            }
+            s->upper_ld = npad_m;
+        }
+        hipLaunchKernelGGL(lower_to_upper_kernel, dim3(2 * nblk, 2 * nblk), dim3(256), 0, ctx->stream, A, lda, n, s->upper,
+                           s->upper_ld);
+        LAUNCH_CHECK(ctx);
+        s->upper_ok = true;
+    }
+    return MADQP_OK;
+}
+
 // Everything of a factorisation except reading its info back: the launches are on the stream, info sits in s->d_info.
 static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
     madqp_ctx* ctx = s->ctx;
@@ -1947,118 +2079,14 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
     // the whole trailing matrix, which the left-looking schedule does not)
     // (round 5, with the backward sweep on U = L' behind this path -- ms per iteration, this path / left-looking: 19.1 / 21.0 at
     // n = 10 000, 23.7 / 25.4 at 11 000, 29.2 / 30.5 at 12 000, 35.5 / 36.4 at 13 000, 42.8 / 42.6 at 14 000, 60.8 / 58.1 at 16 000)
-    static const int64_t mid_max = getenv("MADQP_CHOL_MID_MAX") ? atoll(getenv("MADQP_CHOL_MID_MAX")) : 13312;
-    const int64_t npad_m = (n + NB - 1) / NB * NB;
-    if (n <= mid_max && n > NB && s->npos == n && lda >= npad_m && lda % 2 == 0 && (((uintptr_t)A) & 15) == 0) {
-        const int32_t nblk = (int32_t)(npad_m / NB);
-        // one timer scope for the whole factorisation (80 short launches: a scope each costs 0.7 ms per factorisation
-        // at n = 5 000); the scopes of the launches inside are switched off meanwhile
-        ProfScope ps_all(ctx, MADQP_PROF_POTRF_GEMM);
-        struct ProfMute {
-            madqp_ctx* c;
-            decltype(c->prof) saved;
-            explicit ProfMute(madqp_ctx* ctx_) : c(ctx_), saved(ctx_->prof) { c->prof = 0; }
-            ~ProfMute() { c->prof = saved; }
-        } mute(ctx);
-        static const bool mid_dsyrk = !(getenv("MADQP_CHOL_MID_DSYRK") && atoi(getenv("MADQP_CHOL_MID_DSYRK")) == 0);
-        // two panels per trailing pass (see the kernel): needs the diagonal workgroup's own SYRK
-        static const bool mid_two = mid_dsyrk && !(getenv("MADQP_CHOL_MID_TWO") && atoi(getenv("MADQP_CHOL_MID_TWO")) == 0);
-        // planned visits (mid_plan_build) unless switched off; the two-panel schedule otherwise
-        static const bool mid_lazy = mid_dsyrk && !(getenv("MADQP_CHOL_MID_LAZY") && atoi(getenv("MADQP_CHOL_MID_LAZY")) == 0);
-        static const int mid_cap = getenv("MADQP_CHOL_MID_CAP") ? atoi(getenv("MADQP_CHOL_MID_CAP")) : 0;  // (experiments)
-        const bool planned = mid_lazy && mid_plan_build(s, nblk, mid_cap > 0 ? mid_cap : ctx->gemm_slots / 2 - 1);
-        for (int32_t k = 0; k < nblk; ++k) {
-            if (planned) {
-                hipLaunchKernelGGL(chol_mid_step_kernel<1>, dim3((unsigned)(1 + s->mid_units[k])), dim3(MID_THREADS), 0,
-                                   ctx->stream,
-                                   MidArgs{A, lda, n, nblk, k, 1, 0, chol_lite() ? 1 : 0, 1, 0,
-                                           s->d_mid_plan + s->mid_units[nblk + k], s->winv, s->d_info});
-                LAUNCH_CHECK(ctx);
-            } else {
-                const int64_t rem = nblk - k;
-                int64_t nt, extra = 0;  // tiles shared out by pack/npair; workgroups before them besides the diagonal one
-                if (k == 0) {
-                    nt = 0;
-                } else if (!mid_two) {
-                    nt = rem * (rem + 1) / 2 - 1;
-                } else {
-                    nt = rem - 1;  // column k below its diagonal tile, then columns k+2, k+4, ..
-                    for (int64_t c = 1; 2 * c < rem; ++c) nt += rem - 2 * c;
-                    extra = (k + 1 < nblk) ? 1 : 0;  // the next diagonal tile
-                }
-                // One workgroup per CU (LDS), one or two tiles each.  Up to a round of single tiles: singles; up to a round
-                // of pairs: pairs; beyond that -- two rounds -- as few pairs as two rounds of workgroups need, FIRST in the
-                // grid, singles behind them: a CU then works off three tiles (pair + single or three singles, 44 + 22 us)
-                // instead of four (two pairs, 88 us) whenever three per CU are enough (up to 765 tiles).
-                const int64_t cus = ctx->gemm_slots / 2 - 1 - extra;  // (the diagonal workgroup holds a CU)
-                int32_t pack = (nt > cus) ? 2 : 1, npair = 0;
-                unsigned grid = (unsigned)(1 + extra + (nt + pack - 1) / pack);
-                if (pack == 2) {
-                    npair = (int32_t)((nt + 1) / 2);
-                    if (nt > 2 * cus && nt - 2 * cus <= cus) {
-                        npair = (int32_t)(nt - 2 * cus);
-                        grid = (unsigned)(1 + extra + npair + (nt - 2 * (int64_t)npair));
-                    }
-                }
-                hipLaunchKernelGGL(chol_mid_step_kernel<0>, dim3(grid), dim3(MID_THREADS), 0, ctx->stream,
-                                   MidArgs{A, lda, n, nblk, k, pack, npair, chol_lite() ? 1 : 0, mid_dsyrk ? 1 : 0,
-                                           mid_two ? 1 : 0, nullptr, s->winv, s->d_info});
-                LAUNCH_CHECK(ctx);
-            }
-            const int64_t jb = (int64_t)k * NB;
-            static const bool pp_gemm = getenv("MADQP_CHOL_PP") && atoi(getenv("MADQP_CHOL_PP")) == 0;
-            if (jb + NB < n && !panel_inv_mode()) {  // L[below, jb] = C[below, jb] L_kk^-T by block substitution
-                const int32_t r = panel_solve_sub16(ctx, A + (jb + NB) + jb * lda, lda, A + jb + jb * lda, lda,
-                                                    s->winv + (int64_t)k * WBLK, n - jb - NB, npad_m - jb - NB);
-                if (r) return r;
-            } else if (jb + NB < n && !pp_gemm) {  // L[below, jb] = C[below, jb] W_k'
-                const int64_t below = n - jb - NB;
-                hipLaunchKernelGGL(panel_inv_kernel, dim3((unsigned)((npad_m - jb - NB) / 32)), dim3(256), 0, ctx->stream,
-                                   A + (jb + NB) + jb * lda, lda, s->winv + (int64_t)k * WBLK, below);
-                LAUNCH_CHECK(ctx);
-            } else if (jb + NB < n) {  // the same product by the GEMM kernel (see factor_block)
-                GemmArgs g{};
-                g.X = A + (jb + NB) + jb * lda;
-                g.ldx = lda;
-                g.Y = s->winv + (int64_t)k * WBLK;
-                g.ldy = NB;
-                g.C = A + (jb + NB) + jb * lda;
-                g.ldc = lda;
-                g.alpha = 1.0;
-                g.beta = 0.0;
-                g.M = n - jb - NB;
-                g.N = NB;
-                g.K = NB;
-                g.Mread = npad_m - jb - NB;
-                g.Nread = NB;
-                const int32_t r = madqp_gemm_tn(ctx, g, MADQP_PROF_POTRF_TRSM);
-                if (r) return r;
-            }
-        }
-        const int32_t ri = invert_blocks(s, A, lda, 0, n);  // the inverse images of all blocks, one launch (factor-only diagonal kernels)
-        if (ri) return ri;
-        // U = L' for the backward sweep (trsv_fwd_sweep_kernel<1, true>): one pass over the factor, 37 us at n = 5 000
-        static const bool upper_on = !(getenv("MADQP_SWEEP_UPPER") && atoi(getenv("MADQP_SWEEP_UPPER")) == 0);
-        if (upper_on && s->utmp && sweep_diag_mode() == 1) {
-            if (!s->upper) {
-                if (hipMalloc(&s->upper, (size_t)npad_m * npad_m * sizeof(double)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    s->upper = nullptr;
-                    return MADQP_OK;  // (no room for the copy: the backward sweep on L serves)
-                }
-                s->upper_ld = npad_m;
-            }
-            hipLaunchKernelGGL(lower_to_upper_kernel, dim3(2 * nblk, 2 * nblk), dim3(256), 0, ctx->stream, A, lda, n, s->upper,
-                               s->upper_ld);
-            LAUNCH_CHECK(ctx);
-            s->upper_ok = true;
-        }
-        return MADQP_OK;
-    }
+    if (n <= chol_modes().mid_max && n > NB && s->npos == n && lda >= (n + NB - 1) / NB * NB && lda % 2 == 0 &&
+        (((uintptr_t)A) & 15) == 0)
+        return factor_mid(s, A, lda);
     // Quasi-definite mode (npos < n): A = [P, .; B, -Q] with P, Q positive definite and Q's block STORED AS +Q.
     // A = L diag(I, -I) L' with L = [L11, 0; W, L22], W = B L11^-T, L22 L22' = Q + W W': the same left-looking
     // sweep, except that an outer panel of the second block receives the columns of the first with a plus sign
     // (and never straddles the boundary).  No pivoting: stable for quasi-definite matrices.
+    const CholTarget t = chol_target(s, A, lda);
     const int64_t npos = s->npos;
     int64_t W = 0;
     for (int64_t J0 = 0; J0 < n; J0 += W) {
@@ -2066,13 +2094,13 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
         if (J0 < npos && J0 + W > npos) W = npos - J0;
         int32_t r = MADQP_OK;
         if (J0 > 0 && J0 < npos) {
-            r = panel_update(ctx, A, lda, n, J0, 0, W);
+            r = panel_update(t, J0, 0, W);
         } else if (J0 > 0) {
-            if (npos > 0) r = panel_update(ctx, A, lda, n, J0, 0, W, npos, 1.0);
-            if (!r && J0 > npos) r = panel_update(ctx, A, lda, n, J0, npos, W);
+            if (npos > 0) r = panel_update(t, J0, 0, W, npos, 1.0);
+            if (!r && J0 > npos) r = panel_update(t, J0, npos, W);
         }
         if (r) return r;
-        r = factor_range(s, A, lda, J0, W);
+        r = factor_range(t, J0, W);
         if (r) return r;
     }
     return invert_blocks(s, A, lda, 0, n);
@@ -2133,89 +2161,6 @@ void madqp_chol_factor_result(madqp_chol* s, int32_t info) {
 // The same recursive factorisation for a batch of B equally sized matrices at fixed strides (small
 // QPs, batch.hip): every launch covers all problems (grid.y / grid.x = problem), problems with
 // skip[b] != 0 are left alone.  winv: B x nblk x WBLK, info: B ints.
-namespace {
-struct CholBatch {
-    madqp_ctx* ctx;
-    double* A;
-    int64_t lda, n, sA;
-    double* winv;
-    int64_t sW;
-    int32_t* info;
-    int64_t B;
-    const int32_t* skip;
-    const int32_t* list;   // compacted form (GemmBatch::list): B = the number of slots
-    const int32_t* count;
-};
-int32_t bfactor_update(const CholBatch& c, int64_t row0, int64_t k0, int64_t width) {
-    GemmArgs g{};
-    g.X = c.A + row0 + k0 * c.lda;
-    g.ldx = c.lda;
-    g.Y = g.X;
-    g.ldy = c.lda;
-    g.C = c.A + row0 + row0 * c.lda;
-    g.ldc = c.lda;
-    g.Cin = g.C;
-    g.ldcin = c.lda;
-    g.alpha = -1.0;
-    g.beta = 1.0;
-    g.M = c.n - row0;
-    g.N = width;
-    g.K = row0 - k0;
-    const int64_t npad = (c.n + NB - 1) / NB * NB;
-    if (c.lda >= npad) {
-        g.Mread = npad - row0;
-        g.Nread = std::min<int64_t>(npad - row0, (width + NB - 1) / NB * NB);
-    }
-    g.lower_only = 1;
-    GemmBatch bt{c.B, c.sA, c.sA, c.sA, c.sA, 0, c.skip, c.list, c.count};
-    return madqp_gemm_tn(c.ctx, g, MADQP_PROF_POTRF_GEMM, nullptr, 0, &bt);
-}
-int32_t bfactor_block(const CholBatch& c, int64_t jb, int64_t w) {
-    madqp_ctx* ctx = c.ctx;
-    double* Wcm = c.winv + (jb / NB) * WBLK;
-    {
-        ProfScope ps(ctx, MADQP_PROF_POTRF_DIAG);
-        hipLaunchKernelGGL(potf2_inv_kernel<0>, dim3((unsigned)c.B), dim3(P2_KTHREADS), 0, ctx->stream,
-                           c.A + jb + jb * c.lda, c.lda, (int)w, Wcm, Wcm + NB * NB, c.info, (int32_t)jb,
-                           Potf2Batch{c.sA, c.sW, 1, c.skip, c.list, c.count});
-        LAUNCH_CHECK(ctx);
-    }
-    if (jb + w < c.n && w == NB && !panel_inv_mode()) {
-        const int64_t npad = (c.n + NB - 1) / NB * NB;
-        return panel_solve_sub16(ctx, c.A + (jb + NB) + jb * c.lda, c.lda, c.A + jb + jb * c.lda, c.lda, Wcm, c.n - jb - NB,
-                                 c.lda >= npad ? npad - jb - NB : c.n - jb - NB, c.B, PanelBatch{c.sA, c.sA, c.sW, c.skip, c.list, c.count});
-    }
-    if (jb + w < c.n) {
-        GemmArgs g{};
-        g.X = c.A + (jb + w) + jb * c.lda;
-        g.ldx = c.lda;
-        g.Y = Wcm;
-        g.ldy = NB;
-        g.C = c.A + (jb + w) + jb * c.lda;
-        g.ldc = c.lda;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.M = c.n - jb - w;
-        g.N = w;
-        g.K = w;
-        const int64_t npad = (c.n + NB - 1) / NB * NB;
-        if (c.lda >= npad) g.Mread = npad - jb - w;
-        g.Nread = NB;
-        GemmBatch bt{c.B, c.sA, c.sW, c.sA, 0, 0, c.skip, c.list, c.count};
-        return madqp_gemm_tn(ctx, g, MADQP_PROF_POTRF_TRSM, nullptr, 0, &bt);
-    }
-    return MADQP_OK;
-}
-int32_t bfactor_range(const CholBatch& c, int64_t j0, int64_t w) {
-    if (w <= NB) return bfactor_block(c, j0, w);
-    const int64_t h = ((w + NB - 1) / NB + 1) / 2 * NB;
-    int32_t r = bfactor_range(c, j0, h);
-    if (r) return r;
-    if ((r = bfactor_update(c, j0 + h, j0, w - h))) return r;
-    return bfactor_range(c, j0 + h, w - h);
-}
-}  // namespace
-
 // internal (batch.hip): asynchronous; info[b] = 0 or the first failing column of problem b (1-based)
 int32_t madqp_chol_factor_batched(madqp_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t sA, double* winv,
                                   int64_t sW, int32_t* info, int64_t B, const int32_t* skip, int64_t slots,
@@ -2223,8 +2168,9 @@ int32_t madqp_chol_factor_batched(madqp_ctx* ctx, double* A, int64_t lda, int64_
     ARG_TRY(ctx, A && winv && info && lda >= n && B >= 1 && (!list || (count && slots >= 1)));
     if (n == 0) return MADQP_OK;
     HIP_TRY(ctx, hipMemsetAsync(info, 0, (size_t)B * sizeof(int32_t), ctx->stream));
-    CholBatch c{ctx, A, lda, n, sA, winv, sW, info, list ? slots : B, list ? nullptr : skip, list, count};
-    return bfactor_range(c, 0, n);
+    // (the diagonal kernel factors and inverts: the images are what the batched sweeps multiply with)
+    const CholTarget t{ctx, A, lda, n, winv, info, false, true, list ? slots : B, sA, sW, list ? nullptr : skip, list, count};
+    return factor_range(t, 0, n);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2259,7 +2205,7 @@ extern "C" int32_t madqp_chol_factor_begin(madqp_chol* s, double* A, int64_t lda
 extern "C" int32_t madqp_chol_factor_panel(madqp_chol* s, int64_t j0, int64_t w) {
     if (!s) return MADQP_ERR_ARG;
     ARG_TRY(s->ctx, panel_ok(s, j0, w));
-    const int32_t r = factor_range(s, s->A, s->lda, j0, w);
+    const int32_t r = factor_range(chol_target(s, s->A, s->lda), j0, w);
     return r ? r : invert_blocks(s, s->A, s->lda, j0, w);  // (the caller packs / reads the images of this panel next)
 }
 
@@ -2278,15 +2224,6 @@ extern "C" int32_t madqp_chol_panel_pack(madqp_chol* s, int64_t j0, int64_t w, d
                                   s->A + j0 + j0 * s->lda, s->lda * sizeof(double), rows * sizeof(double),
                                   (size_t)w, hipMemcpyDeviceToDevice, ctx->stream));
     return MADQP_OK;
-}
-
-// X (rows x 128, leading dimension ldx) <- X L^-T for ONE factored 128 x 128 block L (ldl) with the inverse image W of its
-// 16 x 16 diagonal sub-blocks (dist.hip: the leaves of a tile's panel solve); false: this build multiplies with the
-// 128 x 128 inverse instead (MADQP_CHOL_PANEL=inv) and the caller takes its GEMM form
-bool madqp_chol_panel_sub16_on() { return !panel_inv_mode(); }
-int32_t madqp_chol_panel_solve128(madqp_ctx* ctx, double* X, int64_t ldx, int64_t rows, int64_t rows_read, const double* L,
-                                  int64_t ldl, const double* Wcm) {
-    return panel_solve_sub16(ctx, X, ldx, L, ldl, Wcm, rows, rows_read);
 }
 
 // One sweep over a single order-w tile (multi-GPU solves, dist.hip): the same kernels as madqp_chol_solve.

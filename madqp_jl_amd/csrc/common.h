@@ -204,11 +204,15 @@ int32_t madqp_sparse_gram(madqp_ctx* ctx, int64_t n, const int64_t* rowptr, cons
                           const int64_t* t_ptr, const int64_t* t_col, const double* t_val, const double* w,
                           const double* base, int64_t ldbase, const double* dvec, double* C, int64_t ldc);
 
+// chol.hip: the panel solve of one block of w <= 128 columns, X (rows x w) <- X L^-T (see there).  inv: how the products
+// with the 128 x 128 inverse (MADQP_CHOL_PANEL=inv) are formed -- the GEMM kernel, or panel_inv_kernel where it can serve.
+enum PanelInvForm { PANEL_INV_GEMM, PANEL_INV_KERNEL };
+struct CholTarget;
+int32_t madqp_chol_panel_solve(madqp_ctx* ctx, double* X, int64_t ldx, int64_t rows, int64_t rows_read, const double* L,
+                               int64_t ldl, const double* Wcm, int64_t w, PanelInvForm inv,
+                               const CholTarget* batch = nullptr);
 // chol.hip: one triangular sweep over an order-w tile whose factor and inverse diagonal blocks are given (dist.hip):
 // trans = 0: v <- L^-1 v, trans = 1: v <- L^-T v.  tmp: w doubles, ctl: 4 ints of device scratch.
-bool madqp_chol_panel_sub16_on();
-int32_t madqp_chol_panel_solve128(madqp_ctx* ctx, double* X, int64_t ldx, int64_t rows, int64_t rows_read, const double* L,
-                                  int64_t ldl, const double* Wcm);
 int32_t madqp_trsv_tile(madqp_ctx* ctx, int32_t trans, const double* L, int64_t ld, const double* winv, double* v,
                         int64_t w, double* tmp, int32_t* ctl);
 

@@ -258,26 +258,9 @@ int32_t dop_panel_local(Dev* dev, double* K, int64_t ld, int64_t lc, int64_t k, 
 // X (rows x w, leading dimension ldx) <- X L^-T with the inverse 128-blocks W of L's diagonal (recursive, MFMA)
 int32_t trsm_range(Dev* dev, double* X, int64_t ldx, int64_t rows, int64_t rread, const double* L, int64_t ldl,
                    const double* W, int64_t j0, int64_t wd) {
-    if (wd == 128 && madqp_chol_panel_sub16_on())  // block substitution inside the 128-block (chol.hip: panel_sub16_kernel)
-        return madqp_chol_panel_solve128(dev->ctx, X + j0 * ldx, ldx, rows, rread, L + j0 + j0 * ldl, ldl,
-                                         W + (j0 / 128) * (2 * 128 * 128));
-    if (wd <= 128) {  // (a short last block of a tile: the product with its inverse image, zero padded to 128 x 128)
-        GemmArgs g{};
-        g.X = X + j0 * ldx;
-        g.ldx = ldx;
-        g.Y = W + (j0 / 128) * (2 * 128 * 128);  // column-major image: Y[j + k*128] = W(j, k)
-        g.ldy = 128;
-        g.C = X + j0 * ldx;
-        g.ldc = ldx;
-        g.alpha = 1.0;
-        g.beta = 0.0;
-        g.M = rows;
-        g.N = wd;
-        g.K = wd;
-        g.Mread = rread;
-        g.Nread = 128;
-        return madqp_gemm_tn(dev->ctx, g, MADQP_PROF_POTRF_TRSM);
-    }
+    if (wd <= 128)  // one block: block substitution (chol.hip); a short last block of a tile: the product with its inverse image
+        return madqp_chol_panel_solve(dev->ctx, X + j0 * ldx, ldx, rows, rread, L + j0 + j0 * ldl, ldl,
+                                      W + (j0 / 128) * (2 * 128 * 128), wd, PANEL_INV_GEMM);
     const int64_t h = ((wd + 127) / 128 + 1) / 2 * 128;
     int32_t r = trsm_range(dev, X, ldx, rows, rread, L, ldl, W, j0, h);
     if (r) return r;

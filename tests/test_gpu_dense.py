@@ -437,3 +437,58 @@ def test_mid_size_schedules_factor_the_same_matrix():
         first = first or res
         if name != "gemm_diagonal":  # (the GEMM path sums the diagonal tile's products in its own order)
             assert {n: v[2] for n, v in res.items()} == {n: v[2] for n, v in first.items()}, name
+
+
+def test_left_looking_panel_forms_factor_the_same_matrix():
+    """The left-looking driver (chol.hip: factor_range / factor_block, here forced at small orders with
+    MADQP_CHOL_MID_MAX=0) solves the panel of a 128-column block in one of three forms: block substitution (default),
+    panel_inv_kernel (MADQP_CHOL_PANEL=inv, padded leading dimension) and the GEMM with the inverse image
+    (MADQP_CHOL_PANEL=inv with an unpadded leading dimension or MADQP_CHOL_PP=0).  Orders with a single trailing block,
+    one recursion level, a ragged last block and more than one outer panel, at ld = ceil(n/128) 128 and -- 257 and
+    1000 -- at ld = n: every form must give LAPACK's factor and solution up to rounding.  (No bit equality between the
+    forms: the inverse products round differently.)"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import textwrap
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = textwrap.dedent('''
+        import json, sys
+        import numpy as np, torch
+        sys.path.insert(0, %r)
+        import madqp_jl_amd as M
+        be = M.HipBackend(0)
+        out = {}
+        for n, padded in ((129, 1), (257, 1), (1000, 1), (2500, 1), (257, 0), (1000, 0)):
+            rng = np.random.default_rng(n)
+            G = torch.as_tensor(rng.standard_normal((n, n + 8)), device=be.device)
+            K = G @ G.T + n * torch.eye(n, dtype=torch.float64, device=be.device)
+            ld = (n + 127) // 128 * 128 if padded else n
+            Kd = torch.zeros((ld, ld), dtype=torch.float64, device=be.device)
+            Kd[:n, :n] = K
+            h = be.chol_create(n)
+            info = be.chol_factor(h, Kd, ld)
+            Lc = torch.tril(Kd.T[:n, :n])                     # the library's layout is column-major: read it transposed
+            ref = torch.linalg.cholesky(K)
+            err = float((Lc - ref).abs().max() / ref.abs().max())
+            x = torch.as_tensor(rng.standard_normal(n), device=be.device)
+            b = K @ x
+            be.chol_solve(h, b)
+            out["%%d/%%d" %% (n, ld)] = [err, float((b - x).abs().max()), int(info)]
+            be.chol_destroy(h)
+        be.close()
+        print(json.dumps(out))
+    ''') % root
+    variants = (("default", {}), ("inv", {"MADQP_CHOL_PANEL": "inv"}),
+                ("inv_gemm", {"MADQP_CHOL_PANEL": "inv", "MADQP_CHOL_PP": "0"}))
+    for name, env in variants:
+        p = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, MADQP_CHOL_MID_MAX="0", **env),
+                           capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, (name, p.stderr[-2000:])
+        res = json.loads(p.stdout.strip().splitlines()[-1])
+        print(name, res)
+        assert len(res) == 6, (name, res)
+        for key, (err, dx, info) in res.items():
+            assert info == 0 and err < 1e-12 and dx < 1e-9, (name, key, err, dx, info)
