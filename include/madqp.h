@@ -170,6 +170,39 @@ int32_t madqp_debug_batch_op(madqp_ctx* ctx, const madqp_debug_batch_op_args* ar
 int32_t madqp_debug_chol_factor_batched(madqp_ctx* ctx, double* A, int64_t lda, int64_t n, int64_t sA, double* winv,
                                         int64_t sW, int32_t* info, int64_t B, const int32_t* skip, int64_t slots,
                                         const int32_t* list, const int32_t* count);
+/* Debug only (tests/test_gemv_form.py, tests/test_gpu_matvec.py): what madqp_gemv would launch for these arguments -- the
+ * dispatcher's own choice (csrc/gemv.hip: gemv_plan, the one function madqp_gemv launches from), not a restatement of it.
+ * Host only, no context, no device: A and x are inspected as ADDRESSES (16-byte alignment) and never dereferenced, so any
+ * made-up address serves.  MADQP_ERR_ARG where madqp_gemv refuses (negative extents, trans not 0 / 1, lda < cols, a null
+ * A or x of a product that would read them) or out_host is null.  Not part of the solver's interface: the fields follow
+ * the dispatcher and may change with it. */
+enum {
+    MADQP_GEMV_FORM_NONE = 0,  /* nothing to write (the output has length 0): no launch */
+    MADQP_GEMV_FORM_SCALE,     /* inner length 0: y = beta y */
+    MADQP_GEMV_FORM_N_WAVE,    /* trans = 0, one wave per row */
+    MADQP_GEMV_FORM_N_BLOCK,   /* trans = 0, one workgroup per row */
+    MADQP_GEMV_FORM_T_SINGLE,  /* trans = 1, 128-column tiles, one chunk of rows writes y */
+    MADQP_GEMV_FORM_T_CHUNKED, /* trans = 1, 128-column tiles x row chunks, partials, then the reduce kernel */
+    MADQP_GEMV_FORM_T_STRIP,   /* trans = 1, 16-column strips over all rows */
+    MADQP_GEMV_FORM_COUNT
+};
+typedef struct madqp_debug_gemv_form_info {
+    int64_t form;           /* MADQP_GEMV_FORM_* */
+    int64_t vec;            /* 1: the instantiation with 16-byte loads (the strip kernel has no other) */
+    int64_t chunks;         /* trans = 1: chunks of rows (1: no partials, no reduce); 0 otherwise */
+    int64_t rows_per_chunk; /* trans = 1: rows of a chunk (the last one may be shorter); 0 otherwise */
+    int64_t workgroups;     /* of the product kernel (the reduce kernel of T_CHUNKED not counted) */
+} madqp_debug_gemv_form_info;
+int32_t madqp_debug_gemv_form(int32_t trans, int64_t rows, int64_t cols, const double* A, int64_t lda, const double* x,
+                              madqp_debug_gemv_form_info* out_host);
+/* Debug only (tests/test_gpu_matvec.py): y(n) = alpha H x + beta y for a symmetric H (row r at H + r*ldh) from ONE side of
+ * its diagonal through the triangular kernels of csrc/gemv.hip at ANY order n >= 1 -- the solver reaches them from
+ * n >= 12288 (upper = 0, the entries c <= r of row r are read) or 2048 (upper = 1, the entries c >= r) only.  Asynchronous
+ * on the context's stream; uses the context's workspace like madqp_gemv.  MADQP_ERR_ARG before any launch: a null
+ * pointer, ldh < n, ldh odd, H not 16-byte aligned, upper not 0 / 1.  n == 0: nothing is done.  Not part of the solver's
+ * interface. */
+int32_t madqp_debug_symv(madqp_ctx* ctx, int32_t upper, int64_t n, double alpha, const double* H, int64_t ldh,
+                         const double* x, double beta, double* y);
 /* device memory helpers for hosts without their own allocator (Julia glue, C++) */
 int32_t madqp_malloc(madqp_ctx* ctx, size_t bytes, void** out);
 int32_t madqp_free(madqp_ctx* ctx, void* ptr);

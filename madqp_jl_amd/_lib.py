@@ -95,6 +95,14 @@ class CDebugBatchOp(C.Structure):
                 ("count", vp), ("slots", i64)]
 
 
+class CDebugGemvForm(C.Structure):
+    """``madqp_debug_gemv_form_info`` of include/madqp.h (what the dense mat-vec dispatcher would launch)."""
+
+    _fields_ = [(k, i64) for k in ("form", "vec", "chunks", "rows_per_chunk", "workgroups")]
+
+
+GEMV_FORMS = ("none", "scale", "n_wave", "n_block", "t_single", "t_chunked", "t_strip")  # MADQP_GEMV_FORM_*
+
 DEBUG_OPS = ("gemv_n", "gemv_n_then_t", "gemv_t", "symv_lower", "chol_solve", "prewrite_h")  # MADQP_DEBUG_OP_*
 
 
@@ -109,6 +117,8 @@ _SIGNATURES = {
     "madqp_debug_gemm_tn": [vp, C.POINTER(CDebugGemm), C.POINTER(CDebugGemmInfo)],
     "madqp_debug_batch_op": [vp, C.POINTER(CDebugBatchOp)],
     "madqp_debug_chol_factor_batched": [vp, vp, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp, vp],
+    "madqp_debug_gemv_form": [i32, i64, i64, vp, i64, vp, C.POINTER(CDebugGemvForm)],
+    "madqp_debug_symv": [vp, i32, i64, f64, vp, i64, vp, f64, vp],
     "madqp_malloc": [vp, C.c_size_t, C.POINTER(vp)],
     "madqp_free": [vp, vp],
     "madqp_memcpy_h2d": [vp, vp, vp, C.c_size_t],

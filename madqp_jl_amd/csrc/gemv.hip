@@ -342,54 +342,42 @@ int32_t madqp_symv_upper(madqp_ctx* ctx, int64_t n, double alpha, const double* 
     return symv_tri(ctx, true, n, alpha, H, ldh, x, beta, y, prof_cls);
 }
 
-int32_t madqp_gemv_impl(madqp_ctx* ctx, int32_t trans, int64_t rows, int64_t cols, double alpha,
-                        const double* A, int64_t lda, const double* x, double beta, double* y,
-                        int prof_cls) {
-    ARG_TRY(ctx, ctx != nullptr);
-    ARG_TRY(ctx, rows >= 0 && cols >= 0 && (trans == 0 || trans == 1));
+// The dispatcher's choice, in ONE place: what madqp_gemv_impl launches for these arguments (the form, 16-byte loads or
+// not, row chunks, workgroups of the product kernel).  Host only; A and x are inspected as addresses, never
+// dereferenced.  madqp_debug_gemv_form reports the same struct (tests/test_gemv_form.py holds every constant below
+// from both sides).  MADQP_ERR_ARG: arguments the product refuses.
+static int32_t gemv_plan(int32_t trans, int64_t rows, int64_t cols, const double* A, int64_t lda, const double* x,
+                         madqp_debug_gemv_form_info* p) {
+    *p = madqp_debug_gemv_form_info{};
+    if (!(rows >= 0 && cols >= 0 && (trans == 0 || trans == 1))) return MADQP_ERR_ARG;
     const int64_t ylen = trans ? cols : rows, klen = trans ? rows : cols;
-    if (ylen == 0) return MADQP_OK;
-    ARG_TRY(ctx, y != nullptr);
-    if (klen == 0) {  // y = beta*y
-        ProfScope ps(ctx, prof_cls);
-        hipLaunchKernelGGL(scale_kernel, dim3((ylen + 255) / 256), dim3(256), 0, ctx->stream, ylen,
-                           beta, y);
-        LAUNCH_CHECK(ctx);
+    if (ylen == 0) return MADQP_OK;  // MADQP_GEMV_FORM_NONE
+    if (klen == 0) {                 // y = beta*y
+        p->form = MADQP_GEMV_FORM_SCALE;
+        p->workgroups = (ylen + 255) / 256;
         return MADQP_OK;
     }
-    ARG_TRY(ctx, A && x && lda >= cols);
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    if (!(A && x && lda >= cols)) return MADQP_ERR_ARG;
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     if (trans == 0) {
-        const bool vec = al16(A) && al16(x) && (lda % 2 == 0);
-        ProfScope ps(ctx, prof_cls);
+        p->vec = al16(A) && al16(x) && (lda % 2 == 0);
         if (rows >= 2048 || cols <= 1024) {
-            const int64_t blocks = std::min<int64_t>((rows + 3) / 4, 8192);
-            if (vec)
-                hipLaunchKernelGGL(gemv_n_wave_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream,
-                                   rows, cols, alpha, A, lda, x, beta, y);
-            else
-                hipLaunchKernelGGL(gemv_n_wave_kernel<false>, dim3(blocks), dim3(256), 0,
-                                   ctx->stream, rows, cols, alpha, A, lda, x, beta, y);
+            p->form = MADQP_GEMV_FORM_N_WAVE;
+            p->workgroups = std::min<int64_t>((rows + 3) / 4, 8192);
         } else {
-            const int64_t blocks = std::min<int64_t>(rows, 4096);
-            if (vec)
-                hipLaunchKernelGGL(gemv_n_block_kernel<true>, dim3(blocks), dim3(256), 0,
-                                   ctx->stream, rows, cols, alpha, A, lda, x, beta, y);
-            else
-                hipLaunchKernelGGL(gemv_n_block_kernel<false>, dim3(blocks), dim3(256), 0,
-                                   ctx->stream, rows, cols, alpha, A, lda, x, beta, y);
+            p->form = MADQP_GEMV_FORM_N_BLOCK;
+            p->workgroups = std::min<int64_t>(rows, 4096);
         }
-        LAUNCH_CHECK(ctx);
         return MADQP_OK;
     }
     // trans == 1
-    const bool vec = al16(A) && (lda % 2 == 0);
+    p->vec = al16(A) && (lda % 2 == 0);
     static const bool strip_on = !(getenv("MADQP_GEMV_T_STRIP") && atoi(getenv("MADQP_GEMV_T_STRIP")) == 0);
-    if (strip_on && vec && cols >= 2048 && rows >= 64 && rows <= 16384 && rows * cols <= ((int64_t)1 << 27)) {
-        ProfScope ps(ctx, prof_cls);
-        hipLaunchKernelGGL(gemv_t_strip_kernel, dim3((unsigned)((cols + 15) / 16)), dim3(256), 0, ctx->stream, rows, cols, alpha,
-                           A, lda, x, beta, y);
-        LAUNCH_CHECK(ctx);
+    if (strip_on && p->vec && cols >= 2048 && rows >= 64 && rows <= 16384 && rows * cols <= ((int64_t)1 << 27)) {
+        p->form = MADQP_GEMV_FORM_T_STRIP;
+        p->chunks = 1;
+        p->rows_per_chunk = rows;
+        p->workgroups = (cols + 15) / 16;
         return MADQP_OK;
     }
     const int64_t ctiles = (cols + 127) / 128;
@@ -398,12 +386,72 @@ int32_t madqp_gemv_impl(madqp_ctx* ctx, int32_t trans, int64_t rows, int64_t col
     int64_t rpc = (rows + nchunks - 1) / nchunks;
     rpc = (rpc + 3) / 4 * 4;
     nchunks = (rows + rpc - 1) / rpc;
+    p->form = nchunks == 1 ? MADQP_GEMV_FORM_T_SINGLE : MADQP_GEMV_FORM_T_CHUNKED;
+    p->chunks = nchunks;
+    p->rows_per_chunk = rpc;
+    p->workgroups = ctiles * nchunks;
+    return MADQP_OK;
+}
+
+int32_t madqp_gemv_impl(madqp_ctx* ctx, int32_t trans, int64_t rows, int64_t cols, double alpha,
+                        const double* A, int64_t lda, const double* x, double beta, double* y,
+                        int prof_cls) {
+    ARG_TRY(ctx, ctx != nullptr);
+    ARG_TRY(ctx, rows >= 0 && cols >= 0 && (trans == 0 || trans == 1));
+    const int64_t ylen = trans ? cols : rows, klen = trans ? rows : cols;
+    if (ylen == 0) return MADQP_OK;
+    ARG_TRY(ctx, y != nullptr);
+    if (klen != 0) ARG_TRY(ctx, A && x && lda >= cols);
+    madqp_debug_gemv_form_info p;
+    ARG_TRY(ctx, gemv_plan(trans, rows, cols, A, lda, x, &p) == MADQP_OK);
+    const bool vec = p.vec != 0;
+    const dim3 grid1((unsigned)p.workgroups);
+    switch (p.form) {
+    case MADQP_GEMV_FORM_SCALE: {
+        ProfScope ps(ctx, prof_cls);
+        hipLaunchKernelGGL(scale_kernel, grid1, dim3(256), 0, ctx->stream, ylen, beta, y);
+        LAUNCH_CHECK(ctx);
+        return MADQP_OK;
+    }
+    case MADQP_GEMV_FORM_N_WAVE: {
+        ProfScope ps(ctx, prof_cls);
+        if (vec)
+            hipLaunchKernelGGL(gemv_n_wave_kernel<true>, grid1, dim3(256), 0, ctx->stream, rows, cols, alpha, A, lda, x,
+                               beta, y);
+        else
+            hipLaunchKernelGGL(gemv_n_wave_kernel<false>, grid1, dim3(256), 0, ctx->stream, rows, cols, alpha, A, lda, x,
+                               beta, y);
+        LAUNCH_CHECK(ctx);
+        return MADQP_OK;
+    }
+    case MADQP_GEMV_FORM_N_BLOCK: {
+        ProfScope ps(ctx, prof_cls);
+        if (vec)
+            hipLaunchKernelGGL(gemv_n_block_kernel<true>, grid1, dim3(256), 0, ctx->stream, rows, cols, alpha, A, lda, x,
+                               beta, y);
+        else
+            hipLaunchKernelGGL(gemv_n_block_kernel<false>, grid1, dim3(256), 0, ctx->stream, rows, cols, alpha, A, lda, x,
+                               beta, y);
+        LAUNCH_CHECK(ctx);
+        return MADQP_OK;
+    }
+    case MADQP_GEMV_FORM_T_STRIP: {
+        ProfScope ps(ctx, prof_cls);
+        hipLaunchKernelGGL(gemv_t_strip_kernel, grid1, dim3(256), 0, ctx->stream, rows, cols, alpha, A, lda, x, beta, y);
+        LAUNCH_CHECK(ctx);
+        return MADQP_OK;
+    }
+    default:
+        break;
+    }
+    // the 128-column tiles: one chunk of rows writes y itself, several leave partials for the reduce
+    const int64_t nchunks = p.chunks, rpc = p.rows_per_chunk;
     if (nchunks > 1) {
         int32_t r = madqp_work_reserve(ctx, (size_t)nchunks * cols * sizeof(double));
         if (r) return r;
     }
     ProfScope ps(ctx, prof_cls);
-    dim3 grid((unsigned)ctiles, (unsigned)nchunks);
+    dim3 grid((unsigned)(p.workgroups / nchunks), (unsigned)nchunks);
     if (nchunks == 1) {
         if (vec)
             hipLaunchKernelGGL((gemv_t_kernel<true, true>), grid, dim3(256), 0, ctx->stream, rows,
@@ -425,6 +473,22 @@ int32_t madqp_gemv_impl(madqp_ctx* ctx, int32_t trans, int64_t rows, int64_t col
         LAUNCH_CHECK(ctx);
     }
     return MADQP_OK;
+}
+
+// Test seams (include/madqp.h; tests/test_gemv_form.py, tests/test_gpu_matvec.py): the dispatcher's plan for a call, and
+// symv_tri for either side at any order (the solver reaches it from MADQP_SYMV_MIN / 2048 only).
+extern "C" int32_t madqp_debug_gemv_form(int32_t trans, int64_t rows, int64_t cols, const double* A, int64_t lda,
+                                         const double* x, madqp_debug_gemv_form_info* out_host) {
+    if (!out_host) return MADQP_ERR_ARG;
+    return gemv_plan(trans, rows, cols, A, lda, x, out_host);
+}
+extern "C" int32_t madqp_debug_symv(madqp_ctx* ctx, int32_t upper, int64_t n, double alpha, const double* H, int64_t ldh,
+                                    const double* x, double beta, double* y) {
+    if (!ctx) return MADQP_ERR_ARG;
+    ARG_TRY(ctx, (upper == 0 || upper == 1) && n >= 0);
+    if (n == 0) return MADQP_OK;
+    ARG_TRY(ctx, H && x && y && ldh >= n && ldh % 2 == 0 && (((uintptr_t)H) & 15) == 0);
+    return symv_tri(ctx, upper != 0, n, alpha, H, ldh, x, beta, y, MADQP_PROF_GEMV);
 }
 
 extern "C" int32_t madqp_gemv(madqp_ctx* ctx, int32_t trans, int64_t rows, int64_t cols,

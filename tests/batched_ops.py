@@ -120,9 +120,9 @@ def wide_rows(Mx, x):
     return ref.astype(LD), S.astype(LD)
 
 
-def check_product(out, Mx, x, alpha, beta, y0, label):
+def check_product(out, Mx, x, alpha, beta, y0, label, wide=None):
     """out = alpha * Mx @ x + beta * y0 (y0 ignored when beta == 0), inner length Mx.shape[1]; returns the worst err / bound
-    against the extended-precision reference."""
+    against the extended-precision reference.  wide: wide_rows(Mx, x) where the caller shares it among several checks."""
     n = Mx.shape[1]
     assert np.all(np.isfinite(out)), f"{label}: non-finite entries at {np.flatnonzero(~np.isfinite(out))[:8]}"
     add = beta * y0 if beta != 0.0 else np.zeros(Mx.shape[0])
@@ -132,7 +132,7 @@ def check_product(out, Mx, x, alpha, beta, y0, label):
     bad = ~(err <= bound)
     assert not bad.any(), f"{label}: {int(bad.sum())} entries beyond 2 (len + 4) u S against float64, first at {int(np.argmax(bad))}: " \
                           f"out {out[np.argmax(bad)]!r} ref {ref64[np.argmax(bad)]!r} bound {bound[np.argmax(bad)]:.3e}"
-    w, Sw = wide_rows(Mx, x)
+    w, Sw = wide_rows(Mx, x) if wide is None else wide
     ref = LD(alpha) * w + add.astype(LD)
     S = LD(abs(alpha)) * Sw + np.abs(add).astype(LD)
     err, bound = np.abs(out.astype(LD) - ref), LD((n + 4) * U) * S

@@ -69,6 +69,21 @@ def test_debug_batch_op_struct_layout_matches_header():
     assert [e.lower() for e in re.findall(r"MADQP_DEBUG_OP_([A-Z_]+)", enum)] == list(DEBUG_OPS)
 
 
+def test_debug_gemv_form_struct_layout_matches_header():
+    """The test seam madqp_debug_gemv_form: 8-byte fields only, in the header's order; the form names follow the enum."""
+    from madqp_jl_amd._lib import GEMV_FORMS, CDebugGemvForm
+
+    hdr = open(os.path.join(ROOT, "include", "madqp.h")).read()
+    name = "madqp_debug_gemv_form_info"
+    body = hdr[hdr.index("typedef struct %s {" % name):hdr.index("} %s;" % name)]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).split("{", 1)[1]
+    names = re.findall(r"\*?\s*([A-Za-z_0-9]+)\s*[,;]", body)
+    assert [f[0] for f in CDebugGemvForm._fields_] == names
+    assert ctypes.sizeof(CDebugGemvForm) == 8 * len(names)
+    enum = hdr[hdr.index("MADQP_GEMV_FORM_NONE = 0"):hdr.index("MADQP_GEMV_FORM_COUNT")]
+    assert [e.lower() for e in re.findall(r"MADQP_GEMV_FORM_([A-Z_]+)", enum)] == list(GEMV_FORMS)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_no_cpu_fallback():
     with pytest.raises(M.MadQPError):
@@ -83,6 +98,8 @@ def test_usage_errors_are_return_codes_not_aborts():
     assert lib.madqp_chol_solve(None, None) == -1
     assert lib.madqp_debug_batch_op(None, None) == -1
     assert lib.madqp_debug_chol_factor_batched(None, None, 0, 0, 0, None, 0, None, 0, None, 0, None, None) == -1
+    assert lib.madqp_debug_gemv_form(0, 1, 1, None, 1, None, None) == -1
+    assert lib.madqp_debug_symv(None, 0, 1, 1.0, None, 2, None, 0.0, None) == -1
     assert lib.madqp_last_error(None) == b"null context"
 
 
