@@ -36,14 +36,17 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <tuple>
 
 #include "common.h"
+#include "gemm_plan.inc"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 #include "gemm_core.inc"
+static_assert(BM == GEMM_TILE && BN == GEMM_TILE && BK == GEMM_KSTEP, "gemm_plan.inc plans for the tiles of gemm_core.inc");
 
 struct KArgs {
     GemmArgs g;
@@ -283,23 +286,19 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs g, const in
     }
 }
 
+// Identity of a tile table: what gemm_tile_table builds it from.  An unmasked product has an empty mask, which allocates
+// nothing; a masked one (the distributed driver: hundreds of masks per context) copies its mask once per call.
 struct TableKey {
-    int64_t tm, tn, lower, doff;
-    uint64_t cols_hash;  // 0: all tile columns
+    int64_t tm, tn, flags, doff;  // tile counts; lower_only | partial last tile row << 1 | column << 2; diag_off if lower
+    GemmMask kind;
+    std::vector<int64_t> mask;  // the column ranges / per-column first rows
     bool operator<(const TableKey& o) const {
-        if (tm != o.tm) return tm < o.tm;
-        if (tn != o.tn) return tn < o.tn;
-        if (lower != o.lower) return lower < o.lower;
-        if (doff != o.doff) return doff < o.doff;
-        return cols_hash < o.cols_hash;
+        return std::tie(tm, tn, flags, doff, kind, mask) < std::tie(o.tm, o.tn, o.flags, o.doff, o.kind, o.mask);
     }
 };
 struct TableVal {
     int32_t* d;
     int32_t n;
-    std::vector<int64_t> mask;  // the column ranges / per-column first rows the table was built for: the key holds only
-                                // their hash, a hit is a hit only if these agree (the distributed path makes hundreds
-                                // of masks per context)
 };
 // per-context cache of tile tables.  A context is used by one host thread at a time, different
 // contexts may live on different threads (batch sharding): the outer map is guarded by a mutex,
@@ -316,6 +315,33 @@ std::map<TableKey, TableVal>& tables_of(madqp_ctx* ctx) {
     std::lock_guard<std::mutex> lock(table_mutex());
     return table_cache()[ctx];
 }
+
+const GemmModes& gemm_modes() {  // the environment switches, read once, at the first use
+    static const GemmModes modes = [] {
+        auto num = [](const char* name, int64_t dflt) { return getenv(name) ? (int64_t)atoi(getenv(name)) : dflt; };
+        GemmModes m;
+        m.splitk = (int)num("MADQP_GEMM_SPLITK", m.splitk);
+        m.tailsplit = (int)num("MADQP_GEMM_TAILSPLIT", m.tailsplit);
+        m.seg_rounds = (int)num("MADQP_GEMM_SEG_ROUNDS", m.seg_rounds);
+        m.xcd = (int)num("MADQP_GEMM_XCD", m.xcd);
+        m.batch_xcd = (int)num("MADQP_GEMM_BATCH_XCD", m.batch_xcd);
+        m.patch_m = num("MADQP_GEMM_PATCH_M", m.patch_m);  // (tuning knobs for experiments)
+        m.patch_n = num("MADQP_GEMM_PATCH_N", m.patch_n);
+        return m;
+    }();
+    return modes;
+}
+
+// The n tiles at `table` cut into S chunks of K, one workgroup per (tile, chunk), raw partial tiles to the workspace;
+// splitk_reduce_kernel sums them in chunk order and applies the epilogue: same result on every run.
+int32_t launch_split(madqp_ctx* ctx, KArgs ka, const int32_t* table, int32_t n, int32_t S, int64_t chunk) {
+    ka.table = table, ka.ntiles = n, ka.ksplit = S, ka.kchunk = chunk, ka.work = ctx->d_work;
+    hipLaunchKernelGGL(gemm_tn_f64_kernel, dim3(n, (unsigned)S), dim3(NTHREADS), 0, ctx->stream, ka);
+    LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, ka.g, table, n, S, ka.work);
+    LAUNCH_CHECK(ctx);
+    return MADQP_OK;
+}
 }  // namespace
 
 void madqp_gemm_release_tables(madqp_ctx* ctx) {
@@ -331,9 +357,10 @@ void madqp_gemm_release_tables(madqp_ctx* ctx) {
     for (auto& kv : mine) (void)hipFree(kv.second.d);
 }
 
+// Validates, fetches the tile table, asks gemm_plan (gemm_plan.inc) what to launch and launches it.
 int32_t madqp_gemm_tn(madqp_ctx* ctx, const GemmArgs& a, int prof_cls, const int64_t* cols, int64_t ncols,
                       const GemmBatch* batch, madqp_debug_gemm_info* info) {
-    if (info) {  // (test seam only, madqp_debug_gemm_tn: what this call launched)
+    if (info) {  // (test seam only, madqp_debug_gemm_tn: what this call launched; filled from the plan at the end)
         *info = madqp_debug_gemm_info{};
         info->gemm_slots = ctx ? ctx->gemm_slots : 0;
     }
@@ -341,233 +368,69 @@ int32_t madqp_gemm_tn(madqp_ctx* ctx, const GemmArgs& a, int prof_cls, const int
     if (a.M == 0 || a.N == 0) return MADQP_OK;
     const int64_t tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN - 1) / BN;
     ARG_TRY(ctx, tiles_m < 65536 && tiles_n < 32768);
-    uint64_t cols_hash = 0;
-    std::vector<char> col_on;
+    const GemmModes& md = gemm_modes();
+    TableKey key{tiles_m, tiles_n, (a.lower_only ? 1 : 0) | ((a.M % BM) != 0 ? 2 : 0) | ((a.N % BN) != 0 ? 4 : 0),
+                 a.lower_only ? a.diag_off : 0, GEMM_MASK_NONE, {}};
     if (cols) {
-        col_on.assign((size_t)tiles_n, 0);
-        cols_hash = 1469598103934665603ull;  // FNV-1a over the range list
-        for (int64_t r = 0; r < 2 * ncols; ++r) {
+        for (int64_t r = 0; r < 2 * ncols; ++r)
             ARG_TRY(ctx, cols[r] >= 0 && cols[r] <= a.N && (cols[r] % BN == 0 || cols[r] == a.N));
-            cols_hash = (cols_hash ^ (uint64_t)cols[r]) * 1099511628211ull;
-        }
-        if (cols_hash == 0) cols_hash = 1;
-        for (int64_t r = 0; r < ncols; ++r)
-            for (int64_t t = cols[2 * r] / BN; t < (cols[2 * r + 1] + BN - 1) / BN; ++t) col_on[(size_t)t] = 1;
+        key.kind = GEMM_MASK_COLS;
+        key.mask.assign(cols, cols + 2 * ncols);
     }
-    if (a.tile_row0) {  // per-column first active tile row: part of the table's identity
+    if (a.tile_row0) {  // per-column first active tile row
         ARG_TRY(ctx, !cols && !a.lower_only);
-        cols_hash = 1469598103934665603ull ^ 0x9E3779B97F4A7C15ull;
-        for (int64_t t = 0; t < tiles_n; ++t) cols_hash = (cols_hash ^ (uint64_t)a.tile_row0[t]) * 1099511628211ull;
-        if (cols_hash == 0) cols_hash = 1;
+        key.kind = GEMM_MASK_ROW0;
+        key.mask.assign(a.tile_row0, a.tile_row0 + tiles_n);
     }
-    // diag_off in tile units must be exact for the tile-skip test used when building the table
-    TableKey key{tiles_m, tiles_n,
-                 (a.lower_only ? 1 : 0) | ((a.M % BM) != 0 ? 2 : 0) | ((a.N % BN) != 0 ? 4 : 0),
-                 a.lower_only ? a.diag_off : 0, cols_hash};
-    std::vector<int64_t> mask;
-    if (cols) mask.assign(cols, cols + 2 * ncols);
-    if (a.tile_row0) mask.assign(a.tile_row0, a.tile_row0 + tiles_n);
     auto& cache = tables_of(ctx);
     auto it = cache.find(key);
-    while (it != cache.end() && it->second.mask != mask) {  // same hash, another mask: walk to a free or matching key
-        key.cols_hash += 0x9E3779B97F4A7C15ull;
-        if (key.cols_hash == 0) key.cols_hash = 1;
-        it = cache.find(key);
-    }
     if (it == cache.end()) {
-        std::vector<int32_t> tab;
-        tab.reserve((size_t)tiles_m * tiles_n);
-        // patch of PM x PN tiles (tuning knobs for experiments: MADQP_GEMM_PATCH_M / _N)
-        static const int64_t PM = getenv("MADQP_GEMM_PATCH_M") ? atoi(getenv("MADQP_GEMM_PATCH_M")) : 8;
-        static const int64_t PN = getenv("MADQP_GEMM_PATCH_N") ? atoi(getenv("MADQP_GEMM_PATCH_N")) : 8;
-        // Edge tiles (partial last tile row / column, or K not a multiple of 16) run the slower
-        // register-staged loop: they go FIRST so that they overlap with the bulk instead of forming
-        // the tail of the launch.
-        const bool m_edge = (a.M % BM) != 0, n_edge = (a.N % BN) != 0;
-        auto active = [&](int64_t tm, int64_t tn) {
-            if (cols && !col_on[(size_t)tn]) return false;
-            if (a.tile_row0 && tm < a.tile_row0[tn]) return false;
-            return !(a.lower_only && (tm * BM + BM - 1 + a.diag_off < tn * BN));
-        };
-        auto is_edge = [&](int64_t tm, int64_t tn) {
-            return (m_edge && tm == tiles_m - 1) || (n_edge && tn == tiles_n - 1);
-        };
-        if (m_edge)
-            for (int64_t tn = 0; tn < tiles_n; ++tn)
-                if (active(tiles_m - 1, tn)) tab.push_back((int32_t)(((tiles_m - 1) << 16) | tn));
-        if (n_edge)
-            for (int64_t tm = 0; tm < tiles_m - (m_edge ? 1 : 0); ++tm)
-                if (active(tm, tiles_n - 1)) tab.push_back((int32_t)((tm << 16) | (tiles_n - 1)));
-        for (int64_t pm = 0; pm < tiles_m; pm += PM)
-            for (int64_t pn = 0; pn < tiles_n; pn += PN)
-                for (int64_t tn = pn; tn < pn + PN && tn < tiles_n; ++tn)
-                    for (int64_t tm = pm; tm < pm + PM && tm < tiles_m; ++tm) {
-                        if (!active(tm, tn) || is_edge(tm, tn)) continue;
-                        tab.push_back((int32_t)((tm << 16) | tn));
-                    }
-        TableVal v{nullptr, (int32_t)tab.size(), mask};
+        const std::vector<int32_t> tab = gemm_tile_table(a.M, a.N, a.lower_only != 0, a.diag_off, key.kind, key.mask.data(),
+                                                         (int64_t)key.mask.size(), md.patch_m, md.patch_n);
+        TableVal v{nullptr, (int32_t)tab.size()};
         if (!tab.empty()) {
             HIP_TRY(ctx, hipMalloc(&v.d, tab.size() * sizeof(int32_t)));
-            HIP_TRY(ctx, hipMemcpyAsync(v.d, tab.data(), tab.size() * sizeof(int32_t),
-                                        hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(v.d, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
-        it = cache.emplace(key, v).first;
+        it = cache.emplace(std::move(key), v).first;
     }
     if (it->second.n == 0) return MADQP_OK;
-    KArgs ka;
-    ka.g = a;
-    ka.table = it->second.d;
-    ka.ntiles = it->second.n;
-    static const int xcd_remap = getenv("MADQP_GEMM_XCD") ? atoi(getenv("MADQP_GEMM_XCD")) : 1;
-    ka.xcd_remap = xcd_remap;
-    ka.batch = batch ? *batch : GemmBatch{1, 0, 0, 0, 0, 0, nullptr};
-    unsigned gy = (unsigned)std::max<int64_t>(1, ka.batch.B);
-    ARG_TRY(ctx, gy <= 65535);
-    static const int batch_xcd = getenv("MADQP_GEMM_BATCH_XCD") ? atoi(getenv("MADQP_GEMM_BATCH_XCD")) : 1;
-    ka.batch_xcd = (batch_xcd && batch && !ka.batch.list && ka.batch.B >= 8 && ka.batch.B % 8 == 0) ? 1 : 0;
-    // Split-K: a launch with far fewer tiles than resident workgroups leaves most of the chip idle while
-    // each tile walks all of K alone (5k-20k matrices, the last panels of a large one).  Cut K into up
-    // to 16 chunks of >= 256, one workgroup per (tile, chunk), partials summed in chunk order by a second
-    // small kernel: same result on every run.
-    static const int split_on = getenv("MADQP_GEMM_SPLITK") ? atoi(getenv("MADQP_GEMM_SPLITK")) : 1;
-    ka.ksplit = 1;
-    ka.kchunk = a.K;
-    ka.work = nullptr;
-    int64_t S_few = 0;
-    if (split_on && !batch && (int64_t)ka.ntiles * 2 > ctx->gemm_slots && (int64_t)ka.ntiles < 8 * ctx->gemm_slots &&
-        a.K >= 4096) {
-        // A launch of a few rounds of LONG tiles (the wide updates of the lazy distributed schedule, whose tile-column
-        // width is the grid's tile and cannot be tuned to fill the rounds as chol.hip tunes its panels: 560 tiles of
-        // K = 38 000 take two rounds of 11 ms, the second one a tenth full, and whoever shares a CU with a finished
-        // workgroup runs on alone): cut K into S chunks -- more, shorter rounds.  S minimises the model
-        //   rounds(S) x (tile time of K/S + fixed cost of a tile) + pass over the S x tiles partial tiles
-        // (microseconds: 0.216 per unit of K, 10 per tile, 0.05 per partial tile).  With short tiles (n_x = 5 000:
-        // K = 2 000) the model and the measurement agree that it does not pay; those launches are left alone.
-        auto cost = [&](int64_t S) {  // (an extra term for the drain of the last round was tried: 0.5 .. 2 tile times cost 0 .. 5 ms)
-            const double rounds = std::ceil((double)ka.ntiles * (double)S / (double)ctx->gemm_slots);
-            return rounds * (0.216 * (double)a.K / (double)S + 10.0) + 0.05 * (double)S * (double)ka.ntiles;
-        };
-        double best = cost(1) * 0.97;
-        for (int64_t S = 2; S <= 16 && a.K / S >= 2048; ++S)
-            if (cost(S) < best) {
-                best = cost(S);
-                S_few = S;
-            }
-    }
-    if (split_on && !batch && (((int64_t)ka.ntiles * 2 <= ctx->gemm_slots && a.K >= 512) || S_few)) {
-        int64_t S = S_few ? S_few : std::min<int64_t>(std::min<int64_t>(ctx->gemm_slots / ka.ntiles, a.K / 256), 16);
-        if (S >= 2) {
-            const int64_t chunk = ((a.K + S - 1) / S + BK - 1) / BK * BK;
-            S = (a.K + chunk - 1) / chunk;
-            if (S >= 2) {
-                const size_t bytes = (size_t)S * ka.ntiles * BM * BN * sizeof(double);
-                int32_t r = madqp_work_reserve(ctx, bytes);
-                if (r) return r;
-                ka.ksplit = (int32_t)S;
-                ka.kchunk = chunk;
-                ka.work = ctx->d_work;
-                gy = (unsigned)S;
-            }
-        }
-    }
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    ka.fast_ok = al16(a.X) && al16(a.Y) && (a.ldx % 2 == 0) && (a.ldy % 2 == 0);
-    if (info) {
-        info->ntiles = ka.ntiles;
-        info->ksplit = ka.ksplit;
-        info->kchunk = ka.kchunk;
-        info->fast_ok = ka.fast_ok;
-        info->batch_xcd = ka.batch_xcd;
-    }
+    const int32_t* table = it->second.d;
+    const GemmPlan p = gemm_plan(it->second.n, a.K, ctx->gemm_slots, ctx->gemm_cap_slots,
+                                 !batch ? GEMM_SINGLE : batch->list ? GEMM_BATCH_LIST : GEMM_BATCH, batch ? batch->B : 1, md);
+    ARG_TRY(ctx, p.gy <= 65535);
+    if (int32_t r = madqp_work_reserve(ctx, p.work_bytes)) return r;  // (nothing for a launch of whole tiles)
+    auto al16 = [](const void* ptr) { return ((uintptr_t)ptr & 15) == 0; };
+    const int32_t fast_ok = al16(a.X) && al16(a.Y) && (a.ldx % 2 == 0) && (a.ldy % 2 == 0);
+    KArgs ka{a, table, p.ntiles, fast_ok, md.xcd, p.batch_xcd, batch ? *batch : GemmBatch{1, 0, 0, 0, 0, 0, nullptr},
+             1, a.K, nullptr};  // (whole tiles; launch_split sets the three split fields)
 #ifdef MADQP_STAMPS
     extern unsigned long long* madqp_stamp_buffer;
     ka.stamps = madqp_stamp_buffer;
 #endif
-    // Tail split (round 4): a launch of one to three rounds whose LAST round is partly empty -- the assembly of a
-    // mid-size matrix: 820 tiles on 512 slots are 1.6 rounds that take the time of 2 -- runs its whole rounds as they are
-    // and cuts only the tiles of the last round into S chunks of K (more, shorter pieces that fill the chip), summed in
-    // chunk order by splitk_reduce_kernel like every split launch: same result on every run.  S from the same cost model
-    // as above (microseconds: 0.216 per unit of K and 10 per piece, 0.05 per partial tile of the second pass).
-    int64_t tail_S = 0, tail_n = 0;
-    static const int tail_on = getenv("MADQP_GEMM_TAILSPLIT") ? atoi(getenv("MADQP_GEMM_TAILSPLIT")) : 1;
-    if (split_on && tail_on && !batch && ka.ksplit == 1 && a.K >= 1024 && ctx->gemm_cap_slots == 0 &&
-        (int64_t)ka.ntiles > ctx->gemm_slots && (int64_t)ka.ntiles < 4 * ctx->gemm_slots) {
-        const int64_t slots = ctx->gemm_slots, tl = (int64_t)ka.ntiles % slots;
-        if (tl > 0 && 10 * tl < 8 * slots) {
-            const double tile = 0.216 * (double)a.K + 10.0;
-            double best = tile * 0.93;  // (the last round as it is; worth it only with a clear gain)
-            for (int64_t S = 2; S <= 8 && a.K / S >= 256; ++S) {
-                const double rounds = std::ceil((double)tl * (double)S / (double)slots);
-                const double c = rounds * (0.216 * (double)a.K / (double)S + 10.0) + 0.05 * (double)S * (double)tl;
-                if (c < best) {
-                    best = c;
-                    tail_S = S;
-                }
-            }
-            if (tail_S) tail_n = tl;
-        }
-    }
-    // Long launches are cut into segments of 64 rounds of resident workgroups.  Equal-cost tiles
-    // that start together sweep K in lockstep and share their operand panels through the XCD's
-    // L2; over many rounds that lockstep diffuses away (measured at n = 50000, K = 20480: 0.93-1.3 TB
-    // fetched by one assembly launch, 0.75 TB when re-synchronised every 64 rounds, floor 0.68 TB).
-    // The last round of a segment finishes almost simultaneously: +0.25 % time.
-    static const int seg_rounds = getenv("MADQP_GEMM_SEG_ROUNDS") ? atoi(getenv("MADQP_GEMM_SEG_ROUNDS")) : 64;
-    const int64_t seg = seg_rounds > 0 ? (int64_t)seg_rounds * ctx->gemm_slots : (int64_t)ka.ntiles;
-    const int32_t* table0 = ka.table;
-    const int32_t total = ka.ntiles - (int32_t)tail_n;  // (tiles launched whole)
     ProfScope ps(ctx, prof_cls);
-    // capped launch (ctx->gemm_cap_slots, set by dist.hip around a bulk trailing update): a persistent grid that leaves
-    // workgroup slots free for the kernels of other streams
-    const int64_t capped = ctx->gemm_cap_slots > 0 ? std::max<int64_t>(8, (ctx->gemm_slots - ctx->gemm_cap_slots) / 8 * 8) : 0;
-    if (capped && ka.ksplit == 1 && !batch && total > capped) {
+    if (p.persistent) {
         if (!ctx->d_tickets) HIP_TRY(ctx, hipMalloc(&ctx->d_tickets, 8 * sizeof(unsigned long long)));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_tickets, 0, 8 * sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(gemm_tn_f64_persistent_kernel, dim3((unsigned)capped), dim3(NTHREADS), 0, ctx->stream, ka,
+        hipLaunchKernelGGL(gemm_tn_f64_persistent_kernel, dim3((unsigned)p.persistent), dim3(NTHREADS), 0, ctx->stream, ka,
                            ctx->d_tickets);
         LAUNCH_CHECK(ctx);
-        if (info) info->persistent_workgroups = capped;
-        return MADQP_OK;
-    }
-    for (int64_t off = 0; off < total; off += seg) {
-        int64_t cnt = std::min<int64_t>(seg, total - off);
-        if (total - off - cnt < seg / 4) cnt = total - off;  // no tiny last segment
-        ka.table = table0 + off;
-        ka.ntiles = (int32_t)cnt;
-        hipLaunchKernelGGL(gemm_tn_f64_kernel, dim3(ka.ntiles, gy), dim3(NTHREADS), 0, ctx->stream, ka);
-        LAUNCH_CHECK(ctx);
-        if (info) info->segments += 1;
-        if (cnt == total - off) break;
-    }
-    if (tail_n) {  // the tiles of the last round, K-split
-        const int64_t chunk = ((a.K + tail_S - 1) / tail_S + BK - 1) / BK * BK;
-        const int64_t S = (a.K + chunk - 1) / chunk;
-        const size_t bytes = (size_t)S * tail_n * BM * BN * sizeof(double);
-        int32_t r = madqp_work_reserve(ctx, bytes);
-        if (r) return r;
-        ka.table = table0 + total;
-        ka.ntiles = (int32_t)tail_n;
-        ka.ksplit = (int32_t)S;
-        ka.kchunk = chunk;
-        ka.work = ctx->d_work;
-        hipLaunchKernelGGL(gemm_tn_f64_kernel, dim3(ka.ntiles, (unsigned)S), dim3(NTHREADS), 0, ctx->stream, ka);
-        LAUNCH_CHECK(ctx);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)tail_n), dim3(256), 0, ctx->stream, a, table0 + total,
-                           (int32_t)tail_n, (int32_t)S, ka.work);
-        LAUNCH_CHECK(ctx);
-        if (info) {
-            info->tail_tiles = tail_n;
-            info->tail_split = S;
-            info->kchunk = chunk;
+    } else if (p.ksplit > 1) {
+        if (int32_t r = launch_split(ctx, ka, table, p.whole, p.ksplit, p.kchunk)) return r;
+    } else {
+        for (int64_t off = 0; off < p.whole; off += ka.ntiles) {
+            ka.table = table + off;
+            ka.ntiles = (int32_t)gemm_segment(p, off);
+            hipLaunchKernelGGL(gemm_tn_f64_kernel, dim3(ka.ntiles, p.gy), dim3(NTHREADS), 0, ctx->stream, ka);
+            LAUNCH_CHECK(ctx);
         }
-        return MADQP_OK;
     }
-    if (ka.ksplit > 1) {  // (a split launch is always a single segment: few tiles)
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(total), dim3(256), 0, ctx->stream, a, table0, total, ka.ksplit,
-                           ka.work);
-        LAUNCH_CHECK(ctx);
-    }
+    if (p.tail_tiles)  // the tiles of the last round, K-split
+        if (int32_t r = launch_split(ctx, ka, table + p.whole, p.tail_tiles, p.tail_split, p.tail_chunk)) return r;
+    if (info)
+        *info = madqp_debug_gemm_info{p.ntiles, p.ksplit, p.tail_tiles ? p.tail_chunk : p.kchunk, p.tail_tiles, p.tail_split,
+                                      p.segments, p.persistent, fast_ok, p.batch_xcd, ctx->gemm_slots};
     return MADQP_OK;
 }
 
