@@ -449,7 +449,8 @@ int32_t madqp_kkt_matrix(madqp_kkt* kkt, double** K, int64_t* ld);
 /* create_kkt_system with the Jacobian kept sparse, as the reference does (coo_to_csr src/utils.jl:148-197,
  * src/KKT/normalkkt.jl:51-101): A in CSR (a_*: m rows) and A' in CSR (at_*: nx rows = the CSC of A), device
  * int64 / double arrays, column indices ascending within a row, borrowed.  mode 0: condensed
- * K = H + Sigma_x + A' Theta A (H dense or NULL); mode 1: normal equations A Sigma^-1 A' (LP only,
+ * K = H + Sigma_x + A' Theta A (H dense, NULL, diagonal or CSR: a dense H is passed here, a diagonal one goes through
+ * madqp_kkt_set_hdiag, a sparse one through madqp_kkt_set_hcsr, both with H == NULL here); mode 1: normal equations A Sigma^-1 A' (LP only,
  * assemble_normal_system! src/utils.jl:266-298); mode 2: the augmented system of madqp_kkt_create_augmented
  * (the CSR entries are scattered into its constraint rows).  The factorised matrix stays dense; every madqp_kkt_*
  * call works on the returned object (products with A / A' become CSR mat-vecs). */
@@ -462,6 +463,15 @@ int32_t madqp_kkt_create_sparse(madqp_ctx* ctx, int32_t mode, int64_t nx, int64_
  * condensed K = diag(hdiag) + Sigma_x + A' Theta A; normal equations A (H + Sigma)^-1 A' -- the diagonal-H
  * extension of the LP-only NormalKKTSystem (src/KKT/normalkkt.jl:45-48) that CONT-type QPs need. */
 int32_t madqp_kkt_set_hdiag(madqp_kkt* kkt, const double* hdiag);
+
+/* H as the full symmetric pattern in CSR (nx rows, column indices ascending within a row; device, int64 / double,
+ * borrowed) for a KKT object made by madqp_kkt_create_sparse with H == NULL, mode 0 (condensed) or 2 (augmented).
+ * Symmetry is the caller's promise (assembly reads the entries with col >= row, products read all of them).
+ * The assembled matrix has the bits of the one assembled from the dense form of the same H; nothing of size nx^2 is
+ * read or held for H.  h_col / h_val may be NULL when h_ptr[nx] == 0.  MADQP_ERR_ARG for an object with a dense H, with
+ * hdiag set, with a dense Jacobian, in mode 1 or in the K2.5 form, and for a NULL h_ptr; madqp_kkt_set_hdiag after this
+ * call is refused in the same way. */
+int32_t madqp_kkt_set_hcsr(madqp_kkt* kkt, const int64_t* h_ptr, const int64_t* h_col, const double* h_val);
 
 /* ----------------------------------------- callback buffers -> dense operands */
 /* MadNLP.SparseCallback hands the Jacobian / Hessian values as nnz-long buffers in the order of the model's COO

@@ -14,13 +14,13 @@ from .kkt import (HIPScaledAugmentedKKTSystem, HIPAugmentedKKTSystem, HIPCholesk
                   HIPSparseNormalKKTSystem)
 from .options import (AdaptiveRegularization, AdaptiveStep, ConservativeStep, FixedRegularization,
                       IPMOptions, MehrotraAdaptiveStep, NoRegularization)
-from .qp import DeviceCSR, DeviceQP, stream_key
+from .qp import DeviceCSR, DeviceQP, DeviceSymCSR, stream_key
 from .solver import (ERROR_IN_STEP_COMPUTATION, MAXIMUM_ITERATIONS_EXCEEDED, SOLVE_SUCCEEDED,
                      MPCSolver, SolveException, solve)
 
 __all__ = [
     "HipBackend", "State", "shard", "solve_batch", "BatchedMPCSolver", "solve", "HIPCholeskySolver", "HIPAugmentedKKTSystem", "HIPScaledAugmentedKKTSystem", "HIPCondensedKKTSystem", "HIPNormalKKTSystem", "HIPSparseAugmentedKKTSystem", "HIPSparseCondensedKKTSystem", "HIPSparseNormalKKTSystem", "MPCSolver", "DeviceQP",
-    "DeviceCSR",
+    "DeviceCSR", "DeviceSymCSR",
     "IPMOptions", "AdaptiveStep", "ConservativeStep", "MehrotraAdaptiveStep", "NoRegularization",
     "FixedRegularization", "AdaptiveRegularization", "MadQPError", "SolveException", "load_cdll",
     "EXPORTED_SYMBOLS", "LIB_PATH", "stream_key", "SOLVE_SUCCEEDED", "MAXIMUM_ITERATIONS_EXCEEDED",

@@ -181,6 +181,7 @@ _SIGNATURES = {
     "madqp_kkt_matrix": [vp, C.POINTER(vp), pi64],
     "madqp_kkt_create_sparse": [vp, i32, i64, i64, i64, pi64, vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
     "madqp_kkt_set_hdiag": [vp, vp],
+    "madqp_kkt_set_hcsr": [vp, vp, vp, vp],
     "madqp_coo_map_create": [vp, i64, vp, vp, i64, i64, i32, C.POINTER(vp)],
     "madqp_coo_map_create_cols_cyclic": [vp, i64, vp, vp, i64, i64, i64, i32, i32, C.POINTER(vp)],
     "madqp_coo_map_create_tiles_cyclic": [vp, i64, vp, vp, i64, i64, i32, i32, i32, i32, C.POINTER(vp)],

@@ -320,6 +320,10 @@ class HipBackend:
     def kkt_set_hdiag(self, h, hdiag):
         self._ck(self.lib.madqp_kkt_set_hdiag(h, ptr(hdiag)))
 
+    def kkt_set_hcsr(self, h, hcsr):
+        """``hcsr``: :class:`DeviceSymCSR` (full symmetric pattern; kept alive by the caller)."""
+        self._ck(self.lib.madqp_kkt_set_hcsr(h, ptr(hcsr.ptr), ptr(hcsr.col), ptr(hcsr.val)))
+
     def kkt_destroy(self, h):
         self.lib.madqp_kkt_destroy(h)
 

@@ -102,7 +102,7 @@ class BatchedMPCSolver:
             self.ind_lb = torch.as_tensor(ic["ind_lb"], dtype=torch.int64, device=dev)
             self.ind_ub = torch.as_tensor(ic["ind_ub"], dtype=torch.int64, device=dev)
             self.nlb, self.nub = self.ind_lb.numel(), self.ind_ub.numel()
-        if any(q.H is not None and q.H.dim() != 2 for q in self.qps) or any(not torch.is_tensor(q.A) for q in self.qps):
+        if any(q.H is not None and (not torch.is_tensor(q.H) or q.H.dim() != 2) for q in self.qps) or any(not torch.is_tensor(q.A) for q in self.qps):
             raise ValueError("the batched driver takes dense H and dense A")
         if any((q.H is None) != (q0.H is None) for q in self.qps):
             raise ValueError("all problems of a batch must be QPs or all LPs")

@@ -199,10 +199,12 @@ int32_t madqp_symv_upper(madqp_ctx* ctx, int64_t n, double alpha, const double* 
 // sparse.hip
 int32_t madqp_spmv_csr(madqp_ctx* ctx, int64_t rows, const int64_t* rowptr, const int64_t* col, const double* val,
                        double alpha, const double* x, double beta, double* y, int prof_cls);
-// rows of V as CSR (rowptr/col/val) and columns of V as CSR of V' (t_ptr/t_col/t_val)
+// rows of V as CSR (rowptr/col/val) and columns of V as CSR of V' (t_ptr/t_col/t_val); the base dense (base, ldbase),
+// a symmetric matrix with both triangles in CSR (b_ptr/b_col/b_val), or none
 int32_t madqp_sparse_gram(madqp_ctx* ctx, int64_t n, const int64_t* rowptr, const int64_t* col, const double* val,
                           const int64_t* t_ptr, const int64_t* t_col, const double* t_val, const double* w,
-                          const double* base, int64_t ldbase, const double* dvec, double* C, int64_t ldc);
+                          const double* base, int64_t ldbase, const double* dvec, const int64_t* b_ptr,
+                          const int64_t* b_col, const double* b_val, double* C, int64_t ldc);
 
 // chol.hip: the panel solve of one block of w <= 128 columns, X (rows x w) <- X L^-T (see there).  inv: how the products
 // with the 128 x 128 inverse (MADQP_CHOL_PANEL=inv) are formed -- the GEMM kernel, or panel_inv_kernel where it can serve.

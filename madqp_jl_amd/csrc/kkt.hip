@@ -50,6 +50,10 @@ struct madqp_kkt {
     const int64_t *a_ptr, *a_col, *at_ptr, *at_col;
     const double *a_val, *at_val;
     const double* hdiag;  // diagonal Hessian (nx), instead of the dense H; borrowed
+    // sparse Hessian instead of the dense H (sparse front end, condensed or augmented): the full symmetric pattern in
+    // CSR, nx rows, column indices ascending within a row; borrowed (madqp_kkt_set_hcsr)
+    const int64_t *h_ptr, *h_col;
+    const double* h_val;
     double* sg;           // Sigma + [hdiag; 0] (n), owned; the solves divide by it
     double *dn, *tn;  // normal mode: 1/Sigma (n) and an n-vector of scratch
     int64_t* d_ind_ineq;  // ns
@@ -278,6 +282,22 @@ __global__ __launch_bounds__(256) void aug_scatter_kernel(int64_t m, int64_t np,
         K[(np + r) + col[e] * ldk] = sf ? val[e] * sf[col[e]] : val[e];
 }
 
+// sparse Hessian (full symmetric pattern in CSR) behind aug_fill_kernel run with H == nullptr, which has left dx on the
+// diagonal and zeros below it: K[i, j] = h for the stored entries with i > j, K[i, i] = h + dx[i] -- the values the
+// dense-H fill writes.  16 lanes per row; only rows and columns < nx are touched.
+__global__ __launch_bounds__(256) void aug_scatter_h_kernel(int64_t nx, const int64_t* __restrict__ ptr,
+                                                            const int64_t* __restrict__ col,
+                                                            const double* __restrict__ val,
+                                                            const double* __restrict__ dx, double* __restrict__ K,
+                                                            int64_t ldk) {
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
+    if (i >= nx) return;
+    for (int64_t e = ptr[i] + (threadIdx.x & 15); e < ptr[i + 1]; e += 16) {
+        const int64_t j = col[e];
+        if (j >= 0 && j <= i) K[i + j * ldk] = (j == i) ? val[e] + dx[i] : val[e];
+    }
+}
+
 // ---- K2.5 (scaled augmented system): set_aug_diagonal_reg!(::ScaledSparseKKTSystem) (src/kernels.jl:149-165) with
 // MadNLP._set_aug_diagonal! folded in, and the sign-flipped reduce_rhs! / finish_aug_solve! / _kktmul! rows
 __global__ __launch_bounds__(TPB) void k25_fill_kernel(madqp_state s, double del_w, double del_c, double* a, double* b) {
@@ -498,8 +518,9 @@ extern "C" int32_t madqp_kkt_create(madqp_ctx* ctx, int64_t nx, int64_t m, int64
 
 // Sparse front end: A as CSR (a_*: m rows, column indices < nx, ascending within a row) and A' as CSR
 // (at_*: nx rows, indices < m), both device, int64, borrowed.  mode 0: condensed K = H + Sigma_x + A' Theta A
-// (H dense or NULL), mode 1: the reference's normal equations A Sigma^-1 A' (LP only), mode 2: the augmented
-// system [H + Sigma_x, A'; A, -D] (H dense, NULL or diagonal through madqp_kkt_set_hdiag).
+// (H dense, NULL, diagonal through madqp_kkt_set_hdiag or CSR through madqp_kkt_set_hcsr), mode 1: the reference's
+// normal equations A Sigma^-1 A' (LP only, or H diagonal), mode 2: the augmented system [H + Sigma_x, A'; A, -D] (H as in
+// mode 0).
 extern "C" int32_t madqp_kkt_create_sparse(madqp_ctx* ctx, int32_t mode, int64_t nx, int64_t m, int64_t ns,
                                            const int64_t* ind_ineq_host, const double* H, int64_t ldh,
                                            const int64_t* a_ptr, const int64_t* a_col, const double* a_val,
@@ -528,13 +549,32 @@ extern "C" int32_t madqp_kkt_create_sparse(madqp_ctx* ctx, int32_t mode, int64_t
 extern "C" int32_t madqp_kkt_set_hdiag(madqp_kkt* k, const double* hdiag) {
     if (!k) return MADQP_ERR_ARG;
     madqp_ctx* ctx = k->ctx;
-    ARG_TRY(ctx, hdiag && !k->H);
+    ARG_TRY(ctx, hdiag && !k->H && !k->h_ptr);
     if (!k->sg) {
         const size_t nb = (size_t)std::max<int64_t>(k->nx + k->ns, 1) * sizeof(double);
         hipError_t e = hipMalloc(&k->sg, nb);
         if (e != hipSuccess) return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_kkt_set_hdiag: %s", hipGetErrorString(e));
     }
     k->hdiag = hdiag;
+    return MADQP_OK;
+}
+
+// Sparse Hessian for the sparse front end: the FULL symmetric pattern of H in CSR (nx rows, column indices ascending
+// within a row, no duplicates; device, borrowed) for an object created by madqp_kkt_create_sparse without a dense H, in
+// the condensed or the augmented form.  Both triangles are stored so that H x is one row-wise mat-vec in a fixed order
+// (no atomics) and column j of the lower triangle is row j's entries with col >= j.  One 8-byte read-back of h_ptr[nx].
+extern "C" int32_t madqp_kkt_set_hcsr(madqp_kkt* k, const int64_t* h_ptr, const int64_t* h_col, const double* h_val) {
+    if (!k) return MADQP_ERR_ARG;
+    madqp_ctx* ctx = k->ctx;
+    ARG_TRY(ctx, h_ptr && !k->H && !k->hdiag);
+    ARG_TRY(ctx, k->a_ptr && k->mode != KKT_NORMAL && !k->scaled);
+    int64_t nnz = 0;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(&nnz, h_ptr + k->nx, sizeof(int64_t), hipMemcpyDeviceToHost));
+    ARG_TRY(ctx, nnz >= 0 && (nnz == 0 || (h_col && h_val)));
+    k->h_ptr = h_ptr;
+    k->h_col = h_col;
+    k->h_val = h_val;
     return MADQP_OK;
 }
 
@@ -607,7 +647,7 @@ static int32_t kkt_build_impl(madqp_kkt* k, const madqp_state* st, int64_t nrang
         if (k->a_ptr) {  // V = A (rows = constraints), weights 1/Sigma over the variables
             ARG_TRY(ctx, ranges == nullptr);
             return madqp_sparse_gram(ctx, k->m, k->a_ptr, k->a_col, k->a_val, k->at_ptr, k->at_col, k->at_val, k->dn,
-                                     nullptr, 0, k->theta, k->K, k->ldk);
+                                     nullptr, 0, k->theta, nullptr, nullptr, nullptr, k->K, k->ldk);
         }
         return madqp_syrk_assemble_ranges(ctx, k->m, k->nx, k->At, k->ldat, k->dn, nullptr, 0, k->theta,
                                           k->K, k->ldk, nranges, ranges);
@@ -628,6 +668,11 @@ static int32_t kkt_build_impl(madqp_kkt* k, const madqp_state* st, int64_t nrang
                                k->m, k->np, k->a_ptr, k->a_col, k->a_val, sf, k->K, k->ldk);
             LAUNCH_CHECK(ctx);
         }
+        if (k->h_ptr && k->nx) {
+            hipLaunchKernelGGL(aug_scatter_h_kernel, dim3((unsigned)((k->nx * 16 + 255) / 256)), dim3(256), 0, ctx->stream,
+                               k->nx, k->h_ptr, k->h_col, k->h_val, st->pr_diag, k->K, k->ldk);
+            LAUNCH_CHECK(ctx);
+        }
         return MADQP_OK;
     }
     {
@@ -639,7 +684,7 @@ static int32_t kkt_build_impl(madqp_kkt* k, const madqp_state* st, int64_t nrang
     if (k->a_ptr) {  // V = A' (rows = variables), weights Theta over the constraints
         ARG_TRY(ctx, ranges == nullptr);
         return madqp_sparse_gram(ctx, k->nx, k->at_ptr, k->at_col, k->at_val, k->a_ptr, k->a_col, k->a_val, k->theta,
-                                 k->H, k->ldh, dvec, k->K, k->ldk);
+                                 k->H, k->ldh, dvec, k->h_ptr, k->h_col, k->h_val, k->K, k->ldk);
     }
     return madqp_syrk_assemble_ranges(ctx, k->nx, k->m, k->A, k->lda, k->theta, k->H, k->ldh, dvec,
                                       k->K, k->ldk, nranges, ranges);
@@ -937,6 +982,8 @@ static int32_t kkt_mul_impl(madqp_kkt* k, const madqp_state* st, double* w, cons
         ProfScope ps(ctx, MADQP_PROF_VEC);
         KLAUNCH(hdiag_axpy_kernel, nx, nx, alpha, k->hdiag, v, w);
     }
+    if (k->h_ptr && nx)  // both triangles are stored: one row-wise mat-vec, fixed order
+        if ((r = madqp_spmv_csr(ctx, nx, k->h_ptr, k->h_col, k->h_val, alpha, v, 1.0, w, MADQP_PROF_GEMV))) return r;
     if (kkt_fusable(k)) {  // the five per-variable passes that follow, in one (resid_tail_kernel)
         if (!have_Av && (r = apply_A(k, 1.0, v, 0.0, k->u))) return r;
         if ((r = ensure_pos(k, st))) return r;
@@ -979,12 +1026,14 @@ int32_t madqp_q_kkt_eval(madqp_kkt* k, const madqp_state* st, const double* q, c
         ProfScope ps(ctx, MADQP_PROF_VEC);
         KLAUNCH(hdiag_mul_kernel, nx, nx, k->hdiag, st->x, st->f);
     }
+    if (k->h_ptr && nx)
+        if ((r = madqp_spmv_csr(ctx, nx, k->h_ptr, k->h_col, k->h_val, 1.0, st->x, 0.0, st->f, MADQP_PROF_GEMV))) return r;
     if (n) {
         const int nb = grid_for(n);
         {
             ProfScope ps(ctx, MADQP_PROF_VEC);
             hipLaunchKernelGGL(eval_grad_kernel, dim3(nb), dim3(TPB), 0, ctx->stream, n, nx,
-                               ((k->H || k->hdiag) && nx) ? 1 : 0, q, st->x, st->f, ctx->d_part);
+                               ((k->H || k->hdiag || k->h_ptr) && nx) ? 1 : 0, q, st->x, st->f, ctx->d_part);
             LAUNCH_CHECK(ctx);
             hipLaunchKernelGGL(sum2_final_kernel, dim3(1), dim3(TPB), 0, ctx->stream, ctx->d_part, nb,
                                ctx->d_res + slot0);

@@ -7,7 +7,8 @@
 //   * the weighted Gram matrix  C = base + diag(dvec) + V diag(w) V'  (lower triangle, dense, column
 //     major) of the sparse rows of V -- assemble_normal_system! (src/utils.jl:266-298) with V = A,
 //     w = 1/Sigma for the normal equations, and V = A', w = Theta for the condensed form.  One
-//     workgroup per column of C (see sparse_gram_kernel): deterministic, no atomics.
+//     workgroup per column of C (see sparse_gram_kernel): deterministic, no atomics.  The base may itself be
+//     sparse (a symmetric H, both triangles in CSR: madqp_kkt_set_hcsr), so that nothing of size n^2 is read.
 #include <algorithm>
 
 #include "common.h"
@@ -48,14 +49,30 @@ __global__ __launch_bounds__(256) void sparse_gram_kernel(int64_t n, const int64
                                                           const double* __restrict__ w,
                                                           const double* __restrict__ base, int64_t ldbase,
                                                           const double* __restrict__ dvec,
+                                                          const int64_t* __restrict__ b_ptr,
+                                                          const int64_t* __restrict__ b_col,
+                                                          const double* __restrict__ b_val,
                                                           double* __restrict__ C, int64_t ldc) {
     const int64_t j = blockIdx.x;
     double* Cj = C + j * ldc;
-    const double* Bj = base ? base + j * ldbase : nullptr;
-    for (int64_t i = j + threadIdx.x; i < n; i += 256) {
-        double v = Bj ? Bj[i] : 0.0;
-        if (dvec && i == j) v += dvec[j];
-        Cj[i] = v;
+    if (b_ptr) {
+        // sparse symmetric base (row j = column j; column indices ascending, no duplicates): zeros over the run, then the
+        // stored entries with i = col >= j are ASSIGNED -- h (+ dvec[j] on the diagonal), the operations of the dense
+        // base below on the same operands, so the bits are those of the dense form of the same matrix
+        for (int64_t i = j + threadIdx.x; i < n; i += 256) Cj[i] = (dvec && i == j) ? dvec[j] : 0.0;
+        __syncthreads();
+        const int64_t e = b_ptr[j + 1];
+        for (int64_t p = b_ptr[j] + threadIdx.x; p < e; p += 256) {
+            const int64_t i = b_col[p];
+            if (i >= j && i < n) Cj[i] = (dvec && i == j) ? b_val[p] + dvec[j] : b_val[p];
+        }
+    } else {
+        const double* Bj = base ? base + j * ldbase : nullptr;
+        for (int64_t i = j + threadIdx.x; i < n; i += 256) {
+            double v = Bj ? Bj[i] : 0.0;
+            if (dvec && i == j) v += dvec[j];
+            Cj[i] = v;
+        }
     }
     __syncthreads();
     for (int64_t p = rowptr[j]; p < rowptr[j + 1]; ++p) {
@@ -85,12 +102,13 @@ int32_t madqp_spmv_csr(madqp_ctx* ctx, int64_t rows, const int64_t* rowptr, cons
 
 int32_t madqp_sparse_gram(madqp_ctx* ctx, int64_t n, const int64_t* rowptr, const int64_t* col, const double* val,
                           const int64_t* t_ptr, const int64_t* t_col, const double* t_val, const double* w,
-                          const double* base, int64_t ldbase, const double* dvec, double* C, int64_t ldc) {
+                          const double* base, int64_t ldbase, const double* dvec, const int64_t* b_ptr,
+                          const int64_t* b_col, const double* b_val, double* C, int64_t ldc) {
     if (n == 0) return MADQP_OK;
-    ARG_TRY(ctx, rowptr && t_ptr && w && C && ldc >= n && (!base || ldbase >= n));
+    ARG_TRY(ctx, rowptr && t_ptr && w && C && ldc >= n && (!base || ldbase >= n) && !(base && b_ptr));
     ProfScope ps(ctx, MADQP_PROF_SYRK);
     hipLaunchKernelGGL(sparse_gram_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, n, rowptr, col, val, t_ptr,
-                       t_col, t_val, w, base, ldbase, dvec, C, ldc);
+                       t_col, t_val, w, base, ldbase, dvec, b_ptr, b_col, b_val, C, ldc);
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }

@@ -11,6 +11,7 @@ test/runtests.jl:151).  Method names follow the reference's generic functions
 from __future__ import annotations
 
 from .backend import State
+from .qp import DeviceSymCSR
 
 
 class HIPCholeskySolver:
@@ -240,7 +241,8 @@ class _SparseMixin:
     reference: src/utils.jl:148-298, src/KKT/normalkkt.jl:51-101)."""
 
     def _init_sparse(self, backend, st, nx, ind_ineq, H, csr, mode):
-        """``H``: None, a dense (nx, nx) tensor (condensed mode) or a 1-D tensor = diagonal of H (either mode)."""
+        """``H``: None, a dense (nx, nx) tensor (condensed or augmented mode), a 1-D tensor = diagonal of H (any mode)
+        or a :class:`DeviceSymCSR` (condensed or augmented mode; kept alive here, the library borrows its arrays)."""
         self.be, self.st = backend, st
         self.nx, self.m = int(nx), st.m
         self.ind_ineq = [int(i) for i in ind_ineq]
@@ -248,9 +250,13 @@ class _SparseMixin:
         assert st.n == self.nx + self.ns and (csr.m, csr.n) == (self.m, self.nx)
         self.H, self.A, self.csr = H, None, csr
         self._t_val = csr.t_val  # values of A' in CSR order, borrowed by the library
-        diag = H is not None and H.dim() == 1
-        self._h = backend.kkt_create_sparse(mode, self.nx, self.m, self.ind_ineq, None if diag else H,
+        hcsr = isinstance(H, DeviceSymCSR)
+        diag = H is not None and not hcsr and H.dim() == 1
+        self._h = backend.kkt_create_sparse(mode, self.nx, self.m, self.ind_ineq, None if diag or hcsr else H,
                                             max(self.nx, 1), csr, self._t_val)
+        if hcsr:
+            assert H.n == self.nx
+            backend.kkt_set_hcsr(self._h, H)
         if diag:
             assert H.is_contiguous() and H.numel() == self.nx
             backend.kkt_set_hdiag(self._h, H)
@@ -260,7 +266,7 @@ class _SparseMixin:
 
 class HIPSparseCondensedKKTSystem(_SparseMixin, HIPCondensedKKTSystem):
     def __init__(self, backend, st, nx, ind_ineq, H, csr):
-        if H is not None and H.dim() == 2:
+        if H is not None and not isinstance(H, DeviceSymCSR) and H.dim() == 2:
             assert H.is_contiguous() and H.shape == (nx, nx)
         self._init_sparse(backend, st, nx, ind_ineq, H, csr, 0)
 
@@ -270,7 +276,7 @@ class HIPSparseNormalKKTSystem(_SparseMixin, HIPNormalKKTSystem):
     (1-D tensor; SURVEY.md 8a-note -- what CONT-type QPs need)."""
 
     def __init__(self, backend, st, nx, ind_ineq, H, csr):
-        if H is not None and H.dim() != 1:
+        if H is not None and (isinstance(H, DeviceSymCSR) or H.dim() != 1):
             raise ValueError("The KKT system NormalKKTSystem supports only linear programs "
                              "(or a diagonal Hessian given as a vector).")  # normalkkt.jl:45-48
         self._init_sparse(backend, st, nx, ind_ineq, H, csr, 1)
@@ -278,10 +284,11 @@ class HIPSparseNormalKKTSystem(_SparseMixin, HIPNormalKKTSystem):
 
 class HIPSparseAugmentedKKTSystem(_SparseMixin, HIPAugmentedKKTSystem):
     """Augmented system with a sparse Jacobian (``DeviceCSR``) scattered into the dense quasi-definite matrix:
-    the exact treatment of equality rows for a QP whose Hessian is dense (or diagonal, 1-D tensor)."""
+    the exact treatment of equality rows for a QP whose Hessian is dense, diagonal (1-D tensor) or sparse
+    (:class:`DeviceSymCSR`)."""
 
     def __init__(self, backend, st, nx, ind_ineq, H, csr):
-        if H is not None and H.dim() == 2:
+        if H is not None and not isinstance(H, DeviceSymCSR) and H.dim() == 2:
             assert H.is_contiguous() and H.shape == (nx, nx)
         self._init_sparse(backend, st, nx, ind_ineq, H, csr, 2)
         self.linear_solver = HIPQuasiDefiniteSolver(backend, self._h, self.nx, self.m)

@@ -547,11 +547,13 @@ def standard_form(qp: HostQP) -> HostQP:
 
 
 # ------------------------------------------------------------------------------------------- hand-over
-def to_device(qp: HostQP, backend, sparse: bool = True):
-    """A :class:`DeviceQP` for the HIP path: the Jacobian as ``DeviceCSR`` (or dense), H dense or None."""
+def to_device(qp: HostQP, backend, sparse: bool = True, sparse_hessian: bool = False):
+    """A :class:`DeviceQP` for the HIP path: the Jacobian as ``DeviceCSR`` (or dense), H dense, a vector (diagonal H,
+    sparse front end) or None.  ``sparse_hessian`` (with ``sparse``): a non-diagonal H stays sparse as a
+    ``DeviceSymCSR`` built from its lower triangle -- nothing of size nvar^2 is allocated for it."""
     import torch
 
-    from .qp import DeviceCSR, DeviceQP
+    from .qp import DeviceCSR, DeviceQP, DeviceSymCSR
 
     dev = backend.device
     f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64), device=dev)
@@ -560,6 +562,9 @@ def to_device(qp: HostQP, backend, sparse: bool = True):
         H = None
     elif sparse and np.all(Hc.row == Hc.col):
         H = f(qp.H.diagonal())  # diagonal Hessian: kept as a vector (madqp_kkt_set_hdiag)
+    elif sparse and sparse_hessian:
+        Hl = sp.tril(qp.H).tocoo()
+        H = DeviceSymCSR(dev, qp.nvar, Hl.row, Hl.col, Hl.data)
     else:
         H = f(qp.H.toarray())
     Ac = qp.A.tocoo()
@@ -574,7 +579,7 @@ def benchmark_row(qp: HostQP, result: dict, total_time: float, linear_solver_tim
 
 
 # ------------------------------------------------------------------------ a CONT-type instance generator
-def boundary_control_qp(N: int, alpha: float = 0.01, ymax: float = 0.8) -> HostQP:
+def boundary_control_qp(N: int, alpha: float = 0.01, ymax: float = 0.8, smooth: float = 0.0) -> HostQP:
     """Elliptic boundary-control QP on an N x N grid, the problem class of the Maros-Meszaros CONT-xxx
     instances (BASELINE configs[2] names CONT-300; its data file is not available offline, so this is a
     stand-in of the same shape, not that instance):
@@ -584,7 +589,11 @@ def boundary_control_qp(N: int, alpha: float = 0.01, ymax: float = 0.8) -> HostQ
              0 <= y <= ymax,  0 <= u <= 1                              the grid is a boundary control u_k)
 
     n = N^2 + 4N variables [y; u_left; u_right; u_bottom; u_top], m = N^2 equality rows with <= 5 entries,
-    diagonal Hessian.  N = 300: n = 91 200, m = 90 000 (CONT-300: 90 597 x 90 298)."""
+    diagonal Hessian.  N = 300: n = 91 200, m = 90 000 (CONT-300: 90 597 x 90 298).
+
+    ``smooth`` = beta > 0 adds the smoothing term ``beta h/2 sum_k (u_(k+1) - u_k)^2`` along each of the four sides,
+    i.e. ``beta h D'D`` on every control block with D the (N-1) x N first-difference matrix: a NON-diagonal
+    (tridiagonal on the controls) Hessian of the same problem class."""
     h = 1.0 / (N + 1)
     idx = lambda i, j: i * N + j
     ul, ur, ub, ut = N * N, N * N + N, N * N + 2 * N, N * N + 3 * N
@@ -606,5 +615,9 @@ def boundary_control_qp(N: int, alpha: float = 0.01, ymax: float = 0.8) -> HostQ
     c = np.concatenate([-h * h * yd, np.zeros(4 * N)])
     lvar = np.zeros(n)
     uvar = np.concatenate([np.full(N * N, ymax), np.ones(4 * N)])
-    return HostQP(0.5 * h * h * float(yd @ yd), c, sp.diags(hd).tocsr(), sp.csr_matrix((vals, (rows, cols)), shape=(m, n)),
+    Hs = sp.diags(hd).tocsr()
+    if smooth:
+        D = sp.diags([-np.ones(N - 1), np.ones(N - 1)], [0, 1], shape=(N - 1, N))
+        Hs = sp.csr_matrix(Hs + smooth * h * sp.block_diag([sp.csr_matrix((N * N, N * N))] + [D.T @ D] * 4))
+    return HostQP(0.5 * h * h * float(yd @ yd), c, Hs, sp.csr_matrix((vals, (rows, cols)), shape=(m, n)),
                   lvar, uvar, np.zeros(m), np.zeros(m), name=f"boundary-control-{N}")

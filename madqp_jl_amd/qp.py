@@ -4,6 +4,8 @@
 
 ``H`` is a full symmetric (nx, nx) tensor (or None for an LP) and ``A`` an
 (m, nx) row-major tensor: the layouts the MFMA kernels consume directly.
+The sparse front end takes ``A`` as a :class:`DeviceCSR` and ``H`` dense, as a
+1-D tensor (its diagonal) or as a :class:`DeviceSymCSR`.
 The synthetic family is the one of BASELINE.md section 3; entries are produced
 in place on the device by ``madqp_gen_*`` and are bit-identical to the CPU
 generator the tests use.
@@ -81,9 +83,78 @@ class DeviceCSR:
         return A
 
 
+class DeviceSymCSR:
+    """A sparse symmetric Hessian on the device, built once on the host from the entries of its LOWER triangle
+    (``rows[k] >= cols[k]``: how MadNLP and QuadraticModels hold a Hessian; explicit zeros are kept).  Stored is the FULL
+    symmetric pattern in CSR (``ptr, col, val``; n rows, column indices ascending within a row; int64 / float64) plus
+    ``row`` (row index of every stored entry): with both triangles one row-wise mat-vec gives ``H x`` in a fixed order
+    without atomics, and column j of the lower triangle is row j's entries with ``col >= j`` (``madqp_kkt_set_hcsr``)."""
+
+    def __init__(self, device, n, rows, cols, vals):
+        rows, cols = np.asarray(rows, dtype=np.int64).ravel(), np.asarray(cols, dtype=np.int64).ravel()
+        vals = np.asarray(vals, dtype=np.float64).ravel()
+        n = int(n)
+        if not (len(rows) == len(cols) == len(vals)):
+            raise ValueError("rows, cols and vals of the sparse Hessian differ in length")
+        if len(rows) and (rows.min() < 0 or cols.min() < 0 or rows.max() >= n):
+            raise ValueError("index out of range in the sparse Hessian")
+        if np.any(cols > rows):
+            raise ValueError("entry above the diagonal in the sparse Hessian (pass the lower triangle)")
+        order = np.lexsort((cols, rows))
+        rows, cols, vals = rows[order], cols[order], vals[order]
+        if len(rows) > 1 and np.any((rows[1:] == rows[:-1]) & (cols[1:] == cols[:-1])):
+            raise ValueError("duplicate entries in the sparse Hessian")
+        off = rows != cols  # mirrored into the upper triangle
+        fr, fc = np.concatenate([rows, cols[off]]), np.concatenate([cols, rows[off]])
+        fv = np.concatenate([vals, vals[off]])
+        order = np.lexsort((fc, fr))  # by row, then column
+        fr, fc, fv = fr[order], fc[order], fv[order]
+        dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=device)
+        self.n, self.nnz, self.nnz_lower = n, len(fv), len(vals)  # nnz_lower: the count QuadraticModels reports
+        self.ptr = dev(np.concatenate([[0], np.cumsum(np.bincount(fr, minlength=n))]), torch.int64)
+        self.col, self.val, self.row = dev(fc, torch.int64), dev(fv, torch.float64), dev(fr, torch.int64)
+
+    @classmethod
+    def from_dense(cls, device, H):
+        """From a dense symmetric matrix: the non-zeros of ``tril(H)``."""
+        L = np.tril(np.asarray(H.detach().cpu().numpy() if torch.is_tensor(H) else H, dtype=np.float64))
+        r, c = np.nonzero(L)
+        return cls(device, L.shape[0], r, c, L[r, c])
+
+    def to_dense(self):
+        H = torch.zeros((self.n, self.n), dtype=torch.float64, device=self.val.device)
+        H[self.row, self.col] = self.val
+        return H
+
+    def scaled(self, s):
+        """A copy that shares the pattern, with every value multiplied by the scalar ``s`` (one IEEE product per entry:
+        what ``s * H`` does to a dense H)."""
+        out = object.__new__(DeviceSymCSR)
+        out.__dict__.update(self.__dict__)
+        out.val = (self.val * float(s)).contiguous()
+        return out
+
+    def matvec(self, x):
+        """``H x`` for the one-off host-side uses (scaling, fixed variables, post-solve): every row summed left to right,
+        one row after the other -- a fixed order, no atomics."""
+        if self.nnz == 0:
+            return torch.zeros(self.n, dtype=torch.float64, device=self.val.device)
+        return torch.segment_reduce(self.val * x[self.col], "sum", offsets=self.ptr, initial=0.0)
+
+    def submatrix(self, free):
+        """``H[free][:, free]`` as a new container; ``free``: ascending index tensor (or array)."""
+        free = np.asarray(free.cpu().numpy() if torch.is_tensor(free) else free, dtype=np.int64)
+        new = np.full(self.n, -1, dtype=np.int64)
+        new[free] = np.arange(len(free))
+        r, c, v = (t.cpu().numpy() for t in (self.row, self.col, self.val))
+        keep = (c <= r) & (new[r] >= 0) & (new[c] >= 0)  # the lower triangle, both indices kept
+        return DeviceSymCSR(self.val.device, len(free), new[r[keep]], new[c[keep]], v[keep])
+
+
 class DeviceQP:
     def __init__(self, H, q, A, lvar, uvar, lcon, ucon, x0, c0=0.0, y0=None, name="qp"):
-        """``A``: (m, nx) row-major tensor, or a :class:`DeviceCSR` (sparse front end)."""
+        """``A``: (m, nx) row-major tensor, or a :class:`DeviceCSR` (sparse front end); ``H``: (nx, nx) tensor, None,
+        a 1-D tensor (diagonal) or a :class:`DeviceSymCSR`."""
         self.H, self.q, self.A = H, q, A
         self.lvar, self.uvar, self.lcon, self.ucon, self.x0 = lvar, uvar, lcon, ucon, x0
         self.c0 = float(c0)
@@ -115,7 +186,14 @@ class DeviceQP:
         c0 = self.c0 + float(self.q[fixed] @ xf)
         q = self.q[free].clone()
         H = self.H
-        if H is not None and H.dim() == 1:
+        if isinstance(H, DeviceSymCSR):
+            xfull = torch.zeros(self.nvar, dtype=torch.float64, device=self.q.device)
+            xfull[fixed] = xf
+            Hx = H.matvec(xfull)  # H[:, fixed] xfix
+            c0 += 0.5 * float(Hx[fixed] @ xf)
+            q += Hx[free]
+            H = H.submatrix(free)
+        elif H is not None and H.dim() == 1:
             c0 += 0.5 * float((H[fixed] * xf) @ xf)
             H = H[free].contiguous()
         elif H is not None:

@@ -22,7 +22,7 @@ from .kkt import (HIPAugmentedKKTSystem, HIPCondensedKKTSystem, HIPNormalKKTSyst
                   HIPSparseAugmentedKKTSystem, HIPSparseCondensedKKTSystem, HIPSparseNormalKKTSystem)
 from .options import (AdaptiveRegularization, AdaptiveStep, ConservativeStep, FixedRegularization,
                       IPMOptions, MehrotraAdaptiveStep, NoRegularization)
-from .qp import DeviceCSR, DeviceQP
+from .qp import DeviceCSR, DeviceQP, DeviceSymCSR
 
 
 def _fdiv(a: float, b: float) -> float:
@@ -109,6 +109,15 @@ class MPCSolver:
             "relax_bound" if self.opt.kkt_system in ("condensed", "augmented", "scaled_augmented") else "make_parameter")
         if fvt not in ("relax_bound", "make_parameter", "error"):
             raise ValueError(f"unknown fixed_variable_treatment {fvt!r}")
+        if isinstance(qp.H, DeviceSymCSR):  # sparse Hessian: sparse front end, condensed or augmented form, one GPU
+            if self.opt.kkt_system == "normal":
+                raise ValueError("The KKT system NormalKKTSystem supports only linear programs.")
+            if self.opt.kkt_system == "scaled_augmented":
+                raise ValueError("the scaled augmented (K2.5) system takes a dense Jacobian and a dense (or no) Hessian")
+            if hasattr(qp, "grid"):
+                raise ValueError("a sparse Hessian (DeviceSymCSR) is assembled on one GPU; a DistributedQP takes a dense H")
+            if not isinstance(qp.A, DeviceCSR):
+                raise ValueError("a sparse Hessian (DeviceSymCSR) needs the sparse front end (A as DeviceCSR)")
         self.full_qp, self._fixed = qp, None
         if fvt == "make_parameter":
             self._fixed = qp.eliminate_fixed()
@@ -126,7 +135,7 @@ class MPCSolver:
         reg = self.opt.regularization
         if self.opt.kkt_system not in ("condensed", "normal", "augmented", "scaled_augmented"):
             raise ValueError(f"unknown kkt_system {self.opt.kkt_system!r}")
-        diag_h = qp.H is not None and qp.H.dim() == 1  # H = diag(vector): sparse front end only
+        diag_h = torch.is_tensor(qp.H) and qp.H.dim() == 1  # H = diag(vector): sparse front end only
         if self.opt.kkt_system == "scaled_augmented" and (diag_h or isinstance(qp.A, DeviceCSR)):
             raise ValueError("the scaled augmented (K2.5) system takes a dense Jacobian and a dense (or no) Hessian")
         if diag_h and not isinstance(qp.A, DeviceCSR) and self.opt.kkt_system != "augmented":
@@ -408,6 +417,8 @@ class MPCSolver:
             if qp.H is not None and nx:
                 if spread:
                     g.add_(qp.hess_times(st.x[:nx]))
+                elif isinstance(qp.H, DeviceSymCSR):
+                    g.add_(qp.H.matvec(st.x[:nx]))
                 elif qp.H.dim() == 1:
                     g.add_(qp.H * st.x[:nx])
                 else:
@@ -429,7 +440,10 @@ class MPCSolver:
                 else:
                     self.A = qp.A.scaled(con_scale) if sparse else (con_scale[:, None] * qp.A).contiguous()
             if self.obj_scale != 1.0:
-                self.H = None if qp.H is None else (self.obj_scale * qp.H).contiguous()
+                if isinstance(qp.H, DeviceSymCSR):
+                    self.H = qp.H.scaled(self.obj_scale)
+                else:
+                    self.H = None if qp.H is None else (self.obj_scale * qp.H).contiguous()
                 self.q = self.obj_scale * qp.q
         if self.kkt is not None:
             self._fact_closed += self.kkt.n_factorizations
@@ -584,7 +598,9 @@ class MPCSolver:
             xs[free], xs[fixed], zls[free], zus[free] = x, h(xf), zl, zu
             xd, yd = torch.as_tensor(xs, device=st.y.device), torch.as_tensor(y, device=st.y.device)
             g = fq.q.clone()
-            if fq.H is not None:
+            if isinstance(fq.H, DeviceSymCSR):
+                g += fq.H.matvec(xd)
+            elif fq.H is not None:
                 g += fq.H * xd if fq.H.dim() == 1 else fq.H @ xd
             if isinstance(fq.A, DeviceCSR):
                 g.index_add_(0, fq.A.col, fq.A.val * yd[fq.A.row])

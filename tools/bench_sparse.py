@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Sparse-A front end on a synthetic sparse LP (normal equations) or QP (condensed): time per IPM iteration
-and the per-class split.  python tools/bench_sparse.py --nx 60000 --ncon 20000 --per-row 8 --kkt normal"""
+and the per-class split.  python tools/bench_sparse.py --nx 60000 --ncon 20000 --per-row 8 --kkt normal
+
+A non-diagonal Hessian, dense against sparse (``DeviceSymCSR``), on the CONT-type problem with a smoothing term on the
+controls -- the same command with and without ``--sparse-hessian``:
+
+    python tools/bench_sparse.py --cont 150 --smooth 1.0 --kkt condensed --warmup 2 --steps 5 [--sparse-hessian]"""
 import argparse
 import json
 import os
@@ -13,21 +18,76 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def bench_hessian_forms(a, be):
+    """Per-iteration cost of one form of a non-diagonal H: iterations/s from a window without the device timers, the
+    per-class split (assembly = syrk, the mat-vecs of mul! and eval = gemv) from a second window with them.  Every window
+    is the first ``steps`` iterations of a solve started afresh, after a warm-up window of the same kind."""
+    import torch
+
+    import madqp_jl_amd as M
+    from madqp_jl_amd import preprocess as P
+
+    h = P.boundary_control_qp(a.cont, smooth=a.smooth)
+    qp = P.to_device(h, be, sparse_hessian=a.sparse_hessian)
+    if isinstance(qp.H, M.DeviceSymCSR):
+        form, h_bytes = "csr", sum(t.numel() * t.element_size() for t in (qp.H.ptr, qp.H.col, qp.H.val, qp.H.row))
+    else:
+        form, h_bytes = "dense", qp.H.numel() * qp.H.element_size()
+    kw = {} if a.kkt == "augmented" else dict(regularization=M.FixedRegularization(1e-8, 0.0 if a.kkt == "normal" else -1e-8))
+    s = M.MPCSolver(qp, be, kkt_system=a.kkt, driver="native", max_iter=300, **kw)
+
+    def window(steps):  # the first iterations of a fresh solve (the problem converges in a handful): the same ones every time
+        s.initialize()
+        torch.cuda.synchronize()
+        t0, done = time.perf_counter(), 0
+        for _ in range(steps):
+            if s.iteration_head() is not None:
+                break
+            s.iteration_body()
+            done += 1
+        torch.cuda.synchronize()
+        return done, time.perf_counter() - t0
+
+    window(a.warmup)
+    done, dt = window(a.steps)
+    be.prof_enable(M._lib.PROF_CLASSES)
+    be.prof_reset()
+    pdone, _ = window(a.steps)
+    prof = be.prof_get()
+    be.prof_enable(())
+    split = {c: round(v[0] / max(pdone, 1), 3) for c, v in prof.items() if v[1]}
+    print(json.dumps({"workload": f"boundary-control QP N={a.cont} smooth={a.smooth}: nx={h.nvar} m={h.ncon} nnzj={h.nnzj} "
+                                  f"nnzh={h.nnzh}, {a.kkt}", "hessian": form, "hessian_bytes": h_bytes,
+                      "iterations_timed": done, "ms_per_iteration": dt / max(done, 1) * 1e3,
+                      "iterations_per_s": done / dt if done else None, "iterations_profiled": pdone,
+                      "split_ms_per_iteration": split, "assembly_ms": split.get("syrk"), "matvec_ms": split.get("gemv"),
+                      "last": s.trace[-1] if s.trace else None}))
+    s.close()
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--nx", type=int, default=60000)
     p.add_argument("--ncon", type=int, default=20000)
     p.add_argument("--per-row", type=int, default=8)
-    p.add_argument("--kkt", choices=("normal", "condensed"), default="normal")
+    p.add_argument("--kkt", choices=("normal", "condensed", "augmented"), default="normal")
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--cont", type=int, default=0, help="N > 0: the CONT-type boundary-control QP on an N x N grid "
                    "(preprocess.boundary_control_qp; N = 300 has the shape of Maros-Meszaros CONT-300), solved to the end")
+    p.add_argument("--smooth", type=float, default=0.0, help="with --cont: beta > 0 adds beta h D'D on the controls "
+                   "(boundary_control_qp(smooth=beta)): a non-diagonal Hessian, which needs --kkt condensed or augmented; "
+                   "the run is then timed per iteration (--warmup iterations, then --steps without and --steps with the "
+                   "library's device timers)")
+    p.add_argument("--sparse-hessian", action="store_true", help="keep a non-diagonal H sparse (DeviceSymCSR)")
+    p.add_argument("--warmup", type=int, default=2)
     a = p.parse_args()
     import torch
 
     import madqp_jl_amd as M
 
     be = M.HipBackend(0)
+    if a.cont and a.smooth:
+        return bench_hessian_forms(a, be)
     if a.cont:
         from madqp_jl_amd import preprocess as P
 

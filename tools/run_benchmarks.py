@@ -9,7 +9,9 @@ FixedRegularization(1e-8, -1e-8), mu_min 1e-12).  The KKT system: the scripts' N
 diagonal-Hessian QPs, the condensed system otherwise (``--kkt-system`` overrides).  Writes the table the scripts write
 (nvar ncon nnzj nnzh status iter objective total_time linear_solver_time) next to the instance names.
 
-    python tools/run_benchmarks.py DIR [--reformulate] [--out results.txt]
+    python tools/run_benchmarks.py DIR [--reformulate] [--sparse-hessian] [--out results.txt]
+
+``--sparse-hessian`` keeps a non-diagonal Q sparse on the device (``DeviceSymCSR``) instead of densifying it.
 """
 import argparse
 import os
@@ -23,7 +25,7 @@ sys.path.insert(0, ROOT)
 EXT = (".mps", ".qps", ".sif", ".mps.gz", ".qps.gz", ".sif.gz")
 
 
-def run(directory, reformulate=False, kkt_system=None, out=None, backend=None, verbose=True):
+def run(directory, reformulate=False, kkt_system=None, out=None, backend=None, verbose=True, sparse_hessian=False):
     import madqp_jl_amd as M
     from madqp_jl_amd import preprocess as P
 
@@ -50,7 +52,7 @@ def run(directory, reformulate=False, kkt_system=None, out=None, backend=None, v
             be.prof_enable(lin_classes)
             be.prof_reset()
             t0 = time.perf_counter()
-            s = M.MPCSolver(P.to_device(model, be), be, max_iter=300, max_ncorr=3, scaling=True,
+            s = M.MPCSolver(P.to_device(model, be, sparse_hessian=sparse_hessian), be, max_iter=300, max_ncorr=3, scaling=True,
                             step_rule=M.AdaptiveStep(0.995), regularization=M.FixedRegularization(1e-8, -1e-8),
                             kkt_system=ksys, rethrow_error=True, mu_min=1e-12, driver="native")  # :33-45
             r = s.solve()
@@ -79,8 +81,9 @@ def main():
     p.add_argument("--reformulate", action="store_true", help="standard_form_qp before the solve")
     p.add_argument("--kkt-system", choices=("condensed", "normal", "augmented"), default=None)
     p.add_argument("--out", default=None)
+    p.add_argument("--sparse-hessian", action="store_true", help="keep a non-diagonal Hessian sparse (DeviceSymCSR)")
     a = p.parse_args()
-    run(a.directory, a.reformulate, a.kkt_system, a.out)
+    run(a.directory, a.reformulate, a.kkt_system, a.out, sparse_hessian=a.sparse_hessian)
 
 
 if __name__ == "__main__":
