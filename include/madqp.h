@@ -502,6 +502,50 @@ int32_t madqp_coo_map_create_tiles_cyclic(madqp_ctx* ctx, int64_t nnz, const int
 int32_t madqp_coo_map_apply(madqp_coo_map* map, const double* vals, double* dst, int64_t ld);
 int32_t madqp_coo_map_destroy(madqp_coo_map* map);
 
+/* ----------------------------------------- callback buffers -> CSR operands (sparse front end) */
+/* The same step for the SPARSE operands of madqp_kkt_create_sparse / madqp_kkt_set_hcsr: what the reference does with
+ * coo_to_csr (src/utils.jl:148-197: pattern -> CSR structure plus a map, once, at src/KKT/normalkkt.jl:84-91) and with the
+ * map in compress_jacobian! (src/KKT/normalkkt.jl:149-158: callback values -> nzval, after every evaluation).  A
+ * madqp_csr_map is built once from the pattern (I_host, J_host: 1-based int32 COO, duplicates allowed, as
+ * madqp_coo_map_create takes them) and holds, on the device, the CSR structure -- 0-based int64, column indices strictly
+ * ascending within a row, ONE stored entry per distinct destination -- and the sources of every stored entry.
+ *   MADQP_CSR_ROWS  CSR of the nrows x ncols matrix (a_* of madqp_kkt_create_sparse);
+ *   MADQP_CSR_COLS  CSR of its transpose, ncols rows (at_*);
+ *   MADQP_CSR_SYM   nrows == ncols; the entries may lie in either triangle (MadNLP's Hessians: the lower one); the
+ *                   result is the FULL symmetric pattern madqp_kkt_set_hcsr wants: every pattern entry k with
+ *                   {I_k, J_k} = {i, j} feeds both (i, j) and (j, i), in the same order, so the two stored values are
+ *                   bitwise equal -- the symmetry madqp_kkt_set_hcsr makes its caller promise.
+ * Value of a stored entry: the sum of its sources in ascending COO position, s = 0.0; s += v, by ONE lane (no atomics,
+ * reproducible) -- the sum madqp_coo_map_apply forms, so the CSR expands to the bits of the dense operand that map writes
+ * for the same pattern and values. */
+typedef struct madqp_csr_map madqp_csr_map;
+enum { MADQP_CSR_ROWS = 0, MADQP_CSR_COLS = 1, MADQP_CSR_SYM = 2 };
+/* The plan madqp_csr_map_create uploads -- the one function it builds from, not a restatement of it -- on the host: no
+ * context, no device.  sizes_host[3] = (rows of the CSR, stored entries, sources: nnz, or nnz + the off-diagonal entries
+ * for SYM); ptr_host: rows + 1; col_host: stored; seg_host: stored + 1 offsets into src_host; src_host: the 0-based COO
+ * positions of the sources, grouped by stored entry, ascending within one.  With the four array pointers NULL only
+ * sizes_host is filled (call twice: sizes, then arrays).  MADQP_ERR_ARG: an entry outside the matrix, an unknown kind, SYM
+ * on a rectangle, negative extents, a NULL pattern with nnz > 0, a NULL sizes_host, some but not all of the four arrays. */
+int32_t madqp_csr_map_plan_host(int64_t nnz, const int32_t* I_host, const int32_t* J_host, int64_t nrows, int64_t ncols,
+                                int32_t kind, int64_t* sizes_host, int64_t* ptr_host, int64_t* col_host,
+                                int64_t* seg_host, int64_t* src_host);
+/* coo_to_csr (src/utils.jl:148-197): the plan above, uploaded.  Refusals as madqp_csr_map_plan_host. */
+int32_t madqp_csr_map_create(madqp_ctx* ctx, int64_t nnz, const int32_t* I_host, const int32_t* J_host, int64_t nrows,
+                             int64_t ncols, int32_t kind, madqp_csr_map** out);
+/* The structure, for madqp_kkt_create_sparse (a_ptr / a_col, at_ptr / at_col) and madqp_kkt_set_hcsr (h_ptr / h_col):
+ * *ptr (rows + 1) and *col (stored) are DEVICE arrays OWNED BY THE MAP; any of the four outputs may be NULL.
+ * LIFETIME: a KKT object that was given these arrays borrows from the map.  After madqp_csr_map_destroy no call may be made
+ * on that KKT object except madqp_kkt_destroy (which reads no borrowed array): destroy the KKT object first, or at least
+ * never use it again. */
+int32_t madqp_csr_map_pattern(madqp_csr_map* map, int64_t* rows_host, int64_t* stored_host, const int64_t** ptr,
+                              const int64_t** col);
+/* compress_jacobian! / compress_hessian! (src/KKT/normalkkt.jl:149-158): nzval[d] = sum of vals[sources of d] for every
+ * stored entry d.  vals: the nnz-long callback buffer; nzval: `stored` doubles, EVERY one written (it may hold anything
+ * before); nothing outside vals[0, nnz) is read.  Asynchronous on the context's stream (class MADQP_PROF_VEC).  A NULL vals
+ * with nnz > 0 or a NULL nzval with stored > 0: MADQP_ERR_ARG before any launch; no rows or nothing stored: no launch. */
+int32_t madqp_csr_map_apply(madqp_csr_map* map, const double* vals, double* nzval);
+int32_t madqp_csr_map_destroy(madqp_csr_map* map);
+
 /* ----------------------------------------- factorisation pieces */
 /* One block column ("panel": start and width multiples of 128, the last one may be short) of a matrix the caller owns:
  * the tile factorisation inside the P x Q distributed Cholesky below is built from these (csrc/dist.hip), and a host

@@ -7,7 +7,7 @@ plugin interface: :class:`HIPCondensedKKTSystem` / :class:`HIPCholeskySolver`
 (the ``mpc!`` loop of ``src/solver.jl``).  There is no CPU fallback.
 """
 from ._lib import EXPORTED_SYMBOLS, LIB_PATH, MadQPError, load_cdll
-from .backend import HipBackend, State
+from .backend import CSRMap, HipBackend, State
 from .batch import shard, solve_batch
 from .batched import BatchedMPCSolver
 from .kkt import (HIPScaledAugmentedKKTSystem, HIPAugmentedKKTSystem, HIPCholeskySolver, HIPCondensedKKTSystem, HIPNormalKKTSystem, HIPSparseAugmentedKKTSystem, HIPSparseCondensedKKTSystem,
@@ -20,7 +20,7 @@ from .solver import (ERROR_IN_STEP_COMPUTATION, MAXIMUM_ITERATIONS_EXCEEDED, SOL
 
 __all__ = [
     "HipBackend", "State", "shard", "solve_batch", "BatchedMPCSolver", "solve", "HIPCholeskySolver", "HIPAugmentedKKTSystem", "HIPScaledAugmentedKKTSystem", "HIPCondensedKKTSystem", "HIPNormalKKTSystem", "HIPSparseAugmentedKKTSystem", "HIPSparseCondensedKKTSystem", "HIPSparseNormalKKTSystem", "MPCSolver", "DeviceQP",
-    "DeviceCSR", "DeviceSymCSR",
+    "DeviceCSR", "DeviceSymCSR", "CSRMap",
     "IPMOptions", "AdaptiveStep", "ConservativeStep", "MehrotraAdaptiveStep", "NoRegularization",
     "FixedRegularization", "AdaptiveRegularization", "MadQPError", "SolveException", "load_cdll",
     "EXPORTED_SYMBOLS", "LIB_PATH", "stream_key", "SOLVE_SUCCEEDED", "MAXIMUM_ITERATIONS_EXCEEDED",

@@ -103,6 +103,8 @@ class CDebugGemvForm(C.Structure):
 
 GEMV_FORMS = ("none", "scale", "n_wave", "n_block", "t_single", "t_chunked", "t_strip")  # MADQP_GEMV_FORM_*
 
+CSR_KINDS = ("rows", "cols", "sym")  # MADQP_CSR_ROWS / _COLS / _SYM
+
 DEBUG_OPS = ("gemv_n", "gemv_n_then_t", "gemv_t", "symv_lower", "chol_solve", "prewrite_h")  # MADQP_DEBUG_OP_*
 
 
@@ -187,6 +189,11 @@ _SIGNATURES = {
     "madqp_coo_map_create_tiles_cyclic": [vp, i64, vp, vp, i64, i64, i32, i32, i32, i32, C.POINTER(vp)],
     "madqp_coo_map_apply": [vp, vp, vp, i64],
     "madqp_coo_map_destroy": [vp],
+    "madqp_csr_map_plan_host": [i64, vp, vp, i64, i64, i32, pi64, vp, vp, vp, vp],
+    "madqp_csr_map_create": [vp, i64, vp, vp, i64, i64, i32, C.POINTER(vp)],
+    "madqp_csr_map_pattern": [vp, pi64, pi64, C.POINTER(vp), C.POINTER(vp)],
+    "madqp_csr_map_apply": [vp, vp, vp],
+    "madqp_csr_map_destroy": [vp],
     "madqp_kkt_chol": [vp, C.POINTER(vp), pi64],
     "madqp_chol_factor_begin": [vp, vp, i64],
     "madqp_chol_factor_panel": [vp, i64, i64],

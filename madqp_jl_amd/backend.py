@@ -327,6 +327,33 @@ class HipBackend:
     def kkt_destroy(self, h):
         self.lib.madqp_kkt_destroy(h)
 
+    # ---- callback buffers -> CSR operands (madqp_csr_map_*) ----
+    def csr_map_create(self, I, J, nrows, ncols, kind):
+        """``I``, ``J``: the pattern as MadNLP keeps it (1-based, host); ``kind``: "rows" | "cols" | "sym"."""
+        import numpy as np
+
+        I, J = np.ascontiguousarray(I, dtype=np.int32), np.ascontiguousarray(J, dtype=np.int32)
+        if I.shape != J.shape or I.ndim != 1:
+            raise ValueError("I and J of a sparsity pattern are vectors of one length")
+        h = C.c_void_p()
+        self._ck(self.lib.madqp_csr_map_create(self.ctx, len(I), I.ctypes.data, J.ctypes.data, nrows, ncols,
+                                               _lib.CSR_KINDS.index(kind), C.byref(h)))
+        return h
+
+    def csr_map_pattern(self, h):
+        """(rows, stored entries, device address of ptr, device address of col); the arrays belong to the map."""
+        rows, stored, p, c = C.c_int64(), C.c_int64(), C.c_void_p(), C.c_void_p()
+        rc = self.lib.madqp_csr_map_pattern(h, C.byref(rows), C.byref(stored), C.byref(p), C.byref(c))
+        if rc != 0:
+            raise MadQPError(f"madqp_csr_map_pattern failed ({rc})")
+        return rows.value, stored.value, p.value, c.value
+
+    def csr_map_apply(self, h, vals, nzval):
+        self._ck(self.lib.madqp_csr_map_apply(h, ptr(vals), ptr(nzval)))
+
+    def csr_map_destroy(self, h):
+        self.lib.madqp_csr_map_destroy(h)
+
     def kkt_build(self, h, st):
         self._ck(self.lib.madqp_kkt_build(h, C.byref(st.cstruct)))
 
@@ -409,3 +436,36 @@ class HipBackend:
         buf = np.empty(count, dtype=np.float64)
         self._ck(self.lib.madqp_memcpy_d2h(self.ctx, buf.ctypes.data, dev_ptr, count * 8))
         return buf
+
+
+class CSRMap:
+    """``madqp_csr_map``: the CSR structure of a COO pattern on the device and the pass that moves callback values into
+    it (coo_to_csr src/utils.jl:148-197, compress_jacobian! src/KKT/normalkkt.jl:149-158).  ``ptr`` / ``col`` are device
+    addresses of arrays the map owns: a KKT object that was given them must not be used after :meth:`close`."""
+
+    def __init__(self, backend, I, J, nrows, ncols, kind):
+        self.be, self.kind = backend, kind
+        self._h = backend.csr_map_create(I, J, nrows, ncols, kind)
+        self.rows, self.stored, self.ptr, self.col = backend.csr_map_pattern(self._h)
+
+    def apply(self, vals, out):
+        """``out[d]`` = sum of the values of stored entry d's sources, in COO order; every entry of ``out`` is written."""
+        if out.numel() != self.stored or not out.is_contiguous() or (vals is not None and not vals.is_contiguous()):
+            raise ValueError("CSRMap.apply: out holds one contiguous double per stored entry, vals is contiguous")
+        self.be.csr_map_apply(self._h, vals, out)
+        return out
+
+    def pattern_host(self):
+        """Host copies (numpy int64) of ``ptr`` (rows + 1) and ``col`` (stored)."""
+        import numpy as np
+
+        p, c = np.empty(self.rows + 1, dtype=np.int64), np.empty(self.stored, dtype=np.int64)
+        self.be._ck(self.be.lib.madqp_memcpy_d2h(self.be.ctx, p.ctypes.data, self.ptr, p.nbytes))
+        if self.stored:
+            self.be._ck(self.be.lib.madqp_memcpy_d2h(self.be.ctx, c.ctypes.data, self.col, c.nbytes))
+        return p, c
+
+    def close(self):
+        if self._h is not None:
+            self.be.csr_map_destroy(self._h)
+            self._h = None

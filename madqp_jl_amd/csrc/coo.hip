@@ -7,6 +7,11 @@
 // non-atomically -- "do we need Atomix?").  Here the map is built once on the host: entries are grouped by destination
 // (stable, so duplicates keep their COO order) and one lane owns one destination -- a fixed summation order, no
 // atomics, bitwise reproducible.
+//
+// COO -> CSR for the sparse front end (madqp_csr_map_*): the same grouping gives, once per pattern, the CSR structure
+// of A, of A' or of the full symmetric H (coo_to_csr, src/utils.jl:148-197) and, per evaluation, the stored values from
+// the callback buffer (the A_csr_map pass of src/KKT/normalkkt.jl:84-91,149-158) -- one stored entry per distinct
+// destination, so the column indices of a row are distinct, as the CSR kernels of sparse.hip require.
 #include <algorithm>
 #include <numeric>
 
@@ -40,27 +45,52 @@ __global__ __launch_bounds__(256) void coo_apply_kernel(int64_t ndest, const int
         if (symmetric && i != j) dst[j * ld + i] = s;
     }
 }
+// nzval[d] = the values of the sources of stored entry d, added in ascending COO position from +0.0 (as above)
+__global__ __launch_bounds__(256) void csr_apply_kernel(int64_t stored, const int64_t* __restrict__ seg,
+                                                        const int64_t* __restrict__ src,
+                                                        const double* __restrict__ vals, double* __restrict__ nzval) {
+    for (int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x; d < stored; d += (int64_t)gridDim.x * 256) {
+        double s = 0.0;
+        for (int64_t k = seg[d]; k < seg[d + 1]; ++k) s += vals[src[k]];
+        nzval[d] = s;
+    }
+}
 }  // namespace
 
 namespace {
-// builds the map from destination keys (row * ncols + col, or -1 = entry dropped) of the nnz pattern entries
-int32_t coo_map_from_keys(madqp_ctx* ctx, int64_t nnz, const std::vector<int64_t>& key, int64_t nrows, int64_t ncols,
-                          int32_t symmetric, madqp_coo_map** out) {
-    std::vector<int64_t> perm;
-    perm.reserve((size_t)nnz);
-    for (int64_t k = 0; k < nnz; ++k)
-        if (key[(size_t)k] >= 0) perm.push_back(k);
+// Groups the entries with key >= 0 by key: perm = their positions in `key`, sorted by key and stable (entries of one key
+// keep their order: duplicates are summed in COO order); seg = ngroups + 1 offsets of the groups in perm; gkey = the key
+// of each group, strictly ascending.  The one grouping behind madqp_coo_map_* and madqp_csr_map_*.
+void group_by_key(const std::vector<int64_t>& key, std::vector<int64_t>& perm, std::vector<int64_t>& seg,
+                  std::vector<int64_t>& gkey) {
+    perm.clear();
+    seg.clear();
+    gkey.clear();
+    perm.reserve(key.size());
+    for (size_t k = 0; k < key.size(); ++k)
+        if (key[k] >= 0) perm.push_back((int64_t)k);
     std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) { return key[(size_t)a] < key[(size_t)b]; });
-    std::vector<int64_t> seg, row, col;
     for (size_t k = 0; k < perm.size(); ++k) {
         const int64_t kk = key[(size_t)perm[k]];
         if (k == 0 || kk != key[(size_t)perm[k - 1]]) {
             seg.push_back((int64_t)k);
-            row.push_back(kk / ncols);
-            col.push_back(kk % ncols);
+            gkey.push_back(kk);
         }
     }
     seg.push_back((int64_t)perm.size());
+}
+inline unsigned apply_grid(int64_t ndest) { return (unsigned)std::min<int64_t>((ndest + 255) / 256, 4096); }
+
+// builds the map from destination keys (row * ncols + col, or -1 = entry dropped) of the nnz pattern entries
+int32_t coo_map_from_keys(madqp_ctx* ctx, int64_t nnz, const std::vector<int64_t>& key, int64_t nrows, int64_t ncols,
+                          int32_t symmetric, madqp_coo_map** out) {
+    std::vector<int64_t> perm, seg, gkey;
+    group_by_key(key, perm, seg, gkey);
+    std::vector<int64_t> row(gkey.size()), col(gkey.size());
+    for (size_t d = 0; d < gkey.size(); ++d) {
+        row[d] = gkey[d] / ncols;
+        col[d] = gkey[d] % ncols;
+    }
     madqp_coo_map* m = new (std::nothrow) madqp_coo_map();
     if (!m) return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
     m->ctx = ctx;
@@ -179,9 +209,8 @@ extern "C" int32_t madqp_coo_map_apply(madqp_coo_map* m, const double* vals, dou
     HIP_TRY(ctx, hipMemset2DAsync(dst, (size_t)ld * sizeof(double), 0, (size_t)m->ncols * sizeof(double),
                                   (size_t)m->nrows, ctx->stream));
     if (m->ndest) {
-        const unsigned grid = (unsigned)std::min<int64_t>((m->ndest + 255) / 256, 4096);
-        hipLaunchKernelGGL(coo_apply_kernel, dim3(grid), dim3(256), 0, ctx->stream, m->ndest, m->d_perm, m->d_seg,
-                           m->d_row, m->d_col, vals, dst, ld, (int)m->symmetric, m->nnz);
+        hipLaunchKernelGGL(coo_apply_kernel, dim3(apply_grid(m->ndest)), dim3(256), 0, ctx->stream, m->ndest, m->d_perm,
+                           m->d_seg, m->d_row, m->d_col, vals, dst, ld, (int)m->symmetric, m->nnz);
         LAUNCH_CHECK(ctx);
     }
     return MADQP_OK;
@@ -194,6 +223,151 @@ extern "C" int32_t madqp_coo_map_destroy(madqp_coo_map* m) {
     if (m->d_seg) (void)hipFree(m->d_seg);
     if (m->d_row) (void)hipFree(m->d_row);
     if (m->d_col) (void)hipFree(m->d_col);
+    delete m;
+    return MADQP_OK;
+}
+
+// ------------------------------------------------------------------ COO -> CSR (madqp_csr_map_*)
+struct madqp_csr_map {
+    madqp_ctx* ctx;
+    int64_t nnz, rows, stored;
+    int64_t* d_ptr;  // rows + 1
+    int64_t* d_col;  // stored
+    int64_t* d_seg;  // stored + 1
+    int64_t* d_src;  // sources: COO positions grouped by stored entry, ascending within an entry
+};
+
+namespace {
+// The plan both madqp_csr_map_plan_host and madqp_csr_map_create are made from.  bad_entry: the first entry outside
+// the matrix (-1: the refusal has another cause).
+int32_t csr_map_plan(int64_t nnz, const int32_t* I, const int32_t* J, int64_t nrows, int64_t ncols, int32_t kind,
+                     int64_t* rows_out, std::vector<int64_t>& ptr, std::vector<int64_t>& col,
+                     std::vector<int64_t>& seg, std::vector<int64_t>& src, int64_t* bad_entry) {
+    *bad_entry = -1;
+    if (nnz < 0 || nrows < 0 || ncols < 0 || (nnz > 0 && !(I && J))) return MADQP_ERR_ARG;
+    if (kind != MADQP_CSR_ROWS && kind != MADQP_CSR_COLS && kind != MADQP_CSR_SYM) return MADQP_ERR_ARG;
+    if (kind == MADQP_CSR_SYM && nrows != ncols) return MADQP_ERR_ARG;
+    const int64_t rows = kind == MADQP_CSR_COLS ? ncols : nrows, width = kind == MADQP_CSR_COLS ? nrows : ncols;
+    // SYM: an off-diagonal entry feeds (i, j) and (j, i); its two keys sit side by side, so that the stable grouping
+    // keeps the sources of EITHER destination in ascending COO position whichever triangle they were given in
+    const int64_t per = kind == MADQP_CSR_SYM ? 2 : 1;
+    std::vector<int64_t> key((size_t)(per * nnz), -1);
+    for (int64_t k = 0; k < nnz; ++k) {
+        const int64_t i = (int64_t)I[k] - 1, j = (int64_t)J[k] - 1;  // MadNLP's patterns are 1-based
+        if (i < 0 || i >= nrows || j < 0 || j >= ncols) {
+            *bad_entry = k;
+            return MADQP_ERR_ARG;
+        }
+        if (kind == MADQP_CSR_COLS) {
+            key[(size_t)k] = j * width + i;
+        } else {
+            key[(size_t)(per * k)] = i * width + j;
+            if (kind == MADQP_CSR_SYM && i != j) key[(size_t)(per * k + 1)] = j * width + i;
+        }
+    }
+    std::vector<int64_t> gkey;
+    group_by_key(key, src, seg, gkey);
+    for (auto& p : src) p /= per;
+    ptr.assign((size_t)rows + 1, 0);
+    col.resize(gkey.size());
+    for (size_t d = 0; d < gkey.size(); ++d) {
+        ++ptr[(size_t)(gkey[d] / width) + 1];
+        col[d] = gkey[d] % width;
+    }
+    for (int64_t r = 0; r < rows; ++r) ptr[(size_t)r + 1] += ptr[(size_t)r];
+    *rows_out = rows;
+    return MADQP_OK;
+}
+}  // namespace
+
+extern "C" int32_t madqp_csr_map_plan_host(int64_t nnz, const int32_t* I_host, const int32_t* J_host, int64_t nrows,
+                                           int64_t ncols, int32_t kind, int64_t* sizes_host, int64_t* ptr_host,
+                                           int64_t* col_host, int64_t* seg_host, int64_t* src_host) {
+    const int given = (ptr_host != nullptr) + (col_host != nullptr) + (seg_host != nullptr) + (src_host != nullptr);
+    if (!sizes_host || (given != 0 && given != 4)) return MADQP_ERR_ARG;
+    std::vector<int64_t> ptr, col, seg, src;
+    int64_t rows = 0, bad = -1;
+    const int32_t rc = csr_map_plan(nnz, I_host, J_host, nrows, ncols, kind, &rows, ptr, col, seg, src, &bad);
+    if (rc) return rc;
+    sizes_host[0] = rows;
+    sizes_host[1] = (int64_t)col.size();
+    sizes_host[2] = (int64_t)src.size();
+    if (given) {
+        std::copy(ptr.begin(), ptr.end(), ptr_host);
+        std::copy(col.begin(), col.end(), col_host);
+        std::copy(seg.begin(), seg.end(), seg_host);
+        std::copy(src.begin(), src.end(), src_host);
+    }
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_csr_map_create(madqp_ctx* ctx, int64_t nnz, const int32_t* I_host, const int32_t* J_host,
+                                        int64_t nrows, int64_t ncols, int32_t kind, madqp_csr_map** out) {
+    ARG_TRY(ctx, ctx && out);
+    *out = nullptr;
+    std::vector<int64_t> ptr, col, seg, src;
+    int64_t rows = 0, bad = -1;
+    const int32_t rc = csr_map_plan(nnz, I_host, J_host, nrows, ncols, kind, &rows, ptr, col, seg, src, &bad);
+    if (rc && bad >= 0)
+        return madqp_fail(ctx, rc, "madqp_csr_map_create: entry %lld = (%lld, %lld) outside %lld x %lld", (long long)bad,
+                          (long long)I_host[bad], (long long)J_host[bad], (long long)nrows, (long long)ncols);
+    if (rc)
+        return madqp_fail(ctx, rc, "bad argument: madqp_csr_map_create(nnz=%lld, %lld x %lld, kind=%d)", (long long)nnz,
+                          (long long)nrows, (long long)ncols, (int)kind);
+    madqp_csr_map* m = new (std::nothrow) madqp_csr_map();
+    if (!m) return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
+    m->ctx = ctx;
+    m->nnz = nnz;
+    m->rows = rows;
+    m->stored = (int64_t)col.size();
+    m->d_ptr = m->d_col = m->d_seg = m->d_src = nullptr;
+    auto up = [&](int64_t** d, const std::vector<int64_t>& h) -> hipError_t {
+        hipError_t e = hipMalloc(d, std::max<size_t>(1, h.size()) * sizeof(int64_t));
+        if (e == hipSuccess && !h.empty())
+            e = hipMemcpy(*d, h.data(), h.size() * sizeof(int64_t), hipMemcpyHostToDevice);
+        return e;
+    };
+    hipError_t e = up(&m->d_ptr, ptr);
+    if (e == hipSuccess) e = up(&m->d_col, col);
+    if (e == hipSuccess) e = up(&m->d_seg, seg);
+    if (e == hipSuccess) e = up(&m->d_src, src);
+    if (e != hipSuccess) {
+        madqp_csr_map_destroy(m);
+        return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_csr_map_create: %s", hipGetErrorString(e));
+    }
+    *out = m;
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_csr_map_pattern(madqp_csr_map* m, int64_t* rows_host, int64_t* stored_host,
+                                         const int64_t** ptr, const int64_t** col) {
+    if (!m) return MADQP_ERR_ARG;
+    if (rows_host) *rows_host = m->rows;
+    if (stored_host) *stored_host = m->stored;
+    if (ptr) *ptr = m->d_ptr;
+    if (col) *col = m->d_col;
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_csr_map_apply(madqp_csr_map* m, const double* vals, double* nzval) {
+    if (!m) return MADQP_ERR_ARG;
+    madqp_ctx* ctx = m->ctx;
+    ARG_TRY(ctx, (vals || m->nnz == 0) && (nzval || m->stored == 0));
+    if (m->rows == 0 || m->stored == 0) return MADQP_OK;
+    ProfScope ps(ctx, MADQP_PROF_VEC);
+    hipLaunchKernelGGL(csr_apply_kernel, dim3(apply_grid(m->stored)), dim3(256), 0, ctx->stream, m->stored, m->d_seg,
+                       m->d_src, vals, nzval);
+    LAUNCH_CHECK(ctx);
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_csr_map_destroy(madqp_csr_map* m) {
+    if (!m) return MADQP_OK;
+    (void)hipStreamSynchronize(m->ctx->stream);
+    if (m->d_ptr) (void)hipFree(m->d_ptr);
+    if (m->d_col) (void)hipFree(m->d_col);
+    if (m->d_seg) (void)hipFree(m->d_seg);
+    if (m->d_src) (void)hipFree(m->d_src);
     delete m;
     return MADQP_OK;
 }

@@ -33,6 +33,42 @@ def stream_key(seed: int, stream: int) -> int:
     return _mix64((seed ^ ((stream * 0xD1B54A32D192ED03) & _MASK)) & _MASK)
 
 
+def csr_plan(I, J, nrows, ncols, kind):
+    """``madqp_csr_map_plan_host`` for a 0-based host pattern (duplicates allowed): ``(rows, ptr, col, seg, src)`` as
+    numpy int64 arrays -- the CSR structure ``madqp_csr_map_create`` would upload and, per stored entry, the COO positions
+    ``src[seg[d]:seg[d + 1]]`` of its sources in ascending order.  Host only: the library is loaded, no device is touched."""
+    import ctypes as C
+
+    from . import _lib
+
+    I, J = np.asarray(I, dtype=np.int64).ravel(), np.asarray(J, dtype=np.int64).ravel()
+    if len(I) != len(J):
+        raise ValueError("I and J of the sparsity pattern differ in length")
+    if len(I) and (min(I.min(), J.min()) < 0 or max(I.max(), J.max()) >= 2 ** 31 - 1):
+        raise ValueError("index out of range in the sparsity pattern")
+    I1, J1 = np.ascontiguousarray(I + 1, dtype=np.int32), np.ascontiguousarray(J + 1, dtype=np.int32)  # 1-based, as MadNLP's
+    lib, k = _lib.load_cdll(), _lib.CSR_KINDS.index(kind)
+    sizes = (C.c_int64 * 3)()
+    head = (len(I1), I1.ctypes.data, J1.ctypes.data, int(nrows), int(ncols), k, sizes)
+    if lib.madqp_csr_map_plan_host(*head, None, None, None, None) != 0:
+        raise ValueError(f"sparsity pattern refused: an entry outside {nrows} x {ncols}, or kind {kind!r} does not fit")
+    rows, stored, sources = sizes
+    ptr, col = np.zeros(rows + 1, dtype=np.int64), np.zeros(stored, dtype=np.int64)
+    seg, src = np.zeros(stored + 1, dtype=np.int64), np.zeros(sources, dtype=np.int64)
+    rc = lib.madqp_csr_map_plan_host(*head, ptr.ctypes.data, col.ctypes.data, seg.ctypes.data, src.ctypes.data)
+    assert rc == 0, rc
+    return rows, ptr, col, seg, src
+
+
+def _csr_values(vals, seg, src):
+    """The value rule of ``madqp_csr_map_apply`` on the host: per stored entry, its sources added one after the other
+    from +0.0 in ascending COO position (``numpy.add.at`` is unbuffered and takes the indices in order)."""
+    vals = np.asarray(vals, dtype=np.float64).ravel()
+    out = np.zeros(len(seg) - 1)
+    np.add.at(out, np.repeat(np.arange(len(seg) - 1), np.diff(seg)), vals[src])
+    return out
+
+
 class DeviceCSR:
     """A sparse Jacobian on the device: CSR of A (``ptr, col, val``; m rows, column indices ascending within
     a row) plus what the transposed products need -- the CSR of A' (``t_ptr, t_col``) and the permutation
@@ -61,6 +97,29 @@ class DeviceCSR:
         A = np.asarray(A, dtype=np.float64)
         r, c = np.nonzero(A)
         return cls(device, A.shape[0], A.shape[1], r, c, A[r, c])
+
+    @classmethod
+    def from_coo(cls, device, m, n, I, J, vals):
+        """From a COO pattern as a model reports it (0-based host arrays, any order, duplicates allowed) and its values:
+        duplicates are summed in COO order.  Built on ``madqp_csr_map_plan_host`` -- the plan the device maps
+        (``madqp_csr_map_create``, kinds rows and cols) upload -- so the container equals what the maps produce."""
+        vals = np.asarray(vals, dtype=np.float64).ravel()
+        if len(vals) != len(np.ravel(I)):
+            raise ValueError("vals and the sparsity pattern differ in length")
+        m, n = int(m), int(n)
+        _, ptr, col, seg, src = csr_plan(I, J, m, n, "rows")
+        _, t_ptr, t_col, _, _ = csr_plan(I, J, m, n, "cols")
+        rows = np.repeat(np.arange(m, dtype=np.int64), np.diff(ptr))
+        t_rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(t_ptr))  # column of A of every entry of A'
+        dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=device)
+        out = object.__new__(cls)
+        out.m, out.n, out.nnz = m, n, len(col)
+        out.ptr, out.col, out.row = dev(ptr, torch.int64), dev(col, torch.int64), dev(rows, torch.int64)
+        out.val = dev(_csr_values(vals, seg, src), torch.float64)
+        out.t_ptr, out.t_col = dev(t_ptr, torch.int64), dev(t_col, torch.int64)
+        # entry (r, c) of A' order sits at the position of key r * n + c among the (ascending) keys of A's order
+        out.t_perm = dev(np.searchsorted(rows * n + col, t_col * n + t_rows), torch.int64)
+        return out
 
     def scaled(self, row_scale):
         """A copy that shares the pattern, with row i multiplied by ``row_scale[i]``."""
@@ -120,6 +179,24 @@ class DeviceSymCSR:
         L = np.tril(np.asarray(H.detach().cpu().numpy() if torch.is_tensor(H) else H, dtype=np.float64))
         r, c = np.nonzero(L)
         return cls(device, L.shape[0], r, c, L[r, c])
+
+    @classmethod
+    def from_coo(cls, device, n, I, J, vals):
+        """From a COO pattern as a model reports it (0-based host arrays, any order, duplicates allowed, entries in EITHER
+        triangle) and its values: all entries of the pair {i, j} are summed in COO order into both (i, j) and (j, i).  Built
+        on ``madqp_csr_map_plan_host`` -- the plan the device map (``madqp_csr_map_create``, kind sym) uploads."""
+        vals = np.asarray(vals, dtype=np.float64).ravel()
+        if len(vals) != len(np.ravel(I)):
+            raise ValueError("vals and the sparsity pattern differ in length")
+        n = int(n)
+        _, ptr, col, seg, src = csr_plan(I, J, n, n, "sym")
+        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(ptr))
+        dev = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=device)
+        out = object.__new__(cls)
+        out.n, out.nnz, out.nnz_lower = n, len(col), int(np.count_nonzero(col <= rows))
+        out.ptr, out.col, out.row = dev(ptr, torch.int64), dev(col, torch.int64), dev(rows, torch.int64)
+        out.val = dev(_csr_values(vals, seg, src), torch.float64)
+        return out
 
     def to_dense(self):
         H = torch.zeros((self.n, self.n), dtype=torch.float64, device=self.val.device)
