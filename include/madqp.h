@@ -273,6 +273,19 @@ int32_t madqp_chol_set_signature(madqp_chol* s, int64_t npos);
 int32_t madqp_chol_factor(madqp_chol* s, double* A, int64_t lda, int32_t* info_host);
 /* MadNLP.solve!(linear_solver, rhs): rhs <- (L L')^-1 rhs in place (two triangular sweeps) */
 int32_t madqp_chol_solve(madqp_chol* s, double* rhs);
+/* Band-limited schedule.  bw is the half-bandwidth of the matrices this handle factors: A[i,j] = 0 for i - j > bw.  A
+ * Cholesky factor without pivoting stays inside the band, so with a bandwidth set madqp_chol_factor (every n) launches
+ * the left-looking schedule's products, diagonal kernels and panel solves on band-limited ranges only.  The storage
+ * stays dense and column-major.  0 <= bw < n sets it, bw = -1 clears it (the dense schedules, launch for launch as before
+ * the call); MADQP_ERR_ARG otherwise and on a handle with a signature npos < n.  With a bandwidth set,
+ * madqp_chol_set_signature(npos < n), madqp_chol_factor_begin and madqp_chol_factor_panel are refused the same way.
+ * CONTRACT.  The schedule works in 128-row tiles and 128-column k-ranges, so it reaches somewhat beyond the band:
+ * madqp_chol_band_extent gives the largest i - j of any entry a factorisation reads or writes (n - 1 with no bandwidth
+ * set).  The caller stores zeros for bw < i - j <= extent; the factorisation neither reads nor writes an entry with
+ * i - j > extent, and leaves zeros where it found them.  madqp_chol_solve is unchanged: it streams the whole lower
+ * triangle, so for a solve every entry outside the band must be zero.  info keeps the LAPACK convention. */
+int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw);
+int32_t madqp_chol_band_extent(madqp_chol* s, int64_t* extent_host);
 
 /* y = alpha*op(A) x + beta*y ; A has `rows` rows of length `cols`, row r at A + r*lda.
  * trans=0: y(rows) = A x(cols);  trans=1: y(cols) = A' x(rows).
@@ -472,6 +485,17 @@ int32_t madqp_kkt_set_hdiag(madqp_kkt* kkt, const double* hdiag);
  * hdiag set, with a dense Jacobian, in mode 1 or in the K2.5 form, and for a NULL h_ptr; madqp_kkt_set_hdiag after this
  * call is refused in the same way. */
 int32_t madqp_kkt_set_hcsr(madqp_kkt* kkt, const int64_t* h_ptr, const int64_t* h_col, const double* h_val);
+
+/* Band-limited assembly and factorisation for an object made by madqp_kkt_create_sparse in mode 0 or 1 with H NULL,
+ * diagonal or CSR, whose matrix has half-bandwidth <= bw (time- or grid-ordered models).  The pattern's own bandwidth --
+ * max over the rows of the CSR of V' of (last - first column), V diag(w) V' being the Gram term, and max |col - row| over
+ * the CSR of H -- is checked ONCE here, against the structures the object holds (a one-off download).  The call zeroes the
+ * stored K once and forwards bw to the object's Cholesky handle (madqp_chol_set_bandwidth); from then on madqp_kkt_build
+ * writes column j over the rows j .. min(order - 1, j + extent) only (zeros beyond j + bw; inside the band the bits of the
+ * dense assembly), which also removes what a factorisation that broke down left in bw < i - j <= extent.
+ * MADQP_ERR_ARG: a dense Jacobian, a dense H, the augmented and K2.5 forms, bw outside [0, order), bw below the pattern's
+ * bandwidth.  After this call madqp_kkt_set_hdiag and madqp_kkt_set_hcsr are refused. */
+int32_t madqp_kkt_set_bandwidth(madqp_kkt* kkt, int64_t bw);
 
 /* ----------------------------------------- callback buffers -> dense operands */
 /* MadNLP.SparseCallback hands the Jacobian / Hessian values as nnz-long buffers in the order of the model's COO

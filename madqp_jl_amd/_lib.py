@@ -135,6 +135,8 @@ _SIGNATURES = {
     "madqp_chol_create": [vp, i64, C.POINTER(vp)],
     "madqp_chol_destroy": [vp],
     "madqp_chol_set_signature": [vp, i64],
+    "madqp_chol_set_bandwidth": [vp, i64],
+    "madqp_chol_band_extent": [vp, pi64],
     "madqp_chol_factor": [vp, vp, i64, pi32],
     "madqp_chol_solve": [vp, vp],
     "madqp_gemv": [vp, i32, i64, i64, f64, vp, i64, vp, f64, vp],
@@ -184,6 +186,7 @@ _SIGNATURES = {
     "madqp_kkt_create_sparse": [vp, i32, i64, i64, i64, pi64, vp, i64, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
     "madqp_kkt_set_hdiag": [vp, vp],
     "madqp_kkt_set_hcsr": [vp, vp, vp, vp],
+    "madqp_kkt_set_bandwidth": [vp, i64],
     "madqp_coo_map_create": [vp, i64, vp, vp, i64, i64, i32, C.POINTER(vp)],
     "madqp_coo_map_create_cols_cyclic": [vp, i64, vp, vp, i64, i64, i64, i32, i32, C.POINTER(vp)],
     "madqp_coo_map_create_tiles_cyclic": [vp, i64, vp, vp, i64, i64, i32, i32, i32, i32, C.POINTER(vp)],

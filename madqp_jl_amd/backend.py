@@ -158,6 +158,16 @@ class HipBackend:
         """Quasi-definite mode: the stored [P, .; B, Q] stands for [P, B'; B, -Q], P of order ``npos``."""
         self._ck(self.lib.madqp_chol_set_signature(h, npos))
 
+    def chol_set_bandwidth(self, h, bw):
+        """Band-limited schedule for matrices with ``A[i, j] = 0`` for ``i - j > bw``; ``bw = -1`` (or None) clears it."""
+        self._ck(self.lib.madqp_chol_set_bandwidth(h, -1 if bw is None else int(bw)))
+
+    def chol_band_extent(self, h) -> int:
+        """Largest ``i - j`` a factorisation of this handle reads or writes (``n - 1`` with no bandwidth set)."""
+        ext = C.c_int64()
+        self._ck(self.lib.madqp_chol_band_extent(h, C.byref(ext)))
+        return ext.value
+
     def chol_factor(self, h, A, lda) -> int:
         info = C.c_int32()
         self._ck(self.lib.madqp_chol_factor(h, ptr(A), lda, C.byref(info)))
@@ -323,6 +333,10 @@ class HipBackend:
     def kkt_set_hcsr(self, h, hcsr):
         """``hcsr``: :class:`DeviceSymCSR` (full symmetric pattern; kept alive by the caller)."""
         self._ck(self.lib.madqp_kkt_set_hcsr(h, ptr(hcsr.ptr), ptr(hcsr.col), ptr(hcsr.val)))
+
+    def kkt_set_bandwidth(self, h, bw):
+        """Band-limited assembly and factorisation of a sparse condensed / normal KKT object (``madqp_kkt_set_bandwidth``)."""
+        self._ck(self.lib.madqp_kkt_set_bandwidth(h, int(bw)))
 
     def kkt_destroy(self, h):
         self.lib.madqp_kkt_destroy(h)

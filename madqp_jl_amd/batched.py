@@ -76,6 +76,9 @@ class BatchedMPCSolver:
             raise ValueError("refine_steps must be >= 0 (None: 0 for the batched engine)")
         if self.opt.kkt_system not in ("condensed", "normal") or self.opt.check_residual:
             raise ValueError("the batched driver supports the condensed KKT system and the normal equations, on one GPU")
+        if self.opt.kkt_bandwidth is not None:
+            raise ValueError("kkt_bandwidth: the batched engine factorises dense matrices (band-limited assembly and "
+                             "Cholesky belong to MPCSolver's sparse front end)")
         self.normal = self.opt.kkt_system == "normal"
         q0 = self.qps[0]
         self.B, self.nx, self.m = len(self.qps), q0.nvar, q0.ncon

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "common.h"
+#include "band_plan.inc"
 #include "mid_plan.inc"
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
@@ -1621,6 +1622,7 @@ struct CholModes {
     bool mid_dsyrk, mid_two, mid_lazy;  // MADQP_CHOL_MID_DSYRK / _TWO / _LAZY (1): see factor_mid
     int mid_cap;              // MADQP_CHOL_MID_CAP (0 = from the CU count; experiments)
     int64_t wt_min, wt_max;   // MADQP_CHOL_WMIN / WMAX (6, 20): outer panel width in blocks
+    int64_t band_w;           // MADQP_CHOL_BAND_W (0 = the rule of band_plan.inc): outer panel in blocks where a band limits it
 };
 static CholModes chol_modes_from_env() {
     auto is = [](const char* name, const char* v) { return getenv(name) && strcmp(getenv(name), v) == 0; };
@@ -1642,6 +1644,7 @@ static CholModes chol_modes_from_env() {
     m.mid_cap = (int)num("MADQP_CHOL_MID_CAP", 0);
     m.wt_min = num("MADQP_CHOL_WMIN", 6);
     m.wt_max = num("MADQP_CHOL_WMAX", 20);
+    m.band_w = std::max<int64_t>(0, num("MADQP_CHOL_BAND_W", 0));
     return m;
 }
 static const CholModes& chol_modes() {  // filled once, at the first use
@@ -1665,6 +1668,10 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
     s->ctx = ctx;
     s->n = n;
     s->npos = n;
+    s->bw = -1;
+    s->band_extent = n - 1;
+    s->band_ops = nullptr;
+    s->band_nops = 0;
     s->factored = false;
     s->A = nullptr;
     s->lda = 0;
@@ -1719,6 +1726,7 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
 extern "C" int32_t madqp_chol_set_signature(madqp_chol* s, int64_t npos) {
     if (!s) return MADQP_ERR_ARG;
     ARG_TRY(s->ctx, npos >= 0 && npos <= s->n && (npos % NB == 0 || npos == s->n));
+    ARG_TRY(s->ctx, s->bw < 0 || npos == s->n);  // the band schedule factors positive definite matrices only
     s->npos = npos;
     s->factored = false;
     return MADQP_OK;
@@ -1735,7 +1743,45 @@ extern "C" int32_t madqp_chol_destroy(madqp_chol* s) {
     if (s->upper) (void)hipFree(s->upper);
     if (s->utmp) (void)hipFree(s->utmp);
     delete[] s->mid_units;
+    delete[] s->band_ops;
     delete s;
+    return MADQP_OK;
+}
+
+// ---- band driver -------------------------------------------------------------------------------------------------------
+// A matrix with half-bandwidth bw (A[i,j] = 0 for i - j > bw) has a factor inside the same band, so the left-looking
+// schedule below runs its products, diagonal kernels and panel solves on band-limited ranges only: the plan of
+// band_plan.inc, built here once per bandwidth.  The storage stays dense; madqp_chol_solve still streams the whole lower
+// triangle.  bw = -1 clears the bandwidth (the dense schedules, launch for launch as without this call).
+extern "C" int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw) {
+    if (!s) return MADQP_ERR_ARG;
+    madqp_ctx* ctx = s->ctx;
+    ARG_TRY(ctx, bw == -1 || (bw >= 0 && bw < s->n && s->npos == s->n));
+    delete[] s->band_ops;
+    s->band_ops = nullptr;
+    s->band_nops = 0;
+    s->bw = bw;
+    s->band_extent = s->n - 1;
+    s->factored = false;
+    if (bw < 0) return MADQP_OK;
+    std::vector<BandOp> ops;
+    const CholModes& md = chol_modes();
+    s->band_extent = band_plan(s->n, bw, ctx->gemm_slots, ops, md.wt_min, md.wt_max, md.band_w);
+    s->band_ops = new (std::nothrow) BandOp[ops.size() + 1];
+    if (!s->band_ops) {
+        s->bw = -1;
+        s->band_extent = s->n - 1;
+        return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
+    }
+    std::copy(ops.begin(), ops.end(), s->band_ops);
+    s->band_nops = (int64_t)ops.size();
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_chol_band_extent(madqp_chol* s, int64_t* extent_host) {
+    if (!s) return MADQP_ERR_ARG;
+    ARG_TRY(s->ctx, extent_host != nullptr);
+    *extent_host = s->bw >= 0 ? s->band_extent : s->n - 1;
     return MADQP_OK;
 }
 
@@ -1744,21 +1790,10 @@ extern "C" int32_t madqp_chol_destroy(madqp_chol* s) {
 // make the last round of tiles as full as possible (tail quantisation is the main loss of a
 // left-looking factorisation; 8 fixed tile columns leave the last round 5-50 % full).
 static int64_t outer_panel_width(int64_t rows, bool has_update, int64_t slots) {
-    const int64_t mt = (rows + NB - 1) / NB;
-    if (!has_update || mt <= 6) return NBO;
-    int64_t best = NBO / NB;
-    double best_eff = -1.0;
-    for (int64_t wt = chol_modes().wt_min; wt <= chol_modes().wt_max && wt <= mt; ++wt) {
-        const int64_t tiles = mt * wt - wt * (wt - 1) / 2;
-        const int64_t rounds = (tiles + slots - 1) / slots;
-        const double eff = (double)tiles / (double)(rounds * slots);
-        if (eff > best_eff + 1e-9 || (eff > best_eff - 0.01 && wt > best && eff > 0.97)) {
-            best_eff = std::max(eff, best_eff);
-            best = wt;
-        }
-    }
-    return best * NB;
+    // (the rule itself lives with the band schedule, which falls back on it: band_plan.inc)
+    return plan_outer_width(rows, has_update, slots, chol_modes().wt_min, chol_modes().wt_max);
 }
+static_assert(BAND_NB == NB && BAND_NBO == NBO, "band_plan.inc plans in this file's blocks");
 
 // What a factorisation works on: one matrix, or B equally sized ones at fixed strides (the batch part; every launch
 // then covers all problems, grid.y / grid.x = problem, and leaves those with skip[b] != 0 alone).
@@ -1787,10 +1822,11 @@ static int32_t target_gemm(const CholTarget& t, const GemmArgs& g, int cls, int6
 }
 
 static int32_t panel_update(const CholTarget& t, int64_t row0, int64_t k0, int64_t width, int64_t kend = -1,
-                            double alpha = -1.0) {
+                            double alpha = -1.0, int64_t rows = -1) {
     // C[row0:n, row0:row0+width] += alpha L[row0:n, k0:kend] * L[row0:row0+width, k0:kend]'   (kend = row0
     // unless given: the distributed factorisation applies one received panel at a time; alpha = +1: the
     // columns of the positive block applied to the negative block of a quasi-definite matrix)
+    // rows >= 0 (band schedule): the rows row0 .. row0+rows-1 only -- whole 128-row tiles, or up to n
     if (kend < 0) kend = row0;
     GemmArgs g{};
     g.X = t.A + row0 + k0 * t.lda;
@@ -1803,11 +1839,11 @@ static int32_t panel_update(const CholTarget& t, int64_t row0, int64_t k0, int64
     g.ldcin = t.lda;
     g.alpha = alpha;
     g.beta = 1.0;
-    g.M = t.n - row0;
+    g.M = rows >= 0 ? rows : t.n - row0;
     g.N = width;
     g.K = kend - k0;
     if (t.padded()) {
-        g.Mread = t.npad() - row0;
+        g.Mread = rows >= 0 ? (rows + NB - 1) / NB * NB : t.npad() - row0;
         g.Nread = std::min<int64_t>(t.npad() - row0, (width + NB - 1) / NB * NB);
     }
     g.diag_off = 0;
@@ -1898,7 +1934,8 @@ int32_t madqp_chol_panel_solve(madqp_ctx* ctx, double* X, int64_t ldx, int64_t r
 
 // One 128-column block whose entries already carry every update from the columns to its left:
 // factor the diagonal block (and invert it), then L[below, jb] = C[below, jb] * W_jj'.
-static int32_t factor_block(const CholTarget& t, int64_t jb, int64_t w) {
+// rows_below >= 0 (band schedule): the panel solve covers that many rows only -- whole 128-row tiles, or up to n.
+static int32_t factor_block(const CholTarget& t, int64_t jb, int64_t w, int64_t rows_below = -1) {
     madqp_ctx* ctx = t.ctx;
     double* Ajj = t.A + jb + jb * t.lda;
     double* Wcm = t.winv + (jb / NB) * WBLK;
@@ -1911,8 +1948,9 @@ static int32_t factor_block(const CholTarget& t, int64_t jb, int64_t w) {
         LAUNCH_CHECK(ctx);
     }
     // the rows below the block; panel_inv_kernel serves one matrix with rows up to the padded order only
-    const int64_t rows = t.n - jb - w;
-    return madqp_chol_panel_solve(ctx, Ajj + w, t.lda, rows, t.padded() ? t.npad() - jb - w : rows, Ajj, t.lda, Wcm, w,
+    const int64_t rows = rows_below >= 0 ? rows_below : t.n - jb - w;
+    const int64_t rows_pad = rows_below >= 0 ? (rows + NB - 1) / NB * NB : t.npad() - jb - w;
+    return madqp_chol_panel_solve(ctx, Ajj + w, t.lda, rows, t.padded() ? rows_pad : rows, Ajj, t.lda, Wcm, w,
                                   !t.batched && t.padded() ? PANEL_INV_KERNEL : PANEL_INV_GEMM, t.batched ? &t : nullptr);
 }
 
@@ -2073,6 +2111,16 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
     const int64_t n = s->n;
     HIP_TRY(ctx, hipMemsetAsync(s->d_info, 0, sizeof(int32_t), ctx->stream));
     s->upper_ok = false;
+    if (s->bw >= 0) {  // band schedule, every n: the operations of band_plan.inc in their order, then the sweep images
+        const CholTarget t = chol_target(s, A, lda);
+        for (int64_t i = 0; i < s->band_nops; ++i) {
+            const BandOp& o = s->band_ops[i];
+            const int32_t r = o.kind == BAND_UPDATE ? panel_update(t, o.row0, o.k0, o.width, o.kend, -1.0, o.rows)
+                                                    : factor_block(t, o.row0, o.width, o.rows);
+            if (r) return r;
+        }
+        return invert_blocks(s, A, lda, 0, n);
+    }
     // mid-size matrices: right-looking, two launches per 128-column block (chol_mid_step_kernel)
     // (measured on bench.py, m = 0.4 n, ms per iteration against the left-looking schedule: 3.34 / 3.90 at n = 3 000,
     // 6.37 / 7.51 at 5 000, 13.7 / 15.1 at 8 000, 22.7 / 23.2 at 10 000, 34.4 / 33.0 at 12 000 -- every step rewrites
@@ -2195,6 +2243,7 @@ extern "C" int32_t madqp_chol_factor_begin(madqp_chol* s, double* A, int64_t lda
     madqp_ctx* ctx = s->ctx;
     ARG_TRY(ctx, A && lda >= s->n);
     ARG_TRY(ctx, s->npos == s->n);  // the panel pieces factor positive definite matrices only
+    ARG_TRY(ctx, s->bw < 0);        // ... and know no band
     s->factored = false;
     s->A = A;
     s->lda = lda;
@@ -2204,7 +2253,7 @@ extern "C" int32_t madqp_chol_factor_begin(madqp_chol* s, double* A, int64_t lda
 
 extern "C" int32_t madqp_chol_factor_panel(madqp_chol* s, int64_t j0, int64_t w) {
     if (!s) return MADQP_ERR_ARG;
-    ARG_TRY(s->ctx, panel_ok(s, j0, w));
+    ARG_TRY(s->ctx, panel_ok(s, j0, w) && s->bw < 0);
     const int32_t r = factor_range(chol_target(s, s->A, s->lda), j0, w);
     return r ? r : invert_blocks(s, s->A, s->lda, j0, w);  // (the caller packs / reads the images of this panel next)
 }

@@ -205,6 +205,11 @@ int32_t madqp_sparse_gram(madqp_ctx* ctx, int64_t n, const int64_t* rowptr, cons
                           const int64_t* t_ptr, const int64_t* t_col, const double* t_val, const double* w,
                           const double* base, int64_t ldbase, const double* dvec, const int64_t* b_ptr,
                           const int64_t* b_col, const double* b_val, double* C, int64_t ldc);
+// the band form (madqp_kkt_set_bandwidth): column j over the rows j .. min(n-1, j+extent), zeros beyond j+bw; sparse or no base
+int32_t madqp_sparse_gram_band(madqp_ctx* ctx, int64_t n, const int64_t* rowptr, const int64_t* col, const double* val,
+                               const int64_t* t_ptr, const int64_t* t_col, const double* t_val, const double* w,
+                               const double* dvec, const int64_t* b_ptr, const int64_t* b_col, const double* b_val,
+                               double* C, int64_t ldc, int64_t bw, int64_t extent);
 
 // chol.hip: the panel solve of one block of w <= 128 columns, X (rows x w) <- X L^-T (see there).  inv: how the products
 // with the 128 x 128 inverse (MADQP_CHOL_PANEL=inv) are formed -- the GEMM kernel, or panel_inv_kernel where it can serve.
@@ -245,4 +250,7 @@ struct madqp_chol {
     double* utmp;
     int64_t utmp_len;
     bool upper_ok;  // the last factorisation left U and substitution images
+    // band schedule (madqp_chol_set_bandwidth): half-bandwidth (-1: none), the plan of band_plan.inc and its extent
+    int64_t bw, band_extent, band_nops;
+    struct BandOp* band_ops;
 };

@@ -79,6 +79,9 @@ struct madqp_kkt {
     int64_t pos_nlb, pos_nub, pos_n;
     double* rs;
     bool fuse;  // MADQP_KKT_FUSE != 0
+    // band-limited assembly and factorisation (madqp_kkt_set_bandwidth): half-bandwidth of K (-1: none) and the rows below
+    // the diagonal the factorisation reaches (madqp_chol_band_extent), which every build rewrites
+    int64_t bw, band_extent;
 };
 
 namespace {
@@ -453,6 +456,7 @@ static int32_t kkt_create_common(madqp_ctx* ctx, int mode, int64_t nx, int64_t m
     if (!k) return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
     memset(k, 0, sizeof(*k));
     k->ctx = ctx;
+    k->bw = -1;
     k->mode = mode;
     k->nx = nx;
     k->m = m;
@@ -550,6 +554,7 @@ extern "C" int32_t madqp_kkt_set_hdiag(madqp_kkt* k, const double* hdiag) {
     if (!k) return MADQP_ERR_ARG;
     madqp_ctx* ctx = k->ctx;
     ARG_TRY(ctx, hdiag && !k->H && !k->h_ptr);
+    ARG_TRY(ctx, k->bw < 0);  // the bandwidth was checked against the Hessian the object held
     if (!k->sg) {
         const size_t nb = (size_t)std::max<int64_t>(k->nx + k->ns, 1) * sizeof(double);
         hipError_t e = hipMalloc(&k->sg, nb);
@@ -568,6 +573,7 @@ extern "C" int32_t madqp_kkt_set_hcsr(madqp_kkt* k, const int64_t* h_ptr, const 
     madqp_ctx* ctx = k->ctx;
     ARG_TRY(ctx, h_ptr && !k->H && !k->hdiag);
     ARG_TRY(ctx, k->a_ptr && k->mode != KKT_NORMAL && !k->scaled);
+    ARG_TRY(ctx, k->bw < 0);  // the bandwidth was checked against the Hessian the object held
     int64_t nnz = 0;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(&nnz, h_ptr + k->nx, sizeof(int64_t), hipMemcpyDeviceToHost));
@@ -575,6 +581,57 @@ extern "C" int32_t madqp_kkt_set_hcsr(madqp_kkt* k, const int64_t* h_ptr, const 
     k->h_ptr = h_ptr;
     k->h_col = h_col;
     k->h_val = h_val;
+    return MADQP_OK;
+}
+
+// Band-limited assembly and factorisation (see include/madqp.h).  The pattern's bandwidth is read off the structures the
+// object holds, once, on the host: K = base + V diag(w) V' has an entry (i, j) only where a row k of V' holds both i and j,
+// so its half-bandwidth is max_k (last - first column of row k of V'), and max |col - row| over the CSR of H.
+static int32_t csr_download(madqp_ctx* ctx, int64_t rows, const int64_t* d_ptr, const int64_t* d_col,
+                            std::vector<int64_t>& ptr, std::vector<int64_t>& col) {
+    ptr.assign((size_t)rows + 1, 0);
+    HIP_TRY(ctx, hipMemcpy(ptr.data(), d_ptr, (size_t)(rows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    ARG_TRY(ctx, ptr[0] == 0 && ptr[rows] >= 0);
+    col.assign((size_t)ptr[rows], 0);
+    if (ptr[rows]) HIP_TRY(ctx, hipMemcpy(col.data(), d_col, (size_t)ptr[rows] * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return MADQP_OK;
+}
+extern "C" int32_t madqp_kkt_set_bandwidth(madqp_kkt* k, int64_t bw) {
+    if (!k) return MADQP_ERR_ARG;
+    madqp_ctx* ctx = k->ctx;
+    ARG_TRY(ctx, k->a_ptr && !k->H && (k->mode == KKT_CONDENSED || k->mode == KKT_NORMAL) && !k->scaled);
+    const int64_t order = (k->mode == KKT_NORMAL) ? k->m : k->nx;
+    ARG_TRY(ctx, bw >= 0 && bw < order);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<int64_t> ptr, col;
+    int64_t pattern = 0;
+    {  // rows of V': the CSR of A' (nx rows) for the normal equations (V = A), the CSR of A (m rows) for the condensed form
+        const bool normal = k->mode == KKT_NORMAL;
+        const int64_t rows = normal ? k->nx : k->m;
+        const int32_t r = csr_download(ctx, rows, normal ? k->at_ptr : k->a_ptr, normal ? k->at_col : k->a_col, ptr, col);
+        if (r) return r;
+        for (int64_t i = 0; i < rows; ++i)
+            if (ptr[i + 1] > ptr[i]) pattern = std::max(pattern, col[ptr[i + 1] - 1] - col[ptr[i]]);
+    }
+    if (k->h_ptr) {
+        const int32_t r = csr_download(ctx, k->nx, k->h_ptr, k->h_col, ptr, col);
+        if (r) return r;
+        for (int64_t i = 0; i < k->nx; ++i)
+            for (int64_t p = ptr[i]; p < ptr[i + 1]; ++p) pattern = std::max<int64_t>(pattern, std::llabs(col[p] - i));
+    }
+    if (bw < pattern)
+        return madqp_fail(ctx, MADQP_ERR_ARG, "madqp_kkt_set_bandwidth(%lld): the pattern's half-bandwidth is %lld",
+                          (long long)bw, (long long)pattern);
+    const int32_t r = madqp_chol_set_bandwidth(k->chol, bw);
+    if (r) return r;
+    int64_t extent = 0;
+    const int32_t re = madqp_chol_band_extent(k->chol, &extent);
+    if (re) return re;
+    // K once: from now on nothing writes beyond the extent, and the solves stream the whole lower triangle
+    const int64_t dpad = std::max<int64_t>(128, (order + 127) / 128 * 128);
+    HIP_TRY(ctx, hipMemsetAsync(k->K, 0, ((size_t)k->ldk * dpad + 128) * sizeof(double), ctx->stream));
+    k->bw = bw;
+    k->band_extent = extent;
     return MADQP_OK;
 }
 
@@ -646,6 +703,9 @@ static int32_t kkt_build_impl(madqp_kkt* k, const madqp_state* st, int64_t nrang
         }
         if (k->a_ptr) {  // V = A (rows = constraints), weights 1/Sigma over the variables
             ARG_TRY(ctx, ranges == nullptr);
+            if (k->bw >= 0)
+                return madqp_sparse_gram_band(ctx, k->m, k->a_ptr, k->a_col, k->a_val, k->at_ptr, k->at_col, k->at_val, k->dn,
+                                              k->theta, nullptr, nullptr, nullptr, k->K, k->ldk, k->bw, k->band_extent);
             return madqp_sparse_gram(ctx, k->m, k->a_ptr, k->a_col, k->a_val, k->at_ptr, k->at_col, k->at_val, k->dn,
                                      nullptr, 0, k->theta, nullptr, nullptr, nullptr, k->K, k->ldk);
         }
@@ -683,6 +743,9 @@ static int32_t kkt_build_impl(madqp_kkt* k, const madqp_state* st, int64_t nrang
     const double* dvec = k->hdiag ? k->sg : st->pr_diag;  // diagonal of H + Sigma_x
     if (k->a_ptr) {  // V = A' (rows = variables), weights Theta over the constraints
         ARG_TRY(ctx, ranges == nullptr);
+        if (k->bw >= 0)
+            return madqp_sparse_gram_band(ctx, k->nx, k->at_ptr, k->at_col, k->at_val, k->a_ptr, k->a_col, k->a_val, k->theta,
+                                          dvec, k->h_ptr, k->h_col, k->h_val, k->K, k->ldk, k->bw, k->band_extent);
         return madqp_sparse_gram(ctx, k->nx, k->at_ptr, k->at_col, k->at_val, k->a_ptr, k->a_col, k->a_val, k->theta,
                                  k->H, k->ldh, dvec, k->h_ptr, k->h_col, k->h_val, k->K, k->ldk);
     }

@@ -86,7 +86,66 @@ __global__ __launch_bounds__(256) void sparse_gram_kernel(int64_t n, const int64
         __syncthreads();
     }
 }
+
+// Band form of sparse_gram_kernel for a matrix with half-bandwidth bw whose factorisation reaches `extent` below the
+// diagonal (madqp_chol_band_extent): column j is written over the rows j .. min(n-1, j+extent) only.  The base, diagonal
+// and scatter passes are those above on the same operands in the same order, so inside the band every entry has the bits of
+// the dense form; the rows j+bw+1 .. j+extent receive zeros -- every build, because a factorisation that ran on a NaN or
+// an overflow leaves NaN there and nothing else would overwrite them.  The base is sparse or absent (no dense H in this form).  A
+// pattern entry outside the band (the caller checked the pattern once; never expected) is dropped, not written out of range.
+__global__ __launch_bounds__(256) void sparse_gram_band_kernel(int64_t n, const int64_t* __restrict__ rowptr,
+                                                               const int64_t* __restrict__ col,
+                                                               const double* __restrict__ val,
+                                                               const int64_t* __restrict__ t_ptr,
+                                                               const int64_t* __restrict__ t_col,
+                                                               const double* __restrict__ t_val,
+                                                               const double* __restrict__ w,
+                                                               const double* __restrict__ dvec,
+                                                               const int64_t* __restrict__ b_ptr,
+                                                               const int64_t* __restrict__ b_col,
+                                                               const double* __restrict__ b_val,
+                                                               double* __restrict__ C, int64_t ldc, int64_t bw,
+                                                               int64_t extent) {
+    const int64_t j = blockIdx.x;
+    double* Cj = C + j * ldc;
+    const int64_t end = (j + extent < n - 1 ? j + extent : n - 1) + 1;  // one past the last row written
+    const int64_t band_end = (j + bw < n - 1 ? j + bw : n - 1) + 1;     // one past the last row of the band
+    // (no base: the dense form adds dvec[j] to 0.0; sparse base: it assigns dvec[j])
+    for (int64_t i = j + threadIdx.x; i < end; i += 256) Cj[i] = (dvec && i == j) ? (b_ptr ? dvec[j] : 0.0 + dvec[j]) : 0.0;
+    if (b_ptr) {
+        __syncthreads();
+        const int64_t e = b_ptr[j + 1];
+        for (int64_t p = b_ptr[j] + threadIdx.x; p < e; p += 256) {
+            const int64_t i = b_col[p];
+            if (i >= j && i < band_end) Cj[i] = (dvec && i == j) ? b_val[p] + dvec[j] : b_val[p];
+        }
+    }
+    __syncthreads();
+    for (int64_t p = rowptr[j]; p < rowptr[j + 1]; ++p) {
+        const int64_t k = col[p];
+        const double f = w[k] * val[p];
+        const int64_t e = t_ptr[k + 1];
+        for (int64_t q = t_ptr[k] + threadIdx.x; q < e; q += 256) {
+            const int64_t i = t_col[q];
+            if (i >= j && i < band_end) Cj[i] += f * t_val[q];
+        }
+        __syncthreads();
+    }
+}
 }  // namespace
+
+int32_t madqp_sparse_gram_band(madqp_ctx* ctx, int64_t n, const int64_t* rowptr, const int64_t* col, const double* val,
+                               const int64_t* t_ptr, const int64_t* t_col, const double* t_val, const double* w,
+                               const double* dvec, const int64_t* b_ptr, const int64_t* b_col, const double* b_val,
+                               double* C, int64_t ldc, int64_t bw, int64_t extent) {
+    if (n == 0) return MADQP_OK;
+    ARG_TRY(ctx, rowptr && t_ptr && w && C && ldc >= n && bw >= 0 && bw <= extent && extent < n);
+    ProfScope ps(ctx, MADQP_PROF_SYRK);
+    hipLaunchKernelGGL(sparse_gram_band_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, n, rowptr, col, val, t_ptr,
+                       t_col, t_val, w, dvec, b_ptr, b_col, b_val, C, ldc, bw, extent);
+    LAUNCH_CHECK(ctx);
+    return MADQP_OK;
+}
 
 int32_t madqp_spmv_csr(madqp_ctx* ctx, int64_t rows, const int64_t* rowptr, const int64_t* col, const double* val,
                        double alpha, const double* x, double beta, double* y, int prof_cls) {

@@ -10,19 +10,50 @@ test/runtests.jl:151).  Method names follow the reference's generic functions
 """
 from __future__ import annotations
 
+import numpy as np
+
 from .backend import State
 from .qp import DeviceSymCSR
+
+
+def pattern_bandwidth(A, H=None, form="condensed") -> int:
+    """Half-bandwidth of the matrix the sparse front end factorises, from the patterns alone (host, numpy): the number
+    ``madqp_kkt_set_bandwidth`` checks its argument against.  ``A``: :class:`DeviceCSR`; ``H``: None, a 1-D tensor
+    (diagonal) or a :class:`DeviceSymCSR`; ``form``: "condensed" (``H + Sigma_x + A' Theta A``: two variables meet where a
+    row of A holds both) or "normal" (``A Sigma^-1 A'``: two rows meet where a column of A holds both)."""
+    if form not in ("condensed", "normal"):
+        raise ValueError(f"a bandwidth is defined for the condensed and the normal form, not {form!r}")
+    host = lambda t: t.detach().cpu().numpy()
+    ptr, col = (host(A.ptr), host(A.col)) if form == "condensed" else (host(A.t_ptr), host(A.t_col))
+    bw = 0
+    rows = np.flatnonzero(np.diff(ptr) > 0)  # (column indices ascend within a row)
+    if len(rows):
+        bw = int(np.max(col[ptr[rows + 1] - 1] - col[ptr[rows]]))
+    if isinstance(H, DeviceSymCSR) and H.nnz:
+        if form == "normal":
+            raise ValueError("The KKT system NormalKKTSystem supports only linear programs "
+                             "(or a diagonal Hessian given as a vector).")
+        bw = max(bw, int(np.max(np.abs(host(H.col) - host(H.row)))))
+    return bw
 
 
 class HIPCholeskySolver:
     """AbstractLinearSolver contract: ctor keeps the matrix it re-reads at every
     ``factorize`` (src/KKT/normalkkt.jl:99-101); ``solve`` is in place (:196)."""
 
-    def __init__(self, backend, kkt_handle):
+    def __init__(self, backend, kkt_handle, bandwidth=None):
+        """``bandwidth``: half-bandwidth of the matrix (sparse condensed / normal KKT objects only): assembly and
+        factorisation are band-limited from here on (``madqp_kkt_set_bandwidth``).  None: the dense schedules."""
         self.be, self._kkt = backend, kkt_handle
         self.info = 0
+        self.bandwidth = None
+        if bandwidth is not None:
+            backend.kkt_set_bandwidth(kkt_handle, int(bandwidth))
+            self.bandwidth = int(bandwidth)
 
     def introduce(self) -> str:  # MadNLP.introduce, src/solver.jl:360
+        if self.bandwidth is not None:
+            return f"madqp-hip blocked left-looking fp64 Cholesky, band-limited (bw = {self.bandwidth}; MFMA, gfx950)"
         return "madqp-hip blocked left-looking fp64 Cholesky (MFMA, gfx950)"
 
     def factorize(self):  # MadNLP.factorize!
@@ -263,8 +294,27 @@ class _SparseMixin:
         self.linear_solver = HIPCholeskySolver(backend, self._h)
         self.n_factorizations = 0
 
+    _band_form = None  # "condensed" / "normal" on the classes that take a bandwidth
+
+    def set_bandwidth(self, bw):
+        """Band-limited assembly and factorisation from here on.  ``bw``: the half-bandwidth of the KKT matrix (at least
+        :func:`pattern_bandwidth`, which the library checks once), or "auto" = that number.  Returns the bandwidth set.
+        Cannot be undone on this object; dense Hessians and the augmented forms are refused."""
+        if self._band_form is None:
+            raise ValueError("a bandwidth is taken by the sparse condensed and normal KKT systems only")
+        if self.H is not None and not isinstance(self.H, DeviceSymCSR) and self.H.dim() == 2:
+            raise ValueError("a bandwidth needs a sparse (DeviceSymCSR), diagonal or absent Hessian, not a dense one")
+        if isinstance(bw, str):
+            if bw != "auto":
+                raise ValueError(f"bandwidth: an int or 'auto', not {bw!r}")
+            bw = pattern_bandwidth(self.csr, self.H, self._band_form)
+        self.linear_solver = HIPCholeskySolver(self.be, self._h, bandwidth=int(bw))
+        return int(bw)
+
 
 class HIPSparseCondensedKKTSystem(_SparseMixin, HIPCondensedKKTSystem):
+    _band_form = "condensed"
+
     def __init__(self, backend, st, nx, ind_ineq, H, csr):
         if H is not None and not isinstance(H, DeviceSymCSR) and H.dim() == 2:
             assert H.is_contiguous() and H.shape == (nx, nx)
@@ -274,6 +324,7 @@ class HIPSparseCondensedKKTSystem(_SparseMixin, HIPCondensedKKTSystem):
 class HIPSparseNormalKKTSystem(_SparseMixin, HIPNormalKKTSystem):
     """Normal equations A (H + Sigma)^-1 A' with H = 0 (the reference's LP-only NormalKKTSystem) or H diagonal
     (1-D tensor; SURVEY.md 8a-note -- what CONT-type QPs need)."""
+    _band_form = "normal"
 
     def __init__(self, backend, st, nx, ind_ineq, H, csr):
         if H is not None and (isinstance(H, DeviceSymCSR) or H.dim() != 1):

@@ -60,7 +60,15 @@ class IPMOptions:
         # <= REFINE_AUTO_MAX -- where a solve costs microseconds -- and none above, where the 16-blocked arithmetic is
         # what LAPACK's own blocked kernels do and the larger parity cases sit within the stated bar without it.
         refine_steps=None,
+        # extension: band-limited assembly and Cholesky for KKT matrices that are band matrices (time- or grid-ordered
+        # models) in the sparse front end, condensed or normal form, H sparse, diagonal or absent.  None (default): the
+        # dense schedules, bit for bit as without the option.  "auto": kkt.pattern_bandwidth of the model, used only when
+        # bw + 1 <= order / 4 (KKT_BAND_AUTO_FRACTION), dense otherwise.  An int: that half-bandwidth (the library checks
+        # it against the pattern).  Refused for the dense front end, a dense H, the augmented forms, a grid and batches.
+        kkt_bandwidth=None,
     )
+    KKT_BAND_AUTO_FRACTION = 4
+
     REFINE_AUTO_MAX = 1024  # MADQP_REFINE_AUTO_MAX overrides
 
     @staticmethod

@@ -19,7 +19,7 @@ import torch
 
 from ._lib import CMpcInfo, CMpcOptions
 from .kkt import (HIPAugmentedKKTSystem, HIPCondensedKKTSystem, HIPNormalKKTSystem, HIPScaledAugmentedKKTSystem,
-                  HIPSparseAugmentedKKTSystem, HIPSparseCondensedKKTSystem, HIPSparseNormalKKTSystem)
+                  HIPSparseAugmentedKKTSystem, HIPSparseCondensedKKTSystem, HIPSparseNormalKKTSystem, pattern_bandwidth)
 from .options import (AdaptiveRegularization, AdaptiveStep, ConservativeStep, FixedRegularization,
                       IPMOptions, MehrotraAdaptiveStep, NoRegularization)
 from .qp import DeviceCSR, DeviceQP, DeviceSymCSR
@@ -118,6 +118,19 @@ class MPCSolver:
                 raise ValueError("a sparse Hessian (DeviceSymCSR) is assembled on one GPU; a DistributedQP takes a dense H")
             if not isinstance(qp.A, DeviceCSR):
                 raise ValueError("a sparse Hessian (DeviceSymCSR) needs the sparse front end (A as DeviceCSR)")
+        bwo = self.opt.kkt_bandwidth
+        if bwo is not None:  # band-limited assembly / Cholesky: sparse front end, condensed or normal form, no dense H
+            if not (bwo == "auto" or (isinstance(bwo, int) and not isinstance(bwo, bool) and bwo >= 0)):
+                raise ValueError(f"kkt_bandwidth: None, 'auto' or a non-negative int, not {bwo!r}")
+            if hasattr(qp, "grid"):
+                raise ValueError("kkt_bandwidth: the band-limited factorisation runs on one GPU; a DistributedQP is dense")
+            if not isinstance(qp.A, DeviceCSR):
+                raise ValueError("kkt_bandwidth needs the sparse front end (A as DeviceCSR)")
+            if self.opt.kkt_system in ("augmented", "scaled_augmented"):
+                raise ValueError("kkt_bandwidth: the augmented KKT systems are not band matrices in this library's "
+                                 "ordering; use kkt_system='condensed' or 'normal'")
+            if torch.is_tensor(qp.H) and qp.H.dim() == 2:
+                raise ValueError("kkt_bandwidth needs a sparse (DeviceSymCSR), diagonal or absent Hessian, not a dense one")
         self.full_qp, self._fixed = qp, None
         if fvt == "make_parameter":
             self._fixed = qp.eliminate_fixed()
@@ -374,7 +387,16 @@ class MPCSolver:
         if isinstance(self.A, DeviceCSR):  # sparse front end: dense K / Cholesky, CSR products
             cls = {"normal": HIPSparseNormalKKTSystem, "augmented": HIPSparseAugmentedKKTSystem,
                    "condensed": HIPSparseCondensedKKTSystem}[opt.kkt_system]
-            return cls(be, st, nx, self.ind_ineq, self.H, self.A)
+            kkt = cls(be, st, nx, self.ind_ineq, self.H, self.A)
+            if opt.kkt_bandwidth is not None:
+                bw, order = opt.kkt_bandwidth, (self.m if opt.kkt_system == "normal" else nx)
+                if bw == "auto":  # only where the band is narrow: the dense schedules are the better ones otherwise
+                    bw = pattern_bandwidth(self.A, self.H, opt.kkt_system)
+                    if (bw + 1) * IPMOptions.KKT_BAND_AUTO_FRACTION > order:
+                        bw = None
+                if bw is not None:
+                    kkt.set_bandwidth(bw)
+            return kkt
         if opt.kkt_system == "augmented":
             return HIPAugmentedKKTSystem(be, st, nx, self.ind_ineq, self.H, self.A)
         if opt.kkt_system == "scaled_augmented":

@@ -5,7 +5,10 @@ and the per-class split.  python tools/bench_sparse.py --nx 60000 --ncon 20000 -
 A non-diagonal Hessian, dense against sparse (``DeviceSymCSR``), on the CONT-type problem with a smoothing term on the
 controls -- the same command with and without ``--sparse-hessian``:
 
-    python tools/bench_sparse.py --cont 150 --smooth 1.0 --kkt condensed --warmup 2 --steps 5 [--sparse-hessian]"""
+    python tools/bench_sparse.py --cont 150 --smooth 1.0 --kkt condensed --warmup 2 --steps 5 [--sparse-hessian]
+
+``--bandwidth auto`` (or an integer) runs the assembly and the Cholesky band-limited (option ``kkt_bandwidth``): the CONT-type
+normal equations of ``--cont N`` have half-bandwidth 2 N.  The same command without it is the dense schedule to compare with."""
 import argparse
 import json
 import os
@@ -34,7 +37,7 @@ def bench_hessian_forms(a, be):
     else:
         form, h_bytes = "dense", qp.H.numel() * qp.H.element_size()
     kw = {} if a.kkt == "augmented" else dict(regularization=M.FixedRegularization(1e-8, 0.0 if a.kkt == "normal" else -1e-8))
-    s = M.MPCSolver(qp, be, kkt_system=a.kkt, driver="native", max_iter=300, **kw)
+    s = M.MPCSolver(qp, be, kkt_system=a.kkt, driver="native", max_iter=300, kkt_bandwidth=a.bandwidth, **kw)
 
     def window(steps):  # the first iterations of a fresh solve (the problem converges in a handful): the same ones every time
         s.initialize()
@@ -58,11 +61,20 @@ def bench_hessian_forms(a, be):
     split = {c: round(v[0] / max(pdone, 1), 3) for c, v in prof.items() if v[1]}
     print(json.dumps({"workload": f"boundary-control QP N={a.cont} smooth={a.smooth}: nx={h.nvar} m={h.ncon} nnzj={h.nnzj} "
                                   f"nnzh={h.nnzh}, {a.kkt}", "hessian": form, "hessian_bytes": h_bytes,
-                      "iterations_timed": done, "ms_per_iteration": dt / max(done, 1) * 1e3,
+                      "bandwidth": s.kkt.linear_solver.bandwidth, "iterations_timed": done, "ms_per_iteration": dt / max(done, 1) * 1e3,
                       "iterations_per_s": done / dt if done else None, "iterations_profiled": pdone,
                       "split_ms_per_iteration": split, "assembly_ms": split.get("syrk"), "matvec_ms": split.get("gemv"),
                       "last": s.trace[-1] if s.trace else None}))
     s.close()
+
+
+def bandwidth_arg(v):
+    """--bandwidth: "auto" or a non-negative integer (option kkt_bandwidth)"""
+    if v == "auto":
+        return v
+    if not v.isdigit():
+        raise argparse.ArgumentTypeError("auto or a non-negative integer")
+    return int(v)
 
 
 def main():
@@ -80,6 +92,8 @@ def main():
                    "library's device timers)")
     p.add_argument("--sparse-hessian", action="store_true", help="keep a non-diagonal H sparse (DeviceSymCSR)")
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--bandwidth", type=bandwidth_arg, default=None, metavar="{auto,INT}",
+                   help="band-limited assembly and Cholesky (kkt_bandwidth); needs a sparse, diagonal or absent Hessian")
     a = p.parse_args()
     import torch
 
@@ -96,20 +110,27 @@ def main():
         qp = P.to_device(h, be)
         t_gen = time.perf_counter() - t0
         s = M.MPCSolver(qp, be, kkt_system="normal", regularization=M.FixedRegularization(1e-8, 0.0), driver="native",
-                        max_iter=100)
-        be.prof_enable(M._lib.PROF_CLASSES)
-        be.prof_reset()
+                        max_iter=100, kkt_bandwidth=a.bandwidth)
+        # two whole solves of the same problem: the first without the device timers (time per iteration), the second
+        # with them (the per-class split; a timer scope per launch costs host time the first window must not carry)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         r = s.solve()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        be.prof_enable(M._lib.PROF_CLASSES)
+        be.prof_reset()
+        r2 = s.solve()
+        torch.cuda.synchronize()
         prof = be.prof_get()
+        be.prof_enable(())
+        assert r2["iter"] == r["iter"]
         nf = max(r["n_factorizations"], 1)
         print(json.dumps({"workload": f"boundary-control QP N={a.cont}: nx={h.nvar} m={h.ncon} nnz={h.nnzj}, diagonal H, "
                                       "normal equations (m x m dense)", "status": r["status"], "iterations": r["iter"],
+                          "bandwidth": s.kkt.linear_solver.bandwidth, "ms_per_iteration": dt / max(r["iter"], 1) * 1e3,
                           "objective": r["objective"], "solve_seconds": dt, "generate_seconds": t_gen,
-                          "factorizations": r["n_factorizations"],
+                          "factorizations": r["n_factorizations"], "band_w": os.environ.get("MADQP_CHOL_BAND_W"),
                           "ms_per_factorization": {c: round(v[0] / nf, 2) for c, v in prof.items() if v[1]},
                           "last": r["trace"][-1]}))
         s.close()
@@ -130,7 +151,7 @@ def main():
         be.gen_wigner(M.stream_key(11, 2), n, 1.0 / np.sqrt(n), H)
     qp = M.DeviceQP(H, q, csr, z(n, 0.0), z(n, 1.0), z(m, 0.0), z(m, 1.0), z(n, 0.0))
     reg = M.FixedRegularization(1e-8, 0.0 if a.kkt == "normal" else -1e-8)
-    s = M.MPCSolver(qp, be, kkt_system=a.kkt, regularization=reg, driver="native", max_iter=300)
+    s = M.MPCSolver(qp, be, kkt_system=a.kkt, regularization=reg, driver="native", max_iter=300, kkt_bandwidth=a.bandwidth)
     s.initialize()
     s.iteration_head()
     s.iteration_body()

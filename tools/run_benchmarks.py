@@ -12,6 +12,8 @@ diagonal-Hessian QPs, the condensed system otherwise (``--kkt-system`` overrides
     python tools/run_benchmarks.py DIR [--reformulate] [--sparse-hessian] [--out results.txt]
 
 ``--sparse-hessian`` keeps a non-diagonal Q sparse on the device (``DeviceSymCSR``) instead of densifying it.
+``--bandwidth auto`` (or an integer) asks for the band-limited assembly and Cholesky (option ``kkt_bandwidth``) wherever the
+instance can take it: the condensed or normal form with a sparse, diagonal or absent Hessian.
 """
 import argparse
 import os
@@ -25,7 +27,8 @@ sys.path.insert(0, ROOT)
 EXT = (".mps", ".qps", ".sif", ".mps.gz", ".qps.gz", ".sif.gz")
 
 
-def run(directory, reformulate=False, kkt_system=None, out=None, backend=None, verbose=True, sparse_hessian=False):
+def run(directory, reformulate=False, kkt_system=None, out=None, backend=None, verbose=True, sparse_hessian=False,
+        bandwidth=None):
     import madqp_jl_amd as M
     from madqp_jl_amd import preprocess as P
 
@@ -52,9 +55,12 @@ def run(directory, reformulate=False, kkt_system=None, out=None, backend=None, v
             be.prof_enable(lin_classes)
             be.prof_reset()
             t0 = time.perf_counter()
-            s = M.MPCSolver(P.to_device(model, be, sparse_hessian=sparse_hessian), be, max_iter=300, max_ncorr=3, scaling=True,
+            dq = P.to_device(model, be, sparse_hessian=sparse_hessian)
+            dense_h = dq.H is not None and not isinstance(dq.H, M.DeviceSymCSR) and dq.H.dim() == 2
+            band = bandwidth if ksys in ("condensed", "normal") and isinstance(dq.A, M.DeviceCSR) and not dense_h else None
+            s = M.MPCSolver(dq, be, max_iter=300, max_ncorr=3, scaling=True,
                             step_rule=M.AdaptiveStep(0.995), regularization=M.FixedRegularization(1e-8, -1e-8),
-                            kkt_system=ksys, rethrow_error=True, mu_min=1e-12, driver="native")  # :33-45
+                            kkt_system=ksys, rethrow_error=True, mu_min=1e-12, driver="native", kkt_bandwidth=band)  # :33-45
             r = s.solve()
             total = time.perf_counter() - t0
             prof = be.prof_get()
@@ -82,8 +88,12 @@ def main():
     p.add_argument("--kkt-system", choices=("condensed", "normal", "augmented"), default=None)
     p.add_argument("--out", default=None)
     p.add_argument("--sparse-hessian", action="store_true", help="keep a non-diagonal Hessian sparse (DeviceSymCSR)")
+    p.add_argument("--bandwidth", default=None, metavar="{auto,INT}",
+                   type=lambda v: v if v == "auto" else int(v), help="band-limited assembly and Cholesky where it applies")
     a = p.parse_args()
-    run(a.directory, a.reformulate, a.kkt_system, a.out, sparse_hessian=a.sparse_hessian)
+    if a.bandwidth is not None and a.bandwidth != "auto" and a.bandwidth < 0:
+        p.error("--bandwidth: auto or a non-negative integer")
+    run(a.directory, a.reformulate, a.kkt_system, a.out, sparse_hessian=a.sparse_hessian, bandwidth=a.bandwidth)
 
 
 if __name__ == "__main__":
