@@ -282,10 +282,20 @@ int32_t madqp_chol_solve(madqp_chol* s, double* rhs);
  * CONTRACT.  The schedule works in 128-row tiles and 128-column k-ranges, so it reaches somewhat beyond the band:
  * madqp_chol_band_extent gives the largest i - j of any entry a factorisation reads or writes (n - 1 with no bandwidth
  * set).  The caller stores zeros for bw < i - j <= extent; the factorisation neither reads nor writes an entry with
- * i - j > extent, and leaves zeros where it found them.  madqp_chol_solve is unchanged: it streams the whole lower
- * triangle, so for a solve every entry outside the band must be zero.  info keeps the LAPACK convention. */
+ * i - j > extent, and leaves zeros where it found them.  With a bandwidth set (and MADQP_SWEEP_BAND not 0)
+ * madqp_chol_solve too reads no entry with i - j > extent: its sweeps stream, per block row, the (bw + 127) / 128 tiles
+ * next to the diagonal block only, which reach min(n - 1, 128 ((bw + 127) / 128) + 127) <= extent.  So zeros for
+ * bw < i - j <= extent are all that is asked of the storage; what lies beyond the extent is never looked at and may hold
+ * anything.  (MADQP_SWEEP_BAND=0: the sweeps stream the whole lower triangle, and every entry outside the band must be
+ * zero for a solve.)  Every call, setting or clearing, changes the form of the sweeps at once, so what the handle last
+ * factored is no longer solved with: madqp_chol_solve returns MADQP_ERR_STATE until the next madqp_chol_factor.
+ * info keeps the LAPACK convention. */
 int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw);
 int32_t madqp_chol_band_extent(madqp_chol* s, int64_t* extent_host);
+/* What the sweeps of madqp_chol_solve run as, three values: out_host[0] the 128-blocks a block row reads left of its
+ * diagonal block ((bw + 127) / 128 under a bandwidth; -1: all of them, the dense sweeps), out_host[1] the workgroups of
+ * one sweep, out_host[2] the tiles per sweep job (MADQP_SWEEP_CHUNK).  MADQP_ERR_ARG for a NULL handle or NULL out_host. */
+int32_t madqp_chol_sweep_info(madqp_chol* s, int64_t* out_host);
 
 /* y = alpha*op(A) x + beta*y ; A has `rows` rows of length `cols`, row r at A + r*lda.
  * trans=0: y(rows) = A x(cols);  trans=1: y(cols) = A' x(rows).

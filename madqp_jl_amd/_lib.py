@@ -137,6 +137,7 @@ _SIGNATURES = {
     "madqp_chol_set_signature": [vp, i64],
     "madqp_chol_set_bandwidth": [vp, i64],
     "madqp_chol_band_extent": [vp, pi64],
+    "madqp_chol_sweep_info": [vp, pi64],
     "madqp_chol_factor": [vp, vp, i64, pi32],
     "madqp_chol_solve": [vp, vp],
     "madqp_gemv": [vp, i32, i64, i64, f64, vp, i64, vp, f64, vp],

@@ -168,6 +168,13 @@ class HipBackend:
         self._ck(self.lib.madqp_chol_band_extent(h, C.byref(ext)))
         return ext.value
 
+    def chol_sweep_info(self, h):
+        """``(blocks, workgroups, chunk)`` of this handle's triangular sweeps: the 128-blocks a block row reads left of
+        its diagonal block (-1: the dense sweeps), the workgroups of one sweep and the tiles per sweep job."""
+        out = (C.c_int64 * 3)()
+        self._ck(self.lib.madqp_chol_sweep_info(h, out))
+        return tuple(out)
+
     def chol_factor(self, h, A, lda) -> int:
         info = C.c_int32()
         self._ck(self.lib.madqp_chol_factor(h, ptr(A), lda, C.byref(info)))

@@ -1,5 +1,6 @@
-// Schedule of the band-limited left-looking factorisation (see chol.hip, "band driver"): plain C++, shared by chol.hip and
-// the CPU test build tests/csrc_band/band_plan_cpu.cpp.  The matrix is dense, column-major and of order n with
+// Schedule of the band-limited left-looking factorisation (see chol.hip, "band driver") and, at the end, the job lists of
+// the triangular sweeps under a band: plain C++, shared by chol.hip and the CPU test builds
+// tests/csrc_band/band_plan_cpu.cpp and tests/csrc_band_sweep/band_sweep_cpu.cpp.  The matrix is dense, column-major and of order n with
 // half-bandwidth bw (A[i,j] = 0 for i - j > bw); a factor without pivoting stays inside the band, so every product and
 // every panel solve of the dense schedule is cut down to the rows and the k-range the band can reach.
 #include <algorithm>
@@ -88,4 +89,27 @@ static int64_t band_plan(int64_t n, int64_t bw, int64_t slots, std::vector<BandO
     for (const BandOp& o : ops)
         extent = std::max(extent, o.kind == BAND_UPDATE ? o.row0 + o.rows - 1 - o.k0 : o.width + o.rows - 1);
     return extent;
+}
+
+// ---- the triangular sweeps under a band (chol.hip, trsv_*_sweep_kernel) --------------------------------------------------
+// Block row r of the factor has nonzero tiles (r, j) for r - kb <= j < r only, kb = band_up(bw) / 128: a tile further left
+// holds entries with i - j >= (kb + 1) 128 - 127 > bw alone.  The sweeps read those tiles and the diagonal blocks, so the
+// largest i - j they touch is min(n - 1, kb 128 + 127) -- never above the extent of band_plan, whose first BLOCK op alone
+// reaches min(band_up(bw) + 127, n - 1) for n >= 128.  The backward sweep is the same in chain coordinates (position rr
+// is block nblk - 1 - rr, its tiles are counted from the last block row).
+static int64_t band_sweep_blocks(int64_t bw) { return band_up(bw) / BAND_NB; }
+static int64_t band_sweep_lo(int64_t r, int64_t kb) { return kb < 0 ? 0 : std::max<int64_t>(0, r - kb); }
+static int64_t band_sweep_reach(int64_t n, int64_t kb) { return std::min(n - 1, kb * BAND_NB + BAND_NB - 1); }
+
+// The job list of one sweep over nblk block rows (ticket -> r | c << 20, ordered by (r, c)): chunk c of row r stands for
+// the tiles [c chunk, min(r, (c + 1) chunk)), and under a band only the chunks that meet [lo(r), r) are jobs -- c from
+// lo(r) / chunk on; the last chunk owns the row and is a job even where the row has no tile (r = 0, kb = 0).  kb < 0 or
+// kb >= nblk - 1: every chunk, the dense list.  Returns the most chunks any row has (the stride of the partial-sum slots).
+static int64_t band_sweep_jobs(int64_t nblk, int64_t kb, int64_t chunk, std::vector<int32_t>& jobs) {
+    jobs.clear();
+    for (int64_t r = 0; r < nblk; ++r) {
+        const int64_t nc = std::max<int64_t>(1, (r + chunk - 1) / chunk);
+        for (int64_t c = std::min(band_sweep_lo(r, kb) / chunk, nc - 1); c < nc; ++c) jobs.push_back((int32_t)(r | (c << 20)));
+    }
+    return std::max<int64_t>(1, (nblk - 1 + chunk - 1) / chunk);
 }

@@ -603,6 +603,9 @@ __device__ __forceinline__ void sweep_poll_block(const double* __restrict__ x, i
 // tiles c*chunk .. min(r, (c+1)*chunk) - 1 of block r (counted from the far end of the dependency chain); the job
 // holding the tile next to the diagonal owns the block, the others publish their 128 partial sums to
 // part[(r*maxc + c)*128 ..] the way solution blocks are published.  jobs == nullptr: one job per block.
+// Under a band of kb blocks (the kernels' last argument; negative: none) block r has the tiles lo = max(0, r - kb) .. r - 1
+// only: a job starts at max(c*chunk, lo), the chunks before lo / chunk are no jobs (band_plan.inc, band_sweep_jobs) and
+// the owner adds the partial sums from that chunk on.  The protocol -- tickets, sentinel, spin limit, order -- is the same.
 struct SweepPlan {
     const int32_t* jobs;  // ticket -> r | c << 20, ordered by (r, c): a job waits only for earlier tickets
     double* part;
@@ -625,11 +628,12 @@ __device__ __forceinline__ double sweep_poll_one(const double* p, double* __rest
 
 // The partial sums of a block's other jobs for the lane's two entries, added in job order.  Up to four jobs' words are
 // requested at once: one after the other, each an L2 round trip of ~1 us, they were half of a hop at n = 50 000 (six
-// jobs per block row: 6.2 us per hop where n = 5 000, one job per row, takes 3.2).
-__device__ __forceinline__ void sweep_far2(const double* __restrict__ pp, int c, int lane, double* __restrict__ err,
-                                           double& f0, double& f1) {
+// jobs per block row: 6.2 us per hop where n = 5 000, one job per row, takes 3.2).  cfirst: the row's first job (0 unless
+// a band cuts the row short: the chunks before it are no jobs and publish nothing).
+__device__ __forceinline__ void sweep_far2(const double* __restrict__ pp, int cfirst, int c, int lane,
+                                           double* __restrict__ err, double& f0, double& f1) {
     f0 = f1 = 0.0;
-    for (int c0 = 0; c0 < c; c0 += 4) {
+    for (int c0 = cfirst; c0 < c; c0 += 4) {
         unsigned long long u[4][2];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -859,7 +863,7 @@ __global__ __launch_bounds__(1024) void trsv_fwd_sweep_kernel(const double* __re
                                                               const double* __restrict__ b,
                                                               double* __restrict__ y, int64_t n,
                                                               int32_t* __restrict__ ctl, double* __restrict__ fault,
-                                                              int vec, SweepPlan plan, double* __restrict__ out) {
+                                                              int vec, SweepPlan plan, double* __restrict__ out, int kb) {
     static_assert(!REV || DIAG == 1, "the sweep on U runs the substituting diagonal step");
     __shared__ double xs[2][NB];
     __shared__ double red[16][NB];
@@ -869,13 +873,20 @@ __global__ __launch_bounds__(1024) void trsv_fwd_sweep_kernel(const double* __re
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) s_r = atomicAdd(&ctl[REV ? 2 : 1], 1);
     __syncthreads();
-    int r = s_r, c = 0, j0 = 0, j1 = r;
+    int r = s_r, c = 0, j0 = 0, j1 = r, clo = 0;
     if (plan.jobs) {
         const int32_t job = plan.jobs[r];
         r = job & 0xFFFFF;
         c = job >> 20;
         j0 = c * plan.chunk;
         j1 = (j0 + plan.chunk < r) ? j0 + plan.chunk : r;
+    }
+    // (these ranges are mirrored by the CPU checks of the job lists -- tests/band_sweep_cases.py `ranges` and
+    // tests/csrc_band_sweep/band_sweep_main.cpp `check` --: change them together)
+    if (kb >= 0 && r > kb) {  // the band: tiles before r - kb hold nothing of the factor and are not read
+        const int lo = r - kb;
+        j0 = j0 > lo ? j0 : lo;
+        if (plan.jobs) clo = lo / plan.chunk;
     }
     const bool owner = (j1 == r);
     const int rl = r;  // the block's place in the chain (partial sums are filed under it)
@@ -942,7 +953,7 @@ __global__ __launch_bounds__(1024) void trsv_fwd_sweep_kernel(const double* __re
                 st_sc1_f64(plan.part + ((int64_t)rl * plan.maxc + c) * NB + tid, sum);
             } else {
                 double far = 0.0;  // the partial sums of this block's other jobs, in column order
-                for (int cc = 0; cc < c; ++cc)
+                for (int cc = clo; cc < c; ++cc)
                     far += sweep_poll_one(plan.part + ((int64_t)rl * plan.maxc + cc) * NB + tid, fault);
                 vs[tid] = (tid < w) ? (b0 - (far + sum)) : 0.0;
             }
@@ -963,7 +974,7 @@ __global__ __launch_bounds__(1024) void trsv_fwd_sweep_kernel(const double* __re
         s1 += red[q][64 + lane];
     }
     double far0, far1;  // the partial sums of this block's other jobs, in column order
-    sweep_far2(plan.part + (int64_t)rl * plan.maxc * NB, c, lane, fault, far0, far1);
+    sweep_far2(plan.part + (int64_t)rl * plan.maxc * NB, clo, c, lane, fault, far0, far1);
     const double u0 = lane < w ? b0 - (far0 + s0) : 0.0, u1 = 64 + lane < w ? b1 - (far1 + s1) : 0.0;
     const double2_t z = REV ? sweep_diag_bwd<DIAG>(ximg, lane, u0, u1) : sweep_diag_fwd<DIAG>(ximg, lane, u0, u1);
     if (lane < w) st_sc1_f64(y + row0 + lane, z.x);
@@ -1007,7 +1018,7 @@ __global__ __launch_bounds__(1024) void trsv_bwd_sweep_kernel(const double* __re
                                                               const double* __restrict__ y,
                                                               double* __restrict__ x, int64_t n,
                                                               int32_t* __restrict__ ctl, double* __restrict__ fault,
-                                                              int vec, SweepPlan plan) {
+                                                              int vec, SweepPlan plan, int kb) {
     __shared__ double xs[2][NB];
     __shared__ double red[DIAG ? 1 : 16][NB];
     __shared__ double vs[NB];
@@ -1019,13 +1030,18 @@ __global__ __launch_bounds__(1024) void trsv_bwd_sweep_kernel(const double* __re
     if (tid == 0) s_r = atomicAdd(&ctl[2], 1);
     __syncthreads();
     // block nblk-1-rr has rr tiles below its diagonal block; the job takes tiles k0 .. k1-1 counted from the last row
-    int rr = s_r, c = 0, k0 = 0, k1 = rr;
+    int rr = s_r, c = 0, k0 = 0, k1 = rr, clo = 0;
     if (plan.jobs) {
         const int32_t job = plan.jobs[rr];
         rr = job & 0xFFFFF;
         c = job >> 20;
         k0 = c * plan.chunk;
         k1 = (k0 + plan.chunk < rr) ? k0 + plan.chunk : rr;
+    }
+    if (kb >= 0 && rr > kb) {  // the band, in chain coordinates (see the forward kernel, and the mirrors named there)
+        const int lo = rr - kb;
+        k0 = k0 > lo ? k0 : lo;
+        if (plan.jobs) clo = lo / plan.chunk;
     }
     const bool owner = (k1 == rr);
     const int r = nblk - 1 - rr;
@@ -1116,7 +1132,7 @@ __global__ __launch_bounds__(1024) void trsv_bwd_sweep_kernel(const double* __re
     if (DIAG == 0) {
         if (tid < NB) {
             double far = 0.0;
-            for (int cc = 0; cc < c; ++cc)
+            for (int cc = clo; cc < c; ++cc)
                 far += sweep_poll_one(plan.part + ((int64_t)rr * plan.maxc + cc) * NB + tid, fault);
             vs[tid] = (tid < w) ? (y0 - (far + vs[tid])) : 0.0;
         }
@@ -1127,7 +1143,7 @@ __global__ __launch_bounds__(1024) void trsv_bwd_sweep_kernel(const double* __re
     }
     if (wave != 0) return;  // wave 0 alone from here, no further barrier
     double far0, far1;
-    sweep_far2(plan.part + (int64_t)rr * plan.maxc * NB, c, lane, fault, far0, far1);
+    sweep_far2(plan.part + (int64_t)rr * plan.maxc * NB, clo, c, lane, fault, far0, far1);
     const double u0 = lane < w ? y0 - (far0 + vs[lane]) : 0.0, u1 = 64 + lane < w ? y1 - (far1 + vs[64 + lane]) : 0.0;
     const double2_t z = sweep_diag_bwd<DIAG>(ximg, lane, u0, u1);
     if (lane < w) st_sc1_f64(x + col0 + lane, z.x);
@@ -1618,6 +1634,7 @@ struct CholModes {
     int sweep_diag;    // MADQP_SWEEP_DIAG: 1 (default), 2 = sub16, 0 = inv (see sweep_diag_mode)
     bool sweep_upper;  // MADQP_SWEEP_UPPER (1): backward sweep of a mid-size factor on U = L'
     int32_t sweep_chunk;      // MADQP_SWEEP_CHUNK (64): tiles of a block row per sweep job
+    bool sweep_band;          // MADQP_SWEEP_BAND (1): under a bandwidth the sweeps stay inside the band; 0: whole block rows
     int64_t mid_max;          // MADQP_CHOL_MID_MAX (13312): largest order of the mid-size schedule
     bool mid_dsyrk, mid_two, mid_lazy;  // MADQP_CHOL_MID_DSYRK / _TWO / _LAZY (1): see factor_mid
     int mid_cap;              // MADQP_CHOL_MID_CAP (0 = from the CU count; experiments)
@@ -1635,6 +1652,7 @@ static CholModes chol_modes_from_env() {
     m.sweep_diag = is("MADQP_SWEEP_DIAG", "inv") ? 0 : is("MADQP_SWEEP_DIAG", "sub16") ? 2 : 1;
     m.sweep_upper = on("MADQP_SWEEP_UPPER");
     m.sweep_chunk = (int32_t)std::max<int64_t>(1, num("MADQP_SWEEP_CHUNK", 64));
+    m.sweep_band = on("MADQP_SWEEP_BAND");
     m.mid_max = num("MADQP_CHOL_MID_MAX", 13312);
     m.mid_dsyrk = on("MADQP_CHOL_MID_DSYRK");
     // two panels per trailing pass (see the kernel): needs the diagonal workgroup's own SYRK
@@ -1685,17 +1703,18 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
     // sweeps: block rows longer than `chunk` tiles are streamed by several workgroups (SweepPlan).  tmp holds the
     // intermediate vector (padded to whole blocks) followed by the partial-sum slots of both sweeps, so that one fill
     // per solve resets all of them.
-    s->sweep_chunk = chol_modes_from_env().sweep_chunk;  // (read per handle: the tests build job lists with several chunks)
+    const CholModes md = chol_modes_from_env();  // (read per handle: the tests build job lists with several chunks)
+    s->sweep_chunk = md.sweep_chunk;
+    s->sweep_band = md.sweep_band;
+    s->sweep_kb = -1;
     s->sweep_maxc = 0;
     s->sweep_njobs = 0;
+    s->band_njobs = 0;
     s->d_jobs = nullptr;
+    s->d_band_jobs = nullptr;
     std::vector<int32_t> jobs;
     if (nblk - 1 > s->sweep_chunk && nblk < (1 << 20)) {
-        s->sweep_maxc = (int32_t)((nblk - 1 + s->sweep_chunk - 1) / s->sweep_chunk);
-        for (int64_t r = 0; r < nblk; ++r) {
-            const int64_t nc = std::max<int64_t>(1, (r + s->sweep_chunk - 1) / s->sweep_chunk);
-            for (int64_t c = 0; c < nc; ++c) jobs.push_back((int32_t)(r | (c << 20)));
-        }
+        s->sweep_maxc = (int32_t)band_sweep_jobs(nblk, -1, s->sweep_chunk, jobs);
         s->sweep_njobs = (int32_t)jobs.size();
     }
     s->tmp_len = nblk * NB + 2 * nblk * (int64_t)s->sweep_maxc * NB;
@@ -1738,6 +1757,7 @@ extern "C" int32_t madqp_chol_destroy(madqp_chol* s) {
     if (s->winv) (void)hipFree(s->winv);
     if (s->tmp) (void)hipFree(s->tmp);
     if (s->d_jobs) (void)hipFree(s->d_jobs);
+    if (s->d_band_jobs) (void)hipFree(s->d_band_jobs);
     if (s->d_info) (void)hipFree(s->d_info);
     if (s->d_mid_plan) (void)hipFree(s->d_mid_plan);
     if (s->upper) (void)hipFree(s->upper);
@@ -1751,8 +1771,10 @@ extern "C" int32_t madqp_chol_destroy(madqp_chol* s) {
 // ---- band driver -------------------------------------------------------------------------------------------------------
 // A matrix with half-bandwidth bw (A[i,j] = 0 for i - j > bw) has a factor inside the same band, so the left-looking
 // schedule below runs its products, diagonal kernels and panel solves on band-limited ranges only: the plan of
-// band_plan.inc, built here once per bandwidth.  The storage stays dense; madqp_chol_solve still streams the whole lower
-// triangle.  bw = -1 clears the bandwidth (the dense schedules, launch for launch as without this call).
+// band_plan.inc, built here once per bandwidth.  The storage stays dense.  The sweeps of madqp_chol_solve stay inside the
+// band as well (MADQP_SWEEP_BAND, default 1): block row r streams the band_sweep_blocks(bw) tiles next to its diagonal
+// block, along a job list of its own where the dense sweeps have one.  bw = -1 clears the bandwidth (the dense schedules
+// and sweeps, launch for launch as without this call).
 extern "C" int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw) {
     if (!s) return MADQP_ERR_ARG;
     madqp_ctx* ctx = s->ctx;
@@ -1762,19 +1784,63 @@ extern "C" int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw) {
     s->band_nops = 0;
     s->bw = bw;
     s->band_extent = s->n - 1;
+    // the form of the sweeps changes with this call and what is stored may be the factor of another schedule: a solve
+    // needs a new factorisation first (madqp_chol_solve refuses with MADQP_ERR_STATE until then)
     s->factored = false;
+    s->A = nullptr;
+    s->upper_ok = false;
+    s->sweep_kb = -1;
+    s->band_njobs = 0;
+    if (s->d_band_jobs) {  // (a solve on the stream may still read it)
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipFree(s->d_band_jobs));
+        s->d_band_jobs = nullptr;
+    }
     if (bw < 0) return MADQP_OK;
+    if (s->sweep_band) {
+        const int64_t kb = band_sweep_blocks(bw);
+        if (s->d_jobs) {
+            std::vector<int32_t> jobs;
+            band_sweep_jobs((s->n + NB - 1) / NB, kb, s->sweep_chunk, jobs);
+            hipError_t e = hipMalloc(&s->d_band_jobs, jobs.size() * sizeof(int32_t));
+            if (e == hipSuccess) e = hipMemcpy(s->d_band_jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                if (s->d_band_jobs) (void)hipFree(s->d_band_jobs);
+                s->d_band_jobs = nullptr;
+                s->bw = -1;
+                return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_chol_set_bandwidth: %s", hipGetErrorString(e));
+            }
+            s->band_njobs = (int32_t)jobs.size();
+        }
+        s->sweep_kb = kb;
+    }
     std::vector<BandOp> ops;
     const CholModes& md = chol_modes();
     s->band_extent = band_plan(s->n, bw, ctx->gemm_slots, ops, md.wt_min, md.wt_max, md.band_w);
     s->band_ops = new (std::nothrow) BandOp[ops.size() + 1];
     if (!s->band_ops) {
         s->bw = -1;
+        s->sweep_kb = -1;
+        s->band_njobs = 0;
+        if (s->d_band_jobs) (void)hipFree(s->d_band_jobs);  // (uploaded with a blocking copy: nothing reads it yet)
+        s->d_band_jobs = nullptr;
         s->band_extent = s->n - 1;
         return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
     }
     std::copy(ops.begin(), ops.end(), s->band_ops);
     s->band_nops = (int64_t)ops.size();
+    return MADQP_OK;
+}
+
+// What the sweeps of madqp_chol_solve run as: [0] the blocks a block row reads left of its diagonal block (-1: all of them,
+// the dense sweeps), [1] workgroups per sweep, [2] tiles per job (MADQP_SWEEP_CHUNK).
+extern "C" int32_t madqp_chol_sweep_info(madqp_chol* s, int64_t* out_host) {
+    if (!s || !out_host) return MADQP_ERR_ARG;
+    const bool band = s->sweep_kb >= 0;
+    const int64_t nblk = std::max<int64_t>(1, (s->n + NB - 1) / NB);
+    out_host[0] = band ? s->sweep_kb : -1;
+    out_host[1] = !s->d_jobs ? nblk : band ? s->band_njobs : s->sweep_njobs;
+    out_host[2] = s->sweep_chunk;
     return MADQP_OK;
 }
 
@@ -1868,19 +1934,21 @@ static int32_t invert_blocks(madqp_chol* s, double* A, int64_t lda, int64_t j0, 
 }
 template <int DIAG>
 static void launch_sweep(bool bwd, unsigned grid, hipStream_t st, const double* L, int64_t ld, const double* winv, const double* in,
-                         double* out, int64_t n, int32_t* ctl, double* fault, int vec, const SweepPlan& plan) {
+                         double* out, int64_t n, int32_t* ctl, double* fault, int vec, const SweepPlan& plan, int kb) {
     if (bwd)
-        hipLaunchKernelGGL(trsv_bwd_sweep_kernel<DIAG>, dim3(grid), dim3(1024), 0, st, L, ld, winv, in, out, n, ctl, fault, vec, plan);
+        hipLaunchKernelGGL(trsv_bwd_sweep_kernel<DIAG>, dim3(grid), dim3(1024), 0, st, L, ld, winv, in, out, n, ctl, fault, vec, plan,
+                           kb);
     else
         hipLaunchKernelGGL(trsv_fwd_sweep_kernel<DIAG>, dim3(grid), dim3(1024), 0, st, L, ld, winv, in, out, n, ctl, fault, vec, plan,
-                           (double*)nullptr);
+                           (double*)nullptr, kb);
 }
+// kb: the band of the sweep in blocks (band_plan.inc), -1 for the whole block rows
 static void launch_sweep(bool bwd, unsigned grid, hipStream_t st, const double* L, int64_t ld, const double* winv, const double* in,
-                         double* out, int64_t n, int32_t* ctl, double* fault, int vec, const SweepPlan& plan) {
+                         double* out, int64_t n, int32_t* ctl, double* fault, int vec, const SweepPlan& plan, int kb = -1) {
     switch (sweep_diag_mode()) {
-        case 0: launch_sweep<0>(bwd, grid, st, L, ld, winv, in, out, n, ctl, fault, vec, plan); break;
-        case 2: launch_sweep<2>(bwd, grid, st, L, ld, winv, in, out, n, ctl, fault, vec, plan); break;
-        default: launch_sweep<1>(bwd, grid, st, L, ld, winv, in, out, n, ctl, fault, vec, plan); break;
+        case 0: launch_sweep<0>(bwd, grid, st, L, ld, winv, in, out, n, ctl, fault, vec, plan, kb); break;
+        case 2: launch_sweep<2>(bwd, grid, st, L, ld, winv, in, out, n, ctl, fault, vec, plan, kb); break;
+        default: launch_sweep<1>(bwd, grid, st, L, ld, winv, in, out, n, ctl, fault, vec, plan, kb); break;
     }
 }
 
@@ -2313,9 +2381,9 @@ extern "C" int32_t madqp_chol_solve(madqp_chol* s, double* rhs) {
         hipLaunchKernelGGL(sweep_prep_kernel, dim3((unsigned)std::min<int64_t>((s->utmp_len + 255) / 256, 256)), dim3(256), 0,
                            ctx->stream, reinterpret_cast<unsigned long long*>(s->utmp), s->utmp_len, s->d_info);
         hipLaunchKernelGGL((trsv_fwd_sweep_kernel<1, false>), dim3(grid), dim3(1024), 0, ctx->stream, A, lda, s->winv,
-                           (const double*)rhs, yv, n, s->d_info, fault, 1, pf, (double*)nullptr);
+                           (const double*)rhs, yv, n, s->d_info, fault, 1, pf, (double*)nullptr, -1);
         hipLaunchKernelGGL((trsv_fwd_sweep_kernel<1, true>), dim3(grid), dim3(1024), 0, ctx->stream, (const double*)s->upper,
-                           s->upper_ld, s->winv, (const double*)yv, xv, n, s->d_info, fault, 1, pb, rhs);
+                           s->upper_ld, s->winv, (const double*)yv, xv, n, s->d_info, fault, 1, pb, rhs, -1);
         LAUNCH_CHECK(ctx);
         return MADQP_OK;
     }
@@ -2324,14 +2392,17 @@ extern "C" int32_t madqp_chol_solve(madqp_chol* s, double* rhs) {
         const unsigned nblk = (unsigned)((n + NB - 1) / NB);
         const int vec = ((((uintptr_t)A) & 15) == 0) && (lda % 2 == 0);
         const int64_t nb64 = nblk;
-        const unsigned grid = s->d_jobs ? (unsigned)s->sweep_njobs : nblk;
+        // under a bandwidth the band form: the tiles within sweep_kb blocks of the diagonal, its own (shorter) job list
+        const int kb = (int)s->sweep_kb;
+        const int32_t* jobs = kb >= 0 ? s->d_band_jobs : s->d_jobs;
+        const unsigned grid = jobs ? (unsigned)(kb >= 0 ? s->band_njobs : s->sweep_njobs) : nblk;
         double* part_f = s->tmp + nb64 * NB;
         double* part_b = part_f + nb64 * s->sweep_maxc * NB;
-        const SweepPlan pf{s->d_jobs, part_f, s->sweep_chunk, s->sweep_maxc};
-        const SweepPlan pb{s->d_jobs, part_b, s->sweep_chunk, s->sweep_maxc};
+        const SweepPlan pf{jobs, part_f, s->sweep_chunk, s->sweep_maxc};
+        const SweepPlan pb{jobs, part_b, s->sweep_chunk, s->sweep_maxc};
         HIP_TRY(ctx, hipMemsetAsync(s->d_info + 1, 0, 3 * sizeof(int32_t), ctx->stream));
         HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)s->tmp, 0x7FF8A5A5, 2 * (size_t)s->tmp_len, ctx->stream));
-        launch_sweep(false, grid, ctx->stream, A, lda, s->winv, rhs, s->tmp, n, s->d_info, ctx->d_res + MADQP_FAULT_SLOT, vec, pf);
+        launch_sweep(false, grid, ctx->stream, A, lda, s->winv, rhs, s->tmp, n, s->d_info, ctx->d_res + MADQP_FAULT_SLOT, vec, pf, kb);
         LAUNCH_CHECK(ctx);
         if (s->npos < n) {  // y <- diag(I, -I) y
             const int64_t len = n - s->npos;
@@ -2340,7 +2411,7 @@ extern "C" int32_t madqp_chol_solve(madqp_chol* s, double* rhs) {
             LAUNCH_CHECK(ctx);
         }
         HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)rhs, 0x7FF8A5A5, 2 * (size_t)n, ctx->stream));
-        launch_sweep(true, grid, ctx->stream, A, lda, s->winv, s->tmp, rhs, n, s->d_info, ctx->d_res + MADQP_FAULT_SLOT, vec, pb);
+        launch_sweep(true, grid, ctx->stream, A, lda, s->winv, s->tmp, rhs, n, s->d_info, ctx->d_res + MADQP_FAULT_SLOT, vec, pb, kb);
         LAUNCH_CHECK(ctx);
     }
     return MADQP_OK;

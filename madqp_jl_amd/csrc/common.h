@@ -231,6 +231,13 @@ struct madqp_chol {
     int64_t tmp_len;
     int32_t* d_jobs;  // sweep job list (chol.hip SweepPlan), nullptr when every block row is one job
     int32_t sweep_chunk, sweep_maxc, sweep_njobs;
+    // the sweeps under a bandwidth (madqp_chol_set_bandwidth; band_plan.inc): sweep_band = MADQP_SWEEP_BAND of this handle,
+    // sweep_kb = blocks a block row reads left of its diagonal block (-1: the dense sweeps), and the band's own job list
+    // where the dense sweeps have one
+    bool sweep_band;
+    int64_t sweep_kb;
+    int32_t* d_band_jobs;
+    int32_t band_njobs;
     int32_t* d_info;
     double* A;  // last factored matrix (borrowed)
     int64_t lda;

@@ -627,7 +627,8 @@ extern "C" int32_t madqp_kkt_set_bandwidth(madqp_kkt* k, int64_t bw) {
     int64_t extent = 0;
     const int32_t re = madqp_chol_band_extent(k->chol, &extent);
     if (re) return re;
-    // K once: from now on nothing writes beyond the extent, and the solves stream the whole lower triangle
+    // K once: from now on nothing writes beyond the extent.  No reader of these zeros is left -- the sweeps of a solve stay
+    // inside the extent too (chol.hip, band form; MADQP_SWEEP_BAND=0 alone still streams the whole lower triangle)
     const int64_t dpad = std::max<int64_t>(128, (order + 127) / 128 * 128);
     HIP_TRY(ctx, hipMemsetAsync(k->K, 0, ((size_t)k->ldk * dpad + 128) * sizeof(double), ctx->stream));
     k->bw = bw;

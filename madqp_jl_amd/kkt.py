@@ -47,9 +47,12 @@ class HIPCholeskySolver:
         self.be, self._kkt = backend, kkt_handle
         self.info = 0
         self.bandwidth = None
+        self.sweep_band_blocks = None  # 128-blocks a block row of the sweeps reads left of the diagonal; None: all (dense)
         if bandwidth is not None:
             backend.kkt_set_bandwidth(kkt_handle, int(bandwidth))
             self.bandwidth = int(bandwidth)
+            kb = backend.chol_sweep_info(backend.kkt_chol(kkt_handle)[0])[0]
+            self.sweep_band_blocks = kb if kb >= 0 else None
 
     def introduce(self) -> str:  # MadNLP.introduce, src/solver.jl:360
         if self.bandwidth is not None:

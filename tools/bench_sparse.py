@@ -131,6 +131,8 @@ def main():
                           "bandwidth": s.kkt.linear_solver.bandwidth, "ms_per_iteration": dt / max(r["iter"], 1) * 1e3,
                           "objective": r["objective"], "solve_seconds": dt, "generate_seconds": t_gen,
                           "factorizations": r["n_factorizations"], "band_w": os.environ.get("MADQP_CHOL_BAND_W"),
+                          "sweep_band": os.environ.get("MADQP_SWEEP_BAND"),
+                          "sweep_band_blocks": s.kkt.linear_solver.sweep_band_blocks,
                           "ms_per_factorization": {c: round(v[0] / nf, 2) for c, v in prof.items() if v[1]},
                           "last": r["trace"][-1]}))
         s.close()
