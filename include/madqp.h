@@ -276,7 +276,7 @@ int32_t madqp_chol_solve(madqp_chol* s, double* rhs);
 /* Band-limited schedule.  bw is the half-bandwidth of the matrices this handle factors: A[i,j] = 0 for i - j > bw.  A
  * Cholesky factor without pivoting stays inside the band, so with a bandwidth set madqp_chol_factor (every n) launches
  * the left-looking schedule's products, diagonal kernels and panel solves on band-limited ranges only.  The storage
- * stays dense and column-major.  0 <= bw < n sets it, bw = -1 clears it (the dense schedules, launch for launch as before
+ * stays dense and column-major (or packed: madqp_chol_set_packed below).  0 <= bw < n sets it, bw = -1 clears it (the dense schedules, launch for launch as before
  * the call); MADQP_ERR_ARG otherwise and on a handle with a signature npos < n.  With a bandwidth set,
  * madqp_chol_set_signature(npos < n), madqp_chol_factor_begin and madqp_chol_factor_panel are refused the same way.
  * CONTRACT.  The schedule works in 128-row tiles and 128-column k-ranges, so it reaches somewhat beyond the band:
@@ -296,6 +296,23 @@ int32_t madqp_chol_band_extent(madqp_chol* s, int64_t* extent_host);
  * diagonal block ((bw + 127) / 128 under a bandwidth; -1: all of them, the dense sweeps), out_host[1] the workgroups of
  * one sweep, out_host[2] the tiles per sweep job (MADQP_SWEEP_CHUNK).  MADQP_ERR_ARG for a NULL handle or NULL out_host. */
 int32_t madqp_chol_sweep_info(madqp_chol* s, int64_t* out_host);
+/* Packed band storage for a handle with a bandwidth set.  Entry (i, j) of the lower triangle lives at P[i + j ld] with
+ * ld >= extent (madqp_chol_band_extent) and ld far below n: LAPACK's lower band storage AB[(i - j) + j LDAB] with
+ * LDAB = ld + 1, seen as a column-major matrix of leading dimension LDAB - 1.  Two entries with 0 <= i - j <= extent never
+ * share an address; entries above the diagonal alias the tail of earlier columns and entries with i - j > ld the head of
+ * later ones -- the band path writes neither, and reads there only what it masks or drops.
+ * madqp_chol_packed_layout: out_host[0] = the leading dimension -- ld_in if positive (MADQP_ERR_ARG when it is below
+ * max(extent, 1)), else the library's choice: even, at least extent + 1 --, out_host[1] = the doubles the storage must
+ * hold, ceil128(n) (ld + 1) + 128 (whole-tile reads go up to the padded order in rows and columns).  MADQP_ERR_ARG
+ * without a bandwidth.  An even ld on 16-byte aligned storage keeps every launch the dense storage of a padded leading
+ * dimension gets (bitwise the same factor and solutions); an odd ld takes the scalar-load forms.
+ * madqp_chol_set_packed(s, 1): from now on the lda of madqp_chol_factor is such a leading dimension, checked as
+ * lda >= max(extent, 1) instead of lda >= n, and rows up to the padded order count as readable.  MADQP_ERR_ARG unless a
+ * bandwidth is set and the sweeps run in their band form (MADQP_SWEEP_BAND not 0: the dense sweeps read the whole
+ * triangle).  madqp_chol_set_bandwidth, with any value, turns packed off again (the extent changes); switching forgets
+ * the stored factor like that call does.  madqp_chol_solve needs nothing: it uses the matrix and lda of the last factor. */
+int32_t madqp_chol_packed_layout(madqp_chol* s, int64_t ld_in, int64_t* out_host);
+int32_t madqp_chol_set_packed(madqp_chol* s, int32_t on);
 
 /* y = alpha*op(A) x + beta*y ; A has `rows` rows of length `cols`, row r at A + r*lda.
  * trans=0: y(rows) = A x(cols);  trans=1: y(cols) = A' x(rows).
@@ -506,6 +523,26 @@ int32_t madqp_kkt_set_hcsr(madqp_kkt* kkt, const int64_t* h_ptr, const int64_t* 
  * MADQP_ERR_ARG: a dense Jacobian, a dense H, the augmented and K2.5 forms, bw outside [0, order), bw below the pattern's
  * bandwidth.  After this call madqp_kkt_set_hdiag and madqp_kkt_set_hcsr are refused. */
 int32_t madqp_kkt_set_bandwidth(madqp_kkt* kkt, int64_t bw);
+
+/* The sparse front end WITHOUT the order^2 allocation: madqp_kkt_create_sparse's arguments less H and ldh (H absent,
+ * diagonal through madqp_kkt_set_hdiag or CSR through madqp_kkt_set_hcsr), mode 0 or 1 only (MADQP_ERR_ARG otherwise).
+ * The object holds no K until madqp_kkt_set_bandwidth, which on such an object checks the pattern as above, forwards bw
+ * to the Cholesky handle, turns its packed form on (madqp_chol_set_packed) and allocates and zeroes the packed storage of
+ * madqp_chol_packed_layout(chol, 0) ONCE; a second madqp_kkt_set_bandwidth is refused (MADQP_ERR_STATE).  Before that
+ * call madqp_kkt_build, madqp_kkt_factorize, madqp_kkt_solve, madqp_kkt_matrix and the native driver (which calls them)
+ * return MADQP_ERR_STATE.  Afterwards every madqp_kkt_* call works as on the dense-storage band object, with the same
+ * bits inside the band; madqp_kkt_matrix returns the packed pointer and its leading dimension. */
+int32_t madqp_kkt_create_sparse_packed(madqp_ctx* ctx, int32_t mode, int64_t nx, int64_t m, int64_t ns,
+                                       const int64_t* ind_ineq_host, const int64_t* a_ptr, const int64_t* a_col,
+                                       const double* a_val, const int64_t* at_ptr, const int64_t* at_col,
+                                       const double* at_val, madqp_kkt** out);
+/* out_host[0] = 1 for packed band storage, 0 for dense; [1] = the leading dimension of K (0: packed, no bandwidth yet);
+ * [2] = the doubles allocated for K (0 likewise). */
+int32_t madqp_kkt_storage(madqp_kkt* kkt, int64_t* out_host);
+/* Packed band storage -> the lower triangle of a dense column-major matrix (inspection): D[i + j ldd] = P[i + j ld] for
+ * 0 <= i - j <= reach, 0 for i - j > reach, the upper triangle of D untouched.  reach <= ld, ldd >= n; asynchronous on
+ * the context's stream. */
+int32_t madqp_band_expand(madqp_ctx* ctx, int64_t n, const double* P, int64_t ld, int64_t reach, double* D, int64_t ldd);
 
 /* ----------------------------------------- callback buffers -> dense operands */
 /* MadNLP.SparseCallback hands the Jacobian / Hessian values as nnz-long buffers in the order of the model's COO

@@ -138,6 +138,8 @@ _SIGNATURES = {
     "madqp_chol_set_bandwidth": [vp, i64],
     "madqp_chol_band_extent": [vp, pi64],
     "madqp_chol_sweep_info": [vp, pi64],
+    "madqp_chol_packed_layout": [vp, i64, pi64],
+    "madqp_chol_set_packed": [vp, i32],
     "madqp_chol_factor": [vp, vp, i64, pi32],
     "madqp_chol_solve": [vp, vp],
     "madqp_gemv": [vp, i32, i64, i64, f64, vp, i64, vp, f64, vp],
@@ -188,6 +190,9 @@ _SIGNATURES = {
     "madqp_kkt_set_hdiag": [vp, vp],
     "madqp_kkt_set_hcsr": [vp, vp, vp, vp],
     "madqp_kkt_set_bandwidth": [vp, i64],
+    "madqp_kkt_create_sparse_packed": [vp, i32, i64, i64, i64, pi64, vp, vp, vp, vp, vp, vp, C.POINTER(vp)],
+    "madqp_kkt_storage": [vp, pi64],
+    "madqp_band_expand": [vp, i64, vp, i64, i64, vp, i64],
     "madqp_coo_map_create": [vp, i64, vp, vp, i64, i64, i32, C.POINTER(vp)],
     "madqp_coo_map_create_cols_cyclic": [vp, i64, vp, vp, i64, i64, i64, i32, i32, C.POINTER(vp)],
     "madqp_coo_map_create_tiles_cyclic": [vp, i64, vp, vp, i64, i64, i32, i32, i32, i32, C.POINTER(vp)],

@@ -175,6 +175,17 @@ class HipBackend:
         self._ck(self.lib.madqp_chol_sweep_info(h, out))
         return tuple(out)
 
+    def chol_packed_layout(self, h, ld=0):
+        """``(ld, doubles)`` of packed band storage for this handle's bandwidth: entry (i, j) at ``P[i + j * ld]``.  ``ld``
+        0: the library's choice (even, at least extent + 1); otherwise that one, refused below the extent."""
+        out = (C.c_int64 * 2)()
+        self._ck(self.lib.madqp_chol_packed_layout(h, int(ld), out))
+        return out[0], out[1]
+
+    def chol_set_packed(self, h, on=True):
+        """The ``lda`` of ``chol_factor`` is a packed leading dimension from here on (needs a bandwidth and the band sweeps)."""
+        self._ck(self.lib.madqp_chol_set_packed(h, 1 if on else 0))
+
     def chol_factor(self, h, A, lda) -> int:
         info = C.c_int32()
         self._ck(self.lib.madqp_chol_factor(h, ptr(A), lda, C.byref(info)))
@@ -333,6 +344,25 @@ class HipBackend:
                                                   ptr(csr.ptr), ptr(csr.col), ptr(csr.val), ptr(csr.t_ptr),
                                                   ptr(csr.t_col), ptr(t_val), C.byref(h)))
         return h
+
+    def kkt_create_sparse_packed(self, mode, nx, m, ind_ineq, csr, t_val):
+        """:meth:`kkt_create_sparse` without H and without any K: the band is allocated by :meth:`kkt_set_bandwidth`."""
+        h = C.c_void_p()
+        ineq = (C.c_int64 * max(1, len(ind_ineq)))(*[int(i) for i in ind_ineq])
+        self._ck(self.lib.madqp_kkt_create_sparse_packed(self.ctx, mode, nx, m, len(ind_ineq), ineq, ptr(csr.ptr),
+                                                         ptr(csr.col), ptr(csr.val), ptr(csr.t_ptr), ptr(csr.t_col),
+                                                         ptr(t_val), C.byref(h)))
+        return h
+
+    def kkt_storage(self, h):
+        """``(packed, ld, doubles)``: the storage of a KKT object's matrix."""
+        out = (C.c_int64 * 3)()
+        self._ck(self.lib.madqp_kkt_storage(h, out))
+        return bool(out[0]), out[1], out[2]
+
+    def band_expand(self, n, P, ld, reach, D, ldd):
+        """Packed band storage -> the lower triangle of the dense column-major ``D``; ``P``: a tensor or a device address."""
+        self._ck(self.lib.madqp_band_expand(self.ctx, n, P if isinstance(P, int) else ptr(P), ld, reach, ptr(D), ldd))
 
     def kkt_set_hdiag(self, h, hdiag):
         self._ck(self.lib.madqp_kkt_set_hdiag(h, ptr(hdiag)))

@@ -79,6 +79,9 @@ class BatchedMPCSolver:
         if self.opt.kkt_bandwidth is not None:
             raise ValueError("kkt_bandwidth: the batched engine factorises dense matrices (band-limited assembly and "
                              "Cholesky belong to MPCSolver's sparse front end)")
+        if self.opt.kkt_storage != "dense":
+            raise ValueError("kkt_storage: the batched engine factorises dense matrices (packed band storage belongs to "
+                             "MPCSolver's sparse front end)")
         self.normal = self.opt.kkt_system == "normal"
         q0 = self.qps[0]
         self.B, self.nx, self.m = len(self.qps), q0.nvar, q0.ncon

@@ -91,6 +91,32 @@ static int64_t band_plan(int64_t n, int64_t bw, int64_t slots, std::vector<BandO
     return extent;
 }
 
+// ---- packed band storage (madqp_chol_set_packed, madqp_chol_packed_layout) --------------------------------------------------
+// Entry (i, j) of the lower triangle at P[i + j ld] with ld >= extent: LAPACK's lower band storage AB[(i - j) + j LDAB],
+// LDAB = ld + 1, seen as a column-major matrix of leading dimension LDAB - 1 (what dpbtrf does to run dense kernels on band
+// storage), so every kernel of the band path runs on it with lda = ld.  Two entries with 0 <= i - j <= extent never share
+// an address ((j' - j)(ld + 1) - extent >= 1 for j' > j); an entry above the diagonal aliases the tail of earlier columns,
+// one with i - j > ld the head of later ones -- neither is written by the band path, and what a whole-tile read finds there
+// is masked or discarded.  Such reads go up to the padded order in rows AND columns, (npad - 1)(ld + 1) at most, and
+// never below (0, 0): npad (ld + 1) doubles hold them all, + 128 of slack for 16-byte loads at the edge as the dense K has.
+static int64_t band_packed_size(int64_t n, int64_t ld) { return band_up(std::max<int64_t>(n, 1)) * (ld + 1) + 128; }
+// The library's own leading dimension: even (16-byte loads of whole columns), at least extent + 1 (so that the entry
+// right above a diagonal entry, which the diagonal and sweep-image kernels load and drop, is no entry of the band), in
+// whole 16s.  pad: further doubles (measurements).  Columns a large power of two apart (extent = 2 047 -> ld = 2 048) were
+// expected to map badly onto the memory channels; measured at order 90 000 they do not -- pad 0 / 16 / 48 give 63.0 /
+// 63.4 / 63.1 ms per factorisation and 10.08 / 10.16 / 10.23 ms per pair of sweeps (DESIGN.md 3.4b) -- so the default adds none.
+constexpr int64_t BAND_PACKED_PAD = 0;
+static int64_t band_packed_ld(int64_t extent, int64_t pad = BAND_PACKED_PAD) { return (extent + 1 + 15) / 16 * 16 + pad; }
+// out[0] = the leading dimension (ld_in, or the library's choice for ld_in <= 0), out[1] = doubles of storage; false: ld_in
+// is below the extent
+static bool band_packed_layout(int64_t n, int64_t extent, int64_t ld_in, int64_t* out, int64_t pad = BAND_PACKED_PAD) {
+    const int64_t ld = ld_in > 0 ? ld_in : band_packed_ld(extent, pad);
+    if (ld < std::max<int64_t>(extent, 1)) return false;
+    out[0] = ld;
+    out[1] = band_packed_size(n, ld);
+    return true;
+}
+
 // ---- the triangular sweeps under a band (chol.hip, trsv_*_sweep_kernel) --------------------------------------------------
 // Block row r of the factor has nonzero tiles (r, j) for r - kb <= j < r only, kb = band_up(bw) / 128: a tile further left
 // holds entries with i - j >= (kb + 1) 128 - 127 > bw alone.  The sweeps read those tiles and the diagonal blocks, so the

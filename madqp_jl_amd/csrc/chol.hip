@@ -1690,6 +1690,7 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
     s->band_extent = n - 1;
     s->band_ops = nullptr;
     s->band_nops = 0;
+    s->packed = false;
     s->factored = false;
     s->A = nullptr;
     s->lda = 0;
@@ -1771,7 +1772,7 @@ extern "C" int32_t madqp_chol_destroy(madqp_chol* s) {
 // ---- band driver -------------------------------------------------------------------------------------------------------
 // A matrix with half-bandwidth bw (A[i,j] = 0 for i - j > bw) has a factor inside the same band, so the left-looking
 // schedule below runs its products, diagonal kernels and panel solves on band-limited ranges only: the plan of
-// band_plan.inc, built here once per bandwidth.  The storage stays dense.  The sweeps of madqp_chol_solve stay inside the
+// band_plan.inc, built here once per bandwidth.  The storage stays dense (or packed, below).  The sweeps of madqp_chol_solve stay inside the
 // band as well (MADQP_SWEEP_BAND, default 1): block row r streams the band_sweep_blocks(bw) tiles next to its diagonal
 // block, along a job list of its own where the dense sweeps have one.  bw = -1 clears the bandwidth (the dense schedules
 // and sweeps, launch for launch as without this call).
@@ -1784,6 +1785,7 @@ extern "C" int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw) {
     s->band_nops = 0;
     s->bw = bw;
     s->band_extent = s->n - 1;
+    s->packed = false;  // (the extent changes: packed storage is laid out for one extent -- madqp_chol_set_packed again)
     // the form of the sweeps changes with this call and what is stored may be the factor of another schedule: a solve
     // needs a new factorisation first (madqp_chol_solve refuses with MADQP_ERR_STATE until then)
     s->factored = false;
@@ -1851,6 +1853,32 @@ extern "C" int32_t madqp_chol_band_extent(madqp_chol* s, int64_t* extent_host) {
     return MADQP_OK;
 }
 
+// Packed band storage (band_plan.inc, "packed band storage"; include/madqp.h).  The kernels and launches of the band path
+// stay: only the leading dimension changes, and what `lda` has to cover.  The band sweeps are a condition -- the dense
+// sweeps stream the whole lower triangle.
+static int64_t packed_ld_pad() {  // MADQP_BAND_LD_PAD: doubles added to ceil16(extent + 1) (measurements)
+    const char* e = getenv("MADQP_BAND_LD_PAD");
+    return e ? std::max<int64_t>(0, atoll(e)) / 2 * 2 : BAND_PACKED_PAD;
+}
+extern "C" int32_t madqp_chol_packed_layout(madqp_chol* s, int64_t ld_in, int64_t* out_host) {
+    if (!s) return MADQP_ERR_ARG;
+    ARG_TRY(s->ctx, out_host != nullptr && s->bw >= 0);
+    if (!band_packed_layout(s->n, s->band_extent, ld_in, out_host, packed_ld_pad()))
+        return madqp_fail(s->ctx, MADQP_ERR_ARG, "madqp_chol_packed_layout: ld = %lld is below the extent %lld", (long long)ld_in,
+                          (long long)s->band_extent);
+    return MADQP_OK;
+}
+extern "C" int32_t madqp_chol_set_packed(madqp_chol* s, int32_t on) {
+    if (!s) return MADQP_ERR_ARG;
+    ARG_TRY(s->ctx, !on || (s->bw >= 0 && s->sweep_kb >= 0 && s->npos == s->n));
+    if (s->packed != (on != 0)) {  // what is stored was factored in the other layout
+        s->factored = false;
+        s->A = nullptr;
+    }
+    s->packed = on != 0;
+    return MADQP_OK;
+}
+
 // Width (multiple of 128, 768..2560; up to 2048: +5 ms per iteration at C-main) of the next outer panel: the wide update GEMM runs
 // (rows/128) x (W/128) tiles of equal cost on `slots` resident workgroups, so W is chosen to
 // make the last round of tiles as full as possible (tail quantisation is the main loss of a
@@ -1875,10 +1903,11 @@ struct CholTarget {
     const int32_t* skip = nullptr;
     const int32_t* list = nullptr;  // compacted form (GemmBatch::list)
     const int32_t* count = nullptr;
+    bool packed = false;  // packed band storage: lda >= the band's extent, rows up to the padded order exist (band_packed_size)
     int64_t npad() const { return (n + NB - 1) / NB * NB; }
     // rows up to the padded order may be read when the leading dimension covers them (the KKT
-    // object allocates K that way): no partial tiles, stores stay masked
-    bool padded() const { return lda >= npad(); }
+    // object allocates K that way) or the storage is packed: no partial tiles, stores stay masked
+    bool padded() const { return packed || lda >= npad(); }
 };
 // a product of the factorisation on target t: operand Y and addend Cin of problem b at strides sY, sCin (X, C: t.sA)
 static int32_t target_gemm(const CholTarget& t, const GemmArgs& g, int cls, int64_t sY, int64_t sCin) {
@@ -2036,7 +2065,9 @@ static int32_t factor_range(const CholTarget& t, int64_t j0, int64_t w) {
 }
 // the one matrix of a handle as a target
 static CholTarget chol_target(madqp_chol* s, double* A, int64_t lda) {
-    return CholTarget{s->ctx, A, lda, s->n, s->winv, s->d_info, chol_lite()};
+    CholTarget t{s->ctx, A, lda, s->n, s->winv, s->d_info, chol_lite()};
+    t.packed = s->packed;
+    return t;
 }
 
 // ---- mid-size schedule: which trailing columns a block step visits (round 4) ---------------------------------------
@@ -2225,7 +2256,7 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
 extern "C" int32_t madqp_chol_factor(madqp_chol* s, double* A, int64_t lda, int32_t* info_host) {
     if (!s) return MADQP_ERR_ARG;
     madqp_ctx* ctx = s->ctx;
-    ARG_TRY(ctx, A && info_host && lda >= s->n);
+    ARG_TRY(ctx, A && info_host && lda >= (s->packed ? std::max<int64_t>(s->band_extent, 1) : s->n));
     s->factored = false;
     s->A = A;
     s->lda = lda;
@@ -2255,7 +2286,7 @@ __global__ void info_to_slot_kernel(const int32_t* __restrict__ info, double* __
 int32_t madqp_chol_factor_q(madqp_chol* s, double* A, int64_t lda, double* d_slot) {
     if (!s) return MADQP_ERR_ARG;
     madqp_ctx* ctx = s->ctx;
-    ARG_TRY(ctx, A && d_slot && lda >= s->n);
+    ARG_TRY(ctx, A && d_slot && lda >= (s->packed ? std::max<int64_t>(s->band_extent, 1) : s->n));
     s->A = A;
     s->lda = lda;
     s->factored = true;

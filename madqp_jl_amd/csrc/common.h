@@ -260,4 +260,6 @@ struct madqp_chol {
     // band schedule (madqp_chol_set_bandwidth): half-bandwidth (-1: none), the plan of band_plan.inc and its extent
     int64_t bw, band_extent, band_nops;
     struct BandOp* band_ops;
+    // packed band storage (madqp_chol_set_packed): the lda of a factorisation is the packed leading dimension (>= extent)
+    bool packed;
 };

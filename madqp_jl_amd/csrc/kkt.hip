@@ -82,6 +82,10 @@ struct madqp_kkt {
     // band-limited assembly and factorisation (madqp_kkt_set_bandwidth): half-bandwidth of K (-1: none) and the rows below
     // the diagonal the factorisation reaches (madqp_chol_band_extent), which every build rewrites
     int64_t bw, band_extent;
+    // packed band storage (madqp_kkt_create_sparse_packed): no K until madqp_kkt_set_bandwidth allocates the band alone --
+    // entry (i, j) at K[i + j ldk], ldk >= band_extent (band_plan.inc); k_doubles: what K holds, either form
+    bool packed;
+    int64_t k_doubles;
 };
 
 namespace {
@@ -441,7 +445,7 @@ extern "C" int32_t madqp_kkt_destroy(madqp_kkt* k) {
 static int32_t kkt_create_common(madqp_ctx* ctx, int mode, int64_t nx, int64_t m, int64_t ns,
                                  const int64_t* ind_ineq_host, const double* H, int64_t ldh,
                                  const double* A, int64_t lda, const double* At, int64_t ldat,
-                                 madqp_kkt** out) {
+                                 madqp_kkt** out, bool packed = false) {
     ARG_TRY(ctx, out && nx >= 0 && m >= 0 && ns >= 0 && ns <= m);
     ARG_TRY(ctx, ns == 0 || ind_ineq_host);
     *out = nullptr;
@@ -482,8 +486,15 @@ static int32_t kkt_create_common(madqp_ctx* ctx, int mode, int64_t nx, int64_t m
     const size_t mb = (size_t)std::max<int64_t>(m, 1) * sizeof(double);
     const size_t nb = (size_t)std::max<int64_t>(n, 1) * sizeof(double);
     // +128 doubles of slack after the last column (room for 16-byte tile loads at the edge)
-    hipError_t e = hipMalloc(&k->K, ((size_t)k->ldk * dpad + 128) * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(k->K, 0, ((size_t)k->ldk * dpad + 128) * sizeof(double));
+    hipError_t e = hipSuccess;
+    k->packed = packed;
+    if (packed) {  // the band alone, once its extent is known (madqp_kkt_set_bandwidth)
+        k->ldk = 0;
+    } else {
+        k->k_doubles = k->ldk * dpad + 128;
+        e = hipMalloc(&k->K, (size_t)k->k_doubles * sizeof(double));
+        if (e == hipSuccess) e = hipMemset(k->K, 0, (size_t)k->k_doubles * sizeof(double));
+    }
     if (e == hipSuccess) e = hipMalloc(&k->d_ind_ineq, (size_t)std::max<int64_t>(ns, 1) * sizeof(int64_t));
     if (e == hipSuccess) e = hipMalloc(&k->d_slot, (size_t)std::max<int64_t>(m, 1) * sizeof(int64_t));
     if (e == hipSuccess) e = hipMalloc(&k->theta, mb);
@@ -546,6 +557,34 @@ extern "C" int32_t madqp_kkt_create_sparse(madqp_ctx* ctx, int32_t mode, int64_t
     return MADQP_OK;
 }
 
+// The same object on PACKED band storage: no dense H (NULL, diagonal or CSR as above), mode 0 or 1, and no K at all until
+// madqp_kkt_set_bandwidth -- which such an object needs before anything is built, factorised or solved (MADQP_ERR_STATE
+// until then) -- allocates the band: npad (ld + 1) + 128 doubles instead of the ldk x dpad of the dense storage.
+extern "C" int32_t madqp_kkt_create_sparse_packed(madqp_ctx* ctx, int32_t mode, int64_t nx, int64_t m, int64_t ns,
+                                                  const int64_t* ind_ineq_host, const int64_t* a_ptr, const int64_t* a_col,
+                                                  const double* a_val, const int64_t* at_ptr, const int64_t* at_col,
+                                                  const double* at_val, madqp_kkt** out) {
+    if (!ctx) return MADQP_ERR_ARG;
+    ARG_TRY(ctx, (mode == 0 || mode == 1) && a_ptr && at_ptr);
+    int32_t r = kkt_create_common(ctx, mode == 1 ? KKT_NORMAL : KKT_CONDENSED, nx, m, ns, ind_ineq_host, nullptr, 0, nullptr, 0,
+                                  nullptr, 0, out, /*packed=*/true);
+    if (r) return r;
+    madqp_kkt* k = *out;
+    k->a_ptr = a_ptr;
+    k->a_col = a_col;
+    k->a_val = a_val;
+    k->at_ptr = at_ptr;
+    k->at_col = at_col;
+    k->at_val = at_val;
+    return MADQP_OK;
+}
+// a packed object has no storage before its bandwidth is set
+static int32_t kkt_storage_ready(madqp_kkt* k, const char* what) {
+    if (k->packed && !k->K)
+        return madqp_fail(k->ctx, MADQP_ERR_STATE, "%s: a packed KKT object has no storage before madqp_kkt_set_bandwidth", what);
+    return MADQP_OK;
+}
+
 // Diagonal Hessian H = diag(hdiag) (nx entries, device, borrowed) for a KKT object created without a dense
 // H: the condensed matrix becomes diag(hdiag) + Sigma_x + A' Theta A, the normal equations A (H + Sigma)^-1 A'
 // ("the alternative of row 6 applies verbatim with Sigma -> H + Sigma") -- the reference's
@@ -602,6 +641,8 @@ extern "C" int32_t madqp_kkt_set_bandwidth(madqp_kkt* k, int64_t bw) {
     ARG_TRY(ctx, k->a_ptr && !k->H && (k->mode == KKT_CONDENSED || k->mode == KKT_NORMAL) && !k->scaled);
     const int64_t order = (k->mode == KKT_NORMAL) ? k->m : k->nx;
     ARG_TRY(ctx, bw >= 0 && bw < order);
+    if (k->packed && k->K)
+        return madqp_fail(ctx, MADQP_ERR_STATE, "madqp_kkt_set_bandwidth: the packed storage of this object is laid out already");
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<int64_t> ptr, col;
     int64_t pattern = 0;
@@ -627,6 +668,30 @@ extern "C" int32_t madqp_kkt_set_bandwidth(madqp_kkt* k, int64_t bw) {
     int64_t extent = 0;
     const int32_t re = madqp_chol_band_extent(k->chol, &extent);
     if (re) return re;
+    if (k->packed) {  // the band alone, zeroed once: every build rewrites the rows j .. j + extent of every column
+        int64_t lay[2] = {0, 0};
+        int32_t rp = madqp_chol_packed_layout(k->chol, 0, lay);
+        if (!rp) rp = madqp_chol_set_packed(k->chol, 1);
+        if (rp) {
+            (void)madqp_chol_set_bandwidth(k->chol, -1);
+            return rp;
+        }
+        hipError_t e = hipMalloc(&k->K, (size_t)lay[1] * sizeof(double));
+        if (e == hipSuccess) e = hipMemset(k->K, 0, (size_t)lay[1] * sizeof(double));
+        if (e != hipSuccess) {
+            if (k->K) (void)hipFree(k->K);
+            k->K = nullptr;
+            (void)hipGetLastError();
+            (void)madqp_chol_set_bandwidth(k->chol, -1);
+            return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_kkt_set_bandwidth: %lld doubles of packed storage: %s",
+                              (long long)lay[1], hipGetErrorString(e));
+        }
+        k->ldk = lay[0];
+        k->k_doubles = lay[1];
+        k->bw = bw;
+        k->band_extent = extent;
+        return MADQP_OK;
+    }
     // K once: from now on nothing writes beyond the extent.  No reader of these zeros is left -- the sweeps of a solve stay
     // inside the extent too (chol.hip, band form; MADQP_SWEEP_BAND=0 alone still streams the whole lower triangle)
     const int64_t dpad = std::max<int64_t>(128, (order + 127) / 128 * 128);
@@ -692,6 +757,7 @@ int32_t madqp_syrk_assemble_ranges(madqp_ctx* ctx, int64_t n, int64_t kdim, cons
 static int32_t kkt_build_impl(madqp_kkt* k, const madqp_state* st, int64_t nranges, const int64_t* ranges) {
     int32_t r = check_kkt_state(k, st);
     if (r) return r;
+    if ((r = kkt_storage_ready(k, "madqp_kkt_build"))) return r;
     madqp_ctx* ctx = k->ctx;
     if (k->mode == KKT_NORMAL) {
         // S = A diag(D_x) A' + diag(D_s on inequality rows),  D = 1/Sigma; du_diag is NOT added
@@ -800,12 +866,14 @@ extern "C" int32_t madqp_kkt_chol(madqp_kkt* k, madqp_chol** chol, int64_t* orde
 
 extern "C" int32_t madqp_kkt_factorize(madqp_kkt* k, int32_t* info_host) {
     if (!k) return MADQP_ERR_ARG;
+    if (int32_t r = kkt_storage_ready(k, "madqp_kkt_factorize")) return r;
     return madqp_chol_factor(k->chol, k->K, k->ldk, info_host);
 }
 // queued form: the factorisation is enqueued, its info lands in the result block; madqp_kkt_factor_result hands the
 // value the caller read back to the solver object
 int32_t madqp_q_kkt_factorize(madqp_kkt* k, int slot0) {
     if (!k) return MADQP_ERR_ARG;
+    if (int32_t r = kkt_storage_ready(k, "madqp_kkt_factorize")) return r;
     return madqp_chol_factor_q(k->chol, k->K, k->ldk, k->ctx->d_res + slot0);
 }
 int32_t madqp_kkt_factor_result(madqp_kkt* k, int32_t info) {
@@ -857,6 +925,7 @@ static int32_t ensure_pos(madqp_kkt* k, const madqp_state* st) {
 int32_t madqp_kkt_solve_from(madqp_kkt* k, const madqp_state* st, const double* p, double* w, double* pcopy) {
     int32_t r = check_kkt_state(k, st);
     if (r) return r;
+    if ((r = kkt_storage_ready(k, "madqp_kkt_solve"))) return r;
     madqp_ctx* ctx = k->ctx;
     ARG_TRY(ctx, p && w && p != w);
     const int64_t len = st->n + st->m + st->nlb + st->nub;
@@ -905,6 +974,7 @@ extern "C" int32_t madqp_kkt_set_refine(madqp_kkt* k, int32_t steps) {
 extern "C" int32_t madqp_kkt_solve(madqp_kkt* k, const madqp_state* st, double* w) {
     int32_t r = check_kkt_state(k, st);
     if (r) return r;
+    if ((r = kkt_storage_ready(k, "madqp_kkt_solve"))) return r;
     ARG_TRY(k->ctx, w != nullptr);
     if (k->refine <= 0) return kkt_solve_once(k, st, w);
     madqp_ctx* ctx = k->ctx;
@@ -1130,7 +1200,40 @@ madqp_ctx* madqp_kkt_ctx(madqp_kkt* kkt) { return kkt->ctx; }
 
 extern "C" int32_t madqp_kkt_matrix(madqp_kkt* k, double** K, int64_t* ld) {
     if (!k || !K || !ld) return MADQP_ERR_ARG;
+    if (int32_t r = kkt_storage_ready(k, "madqp_kkt_matrix")) return r;
     *K = k->K;
     *ld = k->ldk;
+    return MADQP_OK;
+}
+
+// [0] packed 0 / 1, [1] the leading dimension of K (0: a packed object whose bandwidth is not set), [2] doubles allocated
+extern "C" int32_t madqp_kkt_storage(madqp_kkt* k, int64_t* out_host) {
+    if (!k || !out_host) return MADQP_ERR_ARG;
+    out_host[0] = k->packed ? 1 : 0;
+    out_host[1] = k->ldk;
+    out_host[2] = k->K ? k->k_doubles : 0;
+    return MADQP_OK;
+}
+
+// Packed band storage -> the lower triangle of a dense column-major matrix, for hosts that want to look at K: entry (i, j),
+// i >= j, becomes P[i + j ld] where i - j <= reach and 0 beyond; the upper triangle of D is left alone.  One thread per
+// row of a column (coalesced along the column), columns in a grid-stride loop.
+namespace {
+__global__ __launch_bounds__(256) void band_expand_kernel(int64_t n, const double* __restrict__ P, int64_t ld, int64_t reach,
+                                                          double* __restrict__ D, int64_t ldd) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    for (int64_t j = blockIdx.y; j <= i; j += gridDim.y) D[i + j * ldd] = (i - j <= reach) ? P[i + j * ld] : 0.0;
+}
+}  // namespace
+extern "C" int32_t madqp_band_expand(madqp_ctx* ctx, int64_t n, const double* P, int64_t ld, int64_t reach, double* D,
+                                     int64_t ldd) {
+    if (!ctx) return MADQP_ERR_ARG;
+    ARG_TRY(ctx, n >= 0 && reach >= 0 && ld >= 1 && reach <= ld && (n == 0 || (P && D && ldd >= n)));
+    if (n == 0) return MADQP_OK;
+    ProfScope ps(ctx, MADQP_PROF_VEC);
+    hipLaunchKernelGGL(band_expand_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)std::min<int64_t>(n, 4096)), dim3(256), 0,
+                       ctx->stream, n, P, ld, reach, D, ldd);
+    LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }

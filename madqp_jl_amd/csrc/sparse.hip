@@ -139,7 +139,8 @@ int32_t madqp_sparse_gram_band(madqp_ctx* ctx, int64_t n, const int64_t* rowptr,
                                const double* dvec, const int64_t* b_ptr, const int64_t* b_col, const double* b_val,
                                double* C, int64_t ldc, int64_t bw, int64_t extent) {
     if (n == 0) return MADQP_OK;
-    ARG_TRY(ctx, rowptr && t_ptr && w && C && ldc >= n && bw >= 0 && bw <= extent && extent < n);
+    // (ldc >= n: dense storage; packed band storage has ldc >= extent alone -- the kernel writes the rows j .. j + extent of column j)
+    ARG_TRY(ctx, rowptr && t_ptr && w && C && ldc >= std::max<int64_t>(extent, 1) && bw >= 0 && bw <= extent && extent < n);
     ProfScope ps(ctx, MADQP_PROF_SYRK);
     hipLaunchKernelGGL(sparse_gram_band_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, n, rowptr, col, val, t_ptr,
                        t_col, t_val, w, dvec, b_ptr, b_col, b_val, C, ldc, bw, extent);

@@ -37,6 +37,23 @@ def pattern_bandwidth(A, H=None, form="condensed") -> int:
     return bw
 
 
+KKT_STORAGES = ("dense", "packed")
+
+
+def check_storage(storage, bandwidth, band_form="condensed", H=None):
+    """The refusals of ``storage=`` / ``kkt_storage``, before any device call: packed storage is laid out for one
+    bandwidth, which the object therefore needs at construction, on the forms that take one."""
+    if storage not in KKT_STORAGES:
+        raise ValueError(f"storage: one of {KKT_STORAGES}, not {storage!r}")
+    if storage == "packed":
+        if bandwidth is None:
+            raise ValueError("storage='packed' needs a bandwidth at construction: the object never allocates the dense K")
+        if band_form is None:
+            raise ValueError("storage='packed' is taken by the sparse condensed and normal KKT systems only")
+        if H is not None and not isinstance(H, DeviceSymCSR) and H.dim() == 2:
+            raise ValueError("storage='packed' needs a sparse (DeviceSymCSR), diagonal or absent Hessian, not a dense one")
+
+
 class HIPCholeskySolver:
     """AbstractLinearSolver contract: ctor keeps the matrix it re-reads at every
     ``factorize`` (src/KKT/normalkkt.jl:99-101); ``solve`` is in place (:196)."""
@@ -274,9 +291,12 @@ class _SparseMixin:
     """The Jacobian stays sparse (``DeviceCSR``), the factorised matrix stays dense (SURVEY.md 8f rank 1;
     reference: src/utils.jl:148-298, src/KKT/normalkkt.jl:51-101)."""
 
-    def _init_sparse(self, backend, st, nx, ind_ineq, H, csr, mode):
+    def _init_sparse(self, backend, st, nx, ind_ineq, H, csr, mode, bandwidth=None, storage="dense"):
         """``H``: None, a dense (nx, nx) tensor (condensed or augmented mode), a 1-D tensor = diagonal of H (any mode)
-        or a :class:`DeviceSymCSR` (condensed or augmented mode; kept alive here, the library borrows its arrays)."""
+        or a :class:`DeviceSymCSR` (condensed or augmented mode; kept alive here, the library borrows its arrays).
+        ``bandwidth`` (int or "auto"): :meth:`set_bandwidth` at construction.  ``storage="packed"``: the object never
+        allocates the dense K -- the band alone, laid out for that bandwidth (``madqp_kkt_create_sparse_packed``)."""
+        check_storage(storage, bandwidth, self._band_form, H)
         self.be, self.st = backend, st
         self.nx, self.m = int(nx), st.m
         self.ind_ineq = [int(i) for i in ind_ineq]
@@ -286,8 +306,12 @@ class _SparseMixin:
         self._t_val = csr.t_val  # values of A' in CSR order, borrowed by the library
         hcsr = isinstance(H, DeviceSymCSR)
         diag = H is not None and not hcsr and H.dim() == 1
-        self._h = backend.kkt_create_sparse(mode, self.nx, self.m, self.ind_ineq, None if diag or hcsr else H,
-                                            max(self.nx, 1), csr, self._t_val)
+        self.storage = storage
+        if storage == "packed":
+            self._h = backend.kkt_create_sparse_packed(mode, self.nx, self.m, self.ind_ineq, csr, self._t_val)
+        else:
+            self._h = backend.kkt_create_sparse(mode, self.nx, self.m, self.ind_ineq, None if diag or hcsr else H,
+                                                max(self.nx, 1), csr, self._t_val)
         if hcsr:
             assert H.n == self.nx
             backend.kkt_set_hcsr(self._h, H)
@@ -296,6 +320,22 @@ class _SparseMixin:
             backend.kkt_set_hdiag(self._h, H)
         self.linear_solver = HIPCholeskySolver(backend, self._h)
         self.n_factorizations = 0
+        if bandwidth is not None:
+            self.set_bandwidth(bandwidth)
+
+    def dense_matrix(self):
+        """The lower triangle of the stored K (assembled, or factored after a factorisation) as a dense host array of the
+        matrix's order, zeros above the diagonal -- from either storage (packed: ``madqp_band_expand`` over the extent).
+        Allocates order^2 doubles on the device: inspection and tests, not the large problems packed storage is for."""
+        import torch
+
+        ch, order = self.be.kkt_chol(self._h)
+        p, ld = self.be.kkt_matrix(self._h, order)
+        if not self.be.kkt_storage(self._h)[0]:
+            return np.tril(self.be.read_doubles(p, ld * order).reshape(order, ld)[:, :order].T)
+        D = torch.zeros((order, max(order, 1)), dtype=torch.float64, device=self.be.device)
+        self.be.band_expand(order, p, ld, min(self.be.chol_band_extent(ch), ld), D, max(order, 1))
+        return D.cpu().numpy().T.copy()
 
     _band_form = None  # "condensed" / "normal" on the classes that take a bandwidth
 
@@ -318,10 +358,10 @@ class _SparseMixin:
 class HIPSparseCondensedKKTSystem(_SparseMixin, HIPCondensedKKTSystem):
     _band_form = "condensed"
 
-    def __init__(self, backend, st, nx, ind_ineq, H, csr):
+    def __init__(self, backend, st, nx, ind_ineq, H, csr, bandwidth=None, storage="dense"):
         if H is not None and not isinstance(H, DeviceSymCSR) and H.dim() == 2:
             assert H.is_contiguous() and H.shape == (nx, nx)
-        self._init_sparse(backend, st, nx, ind_ineq, H, csr, 0)
+        self._init_sparse(backend, st, nx, ind_ineq, H, csr, 0, bandwidth, storage)
 
 
 class HIPSparseNormalKKTSystem(_SparseMixin, HIPNormalKKTSystem):
@@ -329,11 +369,11 @@ class HIPSparseNormalKKTSystem(_SparseMixin, HIPNormalKKTSystem):
     (1-D tensor; SURVEY.md 8a-note -- what CONT-type QPs need)."""
     _band_form = "normal"
 
-    def __init__(self, backend, st, nx, ind_ineq, H, csr):
+    def __init__(self, backend, st, nx, ind_ineq, H, csr, bandwidth=None, storage="dense"):
         if H is not None and (isinstance(H, DeviceSymCSR) or H.dim() != 1):
             raise ValueError("The KKT system NormalKKTSystem supports only linear programs "
                              "(or a diagonal Hessian given as a vector).")  # normalkkt.jl:45-48
-        self._init_sparse(backend, st, nx, ind_ineq, H, csr, 1)
+        self._init_sparse(backend, st, nx, ind_ineq, H, csr, 1, bandwidth, storage)
 
 
 class HIPSparseAugmentedKKTSystem(_SparseMixin, HIPAugmentedKKTSystem):

@@ -66,6 +66,12 @@ class IPMOptions:
         # bw + 1 <= order / 4 (KKT_BAND_AUTO_FRACTION), dense otherwise.  An int: that half-bandwidth (the library checks
         # it against the pattern).  Refused for the dense front end, a dense H, the augmented forms, a grid and batches.
         kkt_bandwidth=None,
+        # extension: where the band path keeps K.  "dense" (default): column-major of the padded order, as without the
+        # option.  "packed": the band alone, entry (i, j) at K[i + j ld] with ld just above the extent of the band schedule
+        # (madqp_chol_packed_layout) -- the order^2 doubles are never allocated; same kernels, launches and bits.  Needs
+        # kkt_bandwidth; with kkt_bandwidth="auto" on a model whose band the rule declines, storage falls back to dense
+        # together with the schedule.
+        kkt_storage="dense",
     )
     KKT_BAND_AUTO_FRACTION = 4
 

@@ -19,7 +19,7 @@ import torch
 
 from ._lib import CMpcInfo, CMpcOptions
 from .kkt import (HIPAugmentedKKTSystem, HIPCondensedKKTSystem, HIPNormalKKTSystem, HIPScaledAugmentedKKTSystem,
-                  HIPSparseAugmentedKKTSystem, HIPSparseCondensedKKTSystem, HIPSparseNormalKKTSystem, pattern_bandwidth)
+                  HIPSparseAugmentedKKTSystem, HIPSparseCondensedKKTSystem, HIPSparseNormalKKTSystem, KKT_STORAGES, pattern_bandwidth)
 from .options import (AdaptiveRegularization, AdaptiveStep, ConservativeStep, FixedRegularization,
                       IPMOptions, MehrotraAdaptiveStep, NoRegularization)
 from .qp import DeviceCSR, DeviceQP, DeviceSymCSR
@@ -131,6 +131,10 @@ class MPCSolver:
                                  "ordering; use kkt_system='condensed' or 'normal'")
             if torch.is_tensor(qp.H) and qp.H.dim() == 2:
                 raise ValueError("kkt_bandwidth needs a sparse (DeviceSymCSR), diagonal or absent Hessian, not a dense one")
+        if self.opt.kkt_storage not in KKT_STORAGES:
+            raise ValueError(f"kkt_storage: one of {KKT_STORAGES}, not {self.opt.kkt_storage!r}")
+        if self.opt.kkt_storage == "packed" and bwo is None:
+            raise ValueError("kkt_storage='packed' needs kkt_bandwidth: packed band storage is laid out for one bandwidth")
         self.full_qp, self._fixed = qp, None
         if fvt == "make_parameter":
             self._fixed = qp.eliminate_fixed()
@@ -387,15 +391,16 @@ class MPCSolver:
         if isinstance(self.A, DeviceCSR):  # sparse front end: dense K / Cholesky, CSR products
             cls = {"normal": HIPSparseNormalKKTSystem, "augmented": HIPSparseAugmentedKKTSystem,
                    "condensed": HIPSparseCondensedKKTSystem}[opt.kkt_system]
-            kkt = cls(be, st, nx, self.ind_ineq, self.H, self.A)
-            if opt.kkt_bandwidth is not None:
-                bw, order = opt.kkt_bandwidth, (self.m if opt.kkt_system == "normal" else nx)
-                if bw == "auto":  # only where the band is narrow: the dense schedules are the better ones otherwise
-                    bw = pattern_bandwidth(self.A, self.H, opt.kkt_system)
-                    if (bw + 1) * IPMOptions.KKT_BAND_AUTO_FRACTION > order:
-                        bw = None
-                if bw is not None:
-                    kkt.set_bandwidth(bw)
+            bw = opt.kkt_bandwidth
+            if bw == "auto":  # only where the band is narrow: the dense schedules are the better ones otherwise
+                bw, order = pattern_bandwidth(self.A, self.H, opt.kkt_system), (self.m if opt.kkt_system == "normal" else nx)
+                if (bw + 1) * IPMOptions.KKT_BAND_AUTO_FRACTION > order:
+                    bw = None
+            if bw is not None and opt.kkt_storage == "packed":  # the band alone: such an object never allocates the dense K
+                return cls(be, st, nx, self.ind_ineq, self.H, self.A, bandwidth=bw, storage="packed")
+            kkt = cls(be, st, nx, self.ind_ineq, self.H, self.A)  # (storage falls back to dense with the schedule)
+            if bw is not None:
+                kkt.set_bandwidth(bw)
             return kkt
         if opt.kkt_system == "augmented":
             return HIPAugmentedKKTSystem(be, st, nx, self.ind_ineq, self.H, self.A)

@@ -37,7 +37,7 @@ def bench_hessian_forms(a, be):
     else:
         form, h_bytes = "dense", qp.H.numel() * qp.H.element_size()
     kw = {} if a.kkt == "augmented" else dict(regularization=M.FixedRegularization(1e-8, 0.0 if a.kkt == "normal" else -1e-8))
-    s = M.MPCSolver(qp, be, kkt_system=a.kkt, driver="native", max_iter=300, kkt_bandwidth=a.bandwidth, **kw)
+    s = M.MPCSolver(qp, be, kkt_system=a.kkt, driver="native", max_iter=300, kkt_bandwidth=a.bandwidth, kkt_storage=a.storage, **kw)
 
     def window(steps):  # the first iterations of a fresh solve (the problem converges in a handful): the same ones every time
         s.initialize()
@@ -94,7 +94,11 @@ def main():
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--bandwidth", type=bandwidth_arg, default=None, metavar="{auto,INT}",
                    help="band-limited assembly and Cholesky (kkt_bandwidth); needs a sparse, diagonal or absent Hessian")
+    p.add_argument("--storage", choices=("dense", "packed"), default="dense",
+                   help="where the band path keeps K (kkt_storage): packed = the band alone; needs --bandwidth")
     a = p.parse_args()
+    if a.storage == "packed" and a.bandwidth is None:
+        p.error("--storage packed needs --bandwidth")
     import torch
 
     import madqp_jl_amd as M
@@ -110,7 +114,7 @@ def main():
         qp = P.to_device(h, be)
         t_gen = time.perf_counter() - t0
         s = M.MPCSolver(qp, be, kkt_system="normal", regularization=M.FixedRegularization(1e-8, 0.0), driver="native",
-                        max_iter=100, kkt_bandwidth=a.bandwidth)
+                        max_iter=100, kkt_bandwidth=a.bandwidth, kkt_storage=a.storage)
         # two whole solves of the same problem: the first without the device timers (time per iteration), the second
         # with them (the per-class split; a timer scope per launch costs host time the first window must not carry)
         torch.cuda.synchronize()
@@ -125,10 +129,20 @@ def main():
         prof = be.prof_get()
         be.prof_enable(())
         assert r2["iter"] == r["iter"]
+        # the set-up both solves carry, once more on its own: a new KKT object (its storage allocated and zeroed), scaling,
+        # starting point; and what the device holds then (the library allocates K beside torch's allocator)
+        t0 = time.perf_counter()
+        s.initialize()
+        torch.cuda.synchronize()
+        t_setup = time.perf_counter() - t0
+        free, total = torch.cuda.mem_get_info()
         nf = max(r["n_factorizations"], 1)
         print(json.dumps({"workload": f"boundary-control QP N={a.cont}: nx={h.nvar} m={h.ncon} nnz={h.nnzj}, diagonal H, "
                                       "normal equations (m x m dense)", "status": r["status"], "iterations": r["iter"],
                           "bandwidth": s.kkt.linear_solver.bandwidth, "ms_per_iteration": dt / max(r["iter"], 1) * 1e3,
+                          "storage": dict(zip(("packed", "ld", "doubles"), be.kkt_storage(s.kkt._h))),
+                          "setup_seconds": t_setup, "device_bytes_in_use": total - free,
+                          "ld_pad": os.environ.get("MADQP_BAND_LD_PAD"),
                           "objective": r["objective"], "solve_seconds": dt, "generate_seconds": t_gen,
                           "factorizations": r["n_factorizations"], "band_w": os.environ.get("MADQP_CHOL_BAND_W"),
                           "sweep_band": os.environ.get("MADQP_SWEEP_BAND"),
@@ -153,7 +167,7 @@ def main():
         be.gen_wigner(M.stream_key(11, 2), n, 1.0 / np.sqrt(n), H)
     qp = M.DeviceQP(H, q, csr, z(n, 0.0), z(n, 1.0), z(m, 0.0), z(m, 1.0), z(n, 0.0))
     reg = M.FixedRegularization(1e-8, 0.0 if a.kkt == "normal" else -1e-8)
-    s = M.MPCSolver(qp, be, kkt_system=a.kkt, regularization=reg, driver="native", max_iter=300, kkt_bandwidth=a.bandwidth)
+    s = M.MPCSolver(qp, be, kkt_system=a.kkt, regularization=reg, driver="native", max_iter=300, kkt_bandwidth=a.bandwidth, kkt_storage=a.storage)
     s.initialize()
     s.iteration_head()
     s.iteration_body()

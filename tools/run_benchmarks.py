@@ -28,7 +28,7 @@ EXT = (".mps", ".qps", ".sif", ".mps.gz", ".qps.gz", ".sif.gz")
 
 
 def run(directory, reformulate=False, kkt_system=None, out=None, backend=None, verbose=True, sparse_hessian=False,
-        bandwidth=None):
+        bandwidth=None, storage="dense"):
     import madqp_jl_amd as M
     from madqp_jl_amd import preprocess as P
 
@@ -60,7 +60,8 @@ def run(directory, reformulate=False, kkt_system=None, out=None, backend=None, v
             band = bandwidth if ksys in ("condensed", "normal") and isinstance(dq.A, M.DeviceCSR) and not dense_h else None
             s = M.MPCSolver(dq, be, max_iter=300, max_ncorr=3, scaling=True,
                             step_rule=M.AdaptiveStep(0.995), regularization=M.FixedRegularization(1e-8, -1e-8),
-                            kkt_system=ksys, rethrow_error=True, mu_min=1e-12, driver="native", kkt_bandwidth=band)  # :33-45
+                            kkt_system=ksys, rethrow_error=True, mu_min=1e-12, driver="native", kkt_bandwidth=band,
+                            kkt_storage=storage if band is not None else "dense")  # :33-45
             r = s.solve()
             total = time.perf_counter() - t0
             prof = be.prof_get()
@@ -90,10 +91,15 @@ def main():
     p.add_argument("--sparse-hessian", action="store_true", help="keep a non-diagonal Hessian sparse (DeviceSymCSR)")
     p.add_argument("--bandwidth", default=None, metavar="{auto,INT}",
                    type=lambda v: v if v == "auto" else int(v), help="band-limited assembly and Cholesky where it applies")
+    p.add_argument("--storage", choices=("dense", "packed"), default="dense",
+                   help="where the band path keeps the KKT matrix (kkt_storage); packed needs --bandwidth")
     a = p.parse_args()
+    if a.storage == "packed" and a.bandwidth is None:
+        p.error("--storage packed needs --bandwidth")
     if a.bandwidth is not None and a.bandwidth != "auto" and a.bandwidth < 0:
         p.error("--bandwidth: auto or a non-negative integer")
-    run(a.directory, a.reformulate, a.kkt_system, a.out, sparse_hessian=a.sparse_hessian, bandwidth=a.bandwidth)
+    run(a.directory, a.reformulate, a.kkt_system, a.out, sparse_hessian=a.sparse_hessian, bandwidth=a.bandwidth,
+        storage=a.storage)
 
 
 if __name__ == "__main__":
