@@ -9,23 +9,23 @@
 //     inside J, recursively: factor the first half, update the second half with it
 //       C[h:n, h:w] -= L[h:n, 0:h] * L[h:w, 0:h]'           gemm core, N = K = w/2        (MFMA)
 //     down to 128-column blocks jb:
-//       L_jj = chol(C_jj),  W_jj = L_jj^-1                   one workgroup, block resident in LDS
-//       L[jb+128:n, jb] = C[jb+128:n, jb] * W_jj'            gemm core, K = N = 128        (MFMA)
+//       L_jj = chol(C_jj) and the inverses of its 16 x 16 diagonal sub-blocks      one workgroup, block resident in LDS
+//       L[jb+128:n, jb] = C[jb+128:n, jb] * L_jj^-T          block substitution over 16-column sub-blocks (MFMA)
 // Matrices up to n = 13 312 take a right-looking schedule instead (chol_mid_step_kernel below): two launches per
 // 128-column block, the diagonal block factored inside the launch that updates trailing tiles -- which tiles, with
 // which panels, a plan made once per handle decides (mid_plan.inc: updates are applied when there is room, two
 // panels at a time, no later than due).
-// The inverse diagonal blocks W are kept (two images, 2 x n x 128 doubles) and turn the diagonal
-// solves of the two triangular sweeps into 128 x 128 mat-vecs; each sweep is ONE launch of
+// Two sweep images per diagonal block are kept (2 x n x 128 doubles: the 16 x 16 inverses on the diagonal, the
+// sub-blocks off it normalised with them) and turn the diagonal solves of the two triangular sweeps into eight
+// substitution steps on one wave; each sweep is ONE launch of
 // ticket-ordered workgroups handing the solved blocks on through a sentinel-tagged vector, HBM bound
 // (4 n^2 bytes); block rows longer than 64 tiles are streamed by several workgroups (SweepPlan).
 // Host side: ONE left-looking driver (panel_update / factor_block / factor_range) on a CholTarget -- one matrix
 // (madqp_chol_factor), a batch of small matrices at fixed strides (madqp_chol_factor_batched) or a panel of the multi-GPU
 // loop (madqp_chol_factor_panel, ...); ONE panel solve of a 128-column block (madqp_chol_panel_solve), shared with the
-// mid-size schedule (factor_mid) and dist.hip; the A/B switches are read in one place (CholModes).
+// mid-size schedule (factor_mid) and dist.hip; the environment is read in one place (CholModes).
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 
 #include <vector>
 
@@ -166,7 +166,7 @@ __device__ __forceinline__ void diag16_factor_invert(double4_t A, double* __rest
 __device__ unsigned long long madqp_potf2_stamps[64];  // diagnostic build only (tools/potf2_probe.cpp)
 #define P2_STAMP(i)                                                                    \
     do {                                                                               \
-        if (threadIdx.x == 0 && MODE != 2) madqp_potf2_stamps[i] = __builtin_amdgcn_s_memrealtime(); \
+        if (threadIdx.x == 0) madqp_potf2_stamps[i] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 #else
 #define P2_STAMP(i)
@@ -188,8 +188,7 @@ constexpr int P2_WD_DOUBLES = NSB * SB * WD_LD;   // inverse diagonal sub-blocks
 // 8 bits, 0xFF ends the list; bit 6: 0 = trailing tile (K = bits 5..3, I = bits 2..0), 1 = inverse tile (I, J').
 // Drawn at compile time: enumerating the 34 tiles of a step in every wave (loop, modulo, three branches per tile) cost
 // more instruction issue and fetch than the products themselves -- the phase got SLOWER with more helper waves.
-// MODE 0: trailing tiles and inverse tiles (factor + invert in one kernel); 1: trailing tiles only (factor); 2: inverse tiles
-// only (the inverse of an already factored block)
+// MODE 0: trailing tiles and inverse tiles (factor + invert in one kernel); 1: trailing tiles only (factor)
 template <int NHE, int MODE>
 struct P2Lists {
     static_assert(NHE >= 5, "at most 34 tiles per step: seven entries and the end mark per wave");
@@ -206,10 +205,9 @@ struct P2Lists {
                 ++cnt[h];
                 ++c;
             };
-            if (MODE != 2)
-                for (int K = J + 1; K < N; ++K)
-                    for (int I = K; I < N; ++I)
-                        if (!(K == J + 1 && I == J + 1)) put(K * 8 + I);
+            for (int K = J + 1; K < N; ++K)
+                for (int I = K; I < N; ++I)
+                    if (!(K == J + 1 && I == J + 1)) put(K * 8 + I);
             if (MODE != 1)
                 for (int I = J + 1; I < N; ++I)
                     for (int Jp = 0; Jp <= J; ++Jp) put(64 + I * 8 + Jp);
@@ -250,11 +248,11 @@ __device__ __forceinline__ void p2_wait(double (&a)[4], double (&b)[4], double (
 }
 __device__ __forceinline__ unsigned p2_lds(const double* p) { return (unsigned)(uintptr_t)(lds_ptr_t)p; }
 // the whole workgroup (NT threads: 512, or 1024 in probe builds) calls this; S and Wd are its LDS work areas
-// MODE (round 4): 0 = factor and invert (as rounds 1-3); 1 = factor only -- L_jj and the inverses of its eight 16 x 16
-// diagonal sub-blocks, which is all the panel solve (panel_sub16_kernel) needs: the serial spine of a factorisation then
-// carries neither the inverse's tile products nor the stores of two 128 x 128 images; 2 = the inverse of an already
-// factored block from L_jj and those sub-block inverses -- every block of a factorisation in ONE launch, off the chain
-// (potf2_invert_kernel), before anything reads the images (the sweeps).
+// MODE (round 4): 0 = factor and invert (the batched engine, whose workgroup sweeps multiply with the full inverses);
+// 1 = factor only -- L_jj and the inverses of its eight 16 x 16 diagonal sub-blocks, which is all the panel solve
+// (panel_sub16_kernel) needs: the serial spine of a factorisation then carries neither the inverse's tile products nor the
+// stores of two 128 x 128 images; the off-diagonal parts of the sweep images follow in ONE launch per factorisation, off
+// the chain (sweep_image_kernel).
 template <int NT, int MODE = 0>
 __device__ __forceinline__ void potf2_inv_body(double* __restrict__ A, int64_t lda, int nb,
                                                double* __restrict__ Wcm, double* __restrict__ Wrm,
@@ -282,14 +280,6 @@ __device__ __forceinline__ void potf2_inv_body(double* __restrict__ A, int64_t l
         }
 #pragma unroll
         for (int i = 0; i < NB / CG; ++i) S[(c0 + CG * i) * LDS_LD + r] = v[i];
-    }
-    if (MODE == 2) {  // the sub-block inverses the factor-only kernel left on the diagonal of the column-major image
-        // (rows at or beyond the order of a short block were never written by that kernel: identity padding, as MODE 0 has)
-        for (int e = tid; e < NSB * SB * SB; e += NT) {
-            const int J = e >> 8, rr = (e >> 4) & 15, cc = e & 15;
-            const double wv = Wcm[(SB * J + cc) * NB + SB * J + rr];
-            Wd[(J * SB + rr) * WD_LD + cc] = (SB * J + rr < nb) ? ((cc <= rr) ? wv : 0.0) : ((rr == cc) ? 1.0 : 0.0);
-        }
     }
     __syncthreads();
     P2_STAMP(1);
@@ -343,7 +333,7 @@ __device__ __forceinline__ void potf2_inv_body(double* __restrict__ A, int64_t l
         for (int v = 0; v < 4; ++v) S[(SB * I + hi + 4 * v) * LDS_LD + SB * Jp + lo] = -R[v];
     };
     constexpr int NWV = NT / 64, NH = NWV - 1;  // waves; helper waves 1..NH
-    if (MODE != 2 && wave == 0) diag16_factor_invert(diag16_load(S, 0, lane), S, 0, Wd, info, col0, lane);
+    if (wave == 0) diag16_factor_invert(diag16_load(S, 0, lane), S, 0, Wd, info, col0, lane);
     __syncthreads();
     P2_STAMP(2);
     for (int J = 0; J < NSB; ++J) {
@@ -355,7 +345,6 @@ __device__ __forceinline__ void potf2_inv_body(double* __restrict__ A, int64_t l
                 if (MODE != 1) w_finish(J, o);
                 continue;
             }
-            if (MODE == 2) continue;  // (the panel tiles of L are final)
             const int I = o + 1;
             double4_t acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -374,12 +363,10 @@ __device__ __forceinline__ void potf2_inv_body(double* __restrict__ A, int64_t l
         // other tiles of this step and the T tiles of the inverse
         if (J + 1 < NSB) {
             if (wave == 0) {
-                if (MODE != 2) {
-                    trailing_tile(J, J + 1, J + 1);
-                    // (keeping this update in registers as the input of the pivot chain, instead of the round trip through
-                    // S, changed nothing: 2.12-2.20 us per step either way)
-                    diag16_factor_invert(diag16_load(S, b + SB, lane), S, b + SB, WdJ + SB * WD_LD, info, col0, lane);
-                }
+                trailing_tile(J, J + 1, J + 1);
+                // (keeping this update in registers as the input of the pivot chain, instead of the round trip through
+                // S, changed nothing: 2.12-2.20 us per step either way)
+                diag16_factor_invert(diag16_load(S, b + SB, lane), S, b + SB, WdJ + SB * WD_LD, info, col0, lane);
             } else if (P2_QUIET < 0 || (wave & 3) != 0) {
                 // (waves 4, 8, .. share their SIMD with wave 0 and sit this phase out: the fp64 MFMAs of a helper
                 // there hold up every vector instruction of the pivot chain)
@@ -396,13 +383,11 @@ __device__ __forceinline__ void potf2_inv_body(double* __restrict__ A, int64_t l
                 }
                 // the 16 columns of L that step J completed go to global memory now, beside wave 0's pivot chain
                 // (round 4: as one pass after the last step the store of the factor was 1.5 us at the END of the chain)
-                if (MODE != 2) {
-                    for (int c = b + hr; c < b + SB && c < nb; c += NHE) {
-                        const double* sc = S + c * LDS_LD;
-                        double* gc = A + (int64_t)c * lda;
-                        if (lane >= c && lane < nb) gc[lane] = sc[lane];
-                        if (lane + 64 >= c && lane + 64 < nb) gc[lane + 64] = sc[lane + 64];
-                    }
+                for (int c = b + hr; c < b + SB && c < nb; c += NHE) {
+                    const double* sc = S + c * LDS_LD;
+                    double* gc = A + (int64_t)c * lda;
+                    if (lane >= c && lane < nb) gc[lane] = sc[lane];
+                    if (lane + 64 >= c && lane + 64 < nb) gc[lane + 64] = sc[lane + 64];
                 }
             }
         }
@@ -410,7 +395,7 @@ __device__ __forceinline__ void potf2_inv_body(double* __restrict__ A, int64_t l
         P2_STAMP(4 + 3 * J);
     }
     // the last 16 columns of the factor -> global (the others went out step by step)
-    if (MODE != 2) {
+    {
         const int r = (NSB - 1) * SB + (tid & 15), c = (NSB - 1) * SB + (tid >> 4);
         if (tid < SB * SB && c <= r && r < nb) A[r + (int64_t)c * lda] = S[c * LDS_LD + r];
     }
@@ -475,25 +460,14 @@ __global__ __launch_bounds__(P2_KTHREADS) void potf2_inv_kernel(double* __restri
     }
     potf2_inv_body<P2_KTHREADS, MODE>(A, lda, nb, Wcm, Wrm, info, col0, S, Wd);
 }
-// The inverse images of the diagonal blocks j0/128 .. of a factored matrix, one workgroup per block, in ONE launch: what
-// the factor-only diagonal kernel (MODE 1) leaves out of the serial spine.  A: the matrix (block b at (j0 + 128 b) (lda + 1)).
-__global__ __launch_bounds__(P2_KTHREADS) void potf2_invert_kernel(double* __restrict__ A, int64_t lda, int64_t n, int64_t j0,
-                                                                   double* __restrict__ winv) {
-    __shared__ double S[P2_S_DOUBLES];
-    __shared__ double Wd[P2_WD_DOUBLES];
-    const int64_t jb = j0 + (int64_t)blockIdx.x * NB;
-    const int nb = (int)((n - jb < NB) ? (n - jb) : NB);
-    double* Wcm = winv + (jb / NB) * WBLK;
-    potf2_inv_body<P2_KTHREADS, 2>(A + jb + jb * lda, lda, nb, Wcm, Wcm + NB * NB, nullptr, 0, S, Wd);
-}
 
 // The off-diagonal 16 x 16 sub-blocks of both sweep images of the diagonal blocks j0/128 .. of a factored matrix, one
 // workgroup per block, ONE launch per factorisation (see "the diagonal step of a sweep" below): image 1 (column-major)
 // gets Lt_IJ = L_IJ W_JJ at (16 I.., 16 J..), image 2 gets Lh_IJ = W_II L_IJ transposed, i.e. at [(16 I + k) NB + 16 J + c]
-// -- the places the 128 x 128 inverse and its transpose used to fill; the diagonals (W_JJ, left by the factor-only
-// diagonal kernels) stay.  normalise = 0: the sub-blocks of L themselves (plain block substitution, MADQP_SWEEP_DIAG=sub16).
+// -- what the factor-only diagonal kernels (MODE 1) leave out of the serial spine; the diagonals (W_JJ, left by those
+// kernels) stay.
 __global__ __launch_bounds__(256) void sweep_image_kernel(const double* __restrict__ A, int64_t lda, int64_t n, int64_t j0,
-                                                          double* __restrict__ winv, int normalise) {
+                                                          double* __restrict__ winv) {
     __shared__ double S[P2_S_DOUBLES];   // S[c*LDS_LD + r] = L(r, c), zero beyond the order of a short block
     __shared__ double Wd[P2_WD_DOUBLES]; // W_JJ[r][c] at (J*SB + r)*WD_LD + c
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lo = lane & 15, hi = lane >> 4;
@@ -527,10 +501,10 @@ __global__ __launch_bounds__(256) void sweep_image_kernel(const double* __restri
             const int k = 4 * s4 + hi;
             // P = L_IJ W_JJ: A[m = lo][k] = L_IJ[lo][k], B[k][n = lo] = W_JJ[k][lo]
             const double pa = S[(SB * J + k) * LDS_LD + SB * I + lo];
-            const double pb = normalise ? Wd[(J * SB + k) * WD_LD + lo] : (k == lo ? 1.0 : 0.0);
+            const double pb = Wd[(J * SB + k) * WD_LD + lo];
             P = __builtin_amdgcn_mfma_f64_16x16x4f64(pa, pb, P, 0, 0, 0);
             // Q = W_II L_IJ: A[m = lo][k] = W_II[lo][k], B[k][n = lo] = L_IJ[k][lo]
-            const double qa = normalise ? Wd[(I * SB + lo) * WD_LD + k] : (k == lo ? 1.0 : 0.0);
+            const double qa = Wd[(I * SB + lo) * WD_LD + k];
             const double qb = S[(SB * J + lo) * LDS_LD + SB * I + k];
             Q = __builtin_amdgcn_mfma_f64_16x16x4f64(qa, qb, Q, 0, 0, 0);
         }
@@ -546,7 +520,8 @@ __global__ __launch_bounds__(256) void sweep_image_kernel(const double* __restri
 // A sweep over the 128-row blocks is a chain: block r needs the solutions of all blocks before it.
 // Instead of one launch per block (391 launches per sweep at n = 50 000, each with its own ramp and
 // tail) ONE launch runs a workgroup per block; workgroup r streams its own tiles L[r, j] (forward) /
-// L[j, r] (backward) as the x_j appear and then solves its diagonal block with the stored inverse.
+// L[j, r] (backward) as the x_j appear and then solves its diagonal block by unit block substitution on the block's
+// sweep image (see "the diagonal step of a sweep" below).
 //   * order: a workgroup draws its block index from a ticket counter, so it only ever waits for
 //     blocks drawn earlier, which are resident or finished -- the grid always drains, whatever the
 //     dispatch order and however many workgroups fit on the chip;
@@ -554,9 +529,9 @@ __global__ __launch_bounds__(256) void sweep_image_kernel(const double* __restri
 //     vector pre-filled with a NaN sentinel; consumers poll the values themselves with sc1 loads
 //     (data = tag: no flag, no fence; MI355X_MICROARCH.md "handoff-1to1", ~1 us per hop);
 //   * streaming: 16 waves x (2 rows per lane) x (4 columns per wave) = half a tile per stage, two
-//     stages in flight in registers while the wave waits for the next x_j; the inverse diagonal
-//     block sits in registers from the start, so the critical path per block is
-//     poll -> 8 fma -> cross-wave sum -> 128 x 128 product -> publish.
+//     stages in flight in registers while the wave waits for the next x_j; the block's sweep image
+//     sits in LDS from the start, so the critical path per block is
+//     poll -> 8 fma -> cross-wave sum -> eight substitution steps on one wave -> publish.
 // Summation order is fixed by the thread mapping: results do not depend on timing.
 constexpr unsigned long long SWEEP_SENTINEL = 0x7FF8A5A57FF8A5A5ull;  // a NaN no arithmetic produces
 constexpr int SWEEP_SPIN_LIMIT = 1 << 22;
@@ -669,46 +644,20 @@ __device__ __forceinline__ void sweep_load_half(const double* __restrict__ base,
     }
 }
 
-// One product with a 128 x 128 block image held in registers (w0, w1 = the two column halves of this thread's two
-// rows): the 128 results, summed over the 16 waves in wave order, are returned to the threads tid < 128 (others: 0).
-// Ends with the partial sums in `red`: the caller synchronises before `red` is written again.
-__device__ __forceinline__ double sweep_block_product(const double2_t (&w0)[4], const double2_t (&w1)[4],
-                                                      const double* __restrict__ vs, double (*red)[NB], int tid, int lane,
-                                                      int wave) {
-    double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const double v0 = vs[wave * 4 + q], v1 = vs[64 + wave * 4 + q];
-        a0 = __builtin_fma(w0[q].x, v0, a0);
-        a1 = __builtin_fma(w0[q].y, v0, a1);
-        a0 = __builtin_fma(w1[q].x, v1, a0);
-        a1 = __builtin_fma(w1[q].y, v1, a1);
-    }
-    red[wave][2 * lane] = a0;
-    red[wave][2 * lane + 1] = a1;
-    __syncthreads();
-    double sum = 0.0;
-    if (tid < NB) {
-        sum = red[0][tid];
-#pragma unroll
-        for (int q = 1; q < 16; ++q) sum += red[q][tid];
-    }
-    return sum;
-}
 // ---- the diagonal step of a sweep by UNIT BLOCK SUBSTITUTION over the 16 x 16 sub-blocks (round 5) -----------------------
-// A product with the stored 128 x 128 inverse leaves a residual of cond(L_rr) eps where substitution leaves eps, and the
-// interior-point iterates see the residual: on ill-conditioned problems the per-iteration traces sat up to 80 x the CPU
-// noise floor from LAPACK's (profiles/r04_parity_ratios_default.json; tools/numerics/blockchol_emul.py: it is the product
-// with ANY stored 128-inverse, while block substitution over 16 x 16 sub-blocks is statistically as good as dtrsv).  The
-// sweeps therefore substitute: with W_JJ = (L_rr)_JJ^-1 (16 x 16, left on the images' diagonals by the factor-only
+// A product with a stored 128 x 128 inverse (the form of rounds 1-4, removed; its numbers: DESIGN.md 4.2) leaves a
+// residual of cond(L_rr) eps where substitution leaves eps, and the interior-point iterates see the residual: on
+// ill-conditioned problems the per-iteration traces sat up to 80 x the CPU noise floor from LAPACK's
+// (profiles/r04_parity_ratios_default.json; tools/numerics/blockchol_emul.py: it is the product with ANY stored
+// 128-inverse, while block substitution over 16 x 16 sub-blocks is statistically as good as dtrsv).  The sweeps
+// therefore substitute: with W_JJ = (L_rr)_JJ^-1 (16 x 16, left on the images' diagonals by the factor-only
 // diagonal kernel) and the off-diagonal sub-blocks normalised ONCE per factorisation (sweep_image_kernel),
 //     forward   Lt_IJ = L_IJ W_JJ :   u_I = v_I - sum_{J<I} Lt_IJ u_J,    z_I = W_II u_I
 //     backward  Lh_IJ = W_II L_IJ :   w_J = v_J - sum_{I>J} Lh_IJ' w_I,   x_J = W_JJ' w_J
 // (the same error bound as z_I = W_II (v_I - sum L_IJ z_J): the 16 x 16 inverses enter once per term either way), so
 // that ONE broadcast of the 16 values u_J serves both the rows of sub-block J (-> z_J) and every row below (-> update):
 // eight steps of 32 read-lanes + 32 fused multiply-adds on ONE wave, no barrier, no LDS round trip on the chain.
-// DIAG = 2 keeps plain block substitution (images hold L_IJ itself; a second broadcast per step) for A/B runs,
-// DIAG = 0 the product with the 128 x 128 inverse (MADQP_SWEEP_DIAG=inv, and whenever the images hold full inverses).
+// (Plain block substitution on un-normalised images needs a second broadcast per step; measured and removed.)
 // The image of a block sits in LDS packed by columns: forward column c (sub-block J) holds rows 16 J .. 127, backward
 // column q (sub-block I) rows 0 .. 16 I + 15; a lane reads consecutive rows of one column: conflict free.
 constexpr int XIMG_DOUBLES = 16 * (8 * NB - 16 * 28);                                               // 9 216
@@ -747,7 +696,7 @@ __device__ __forceinline__ void sweep_bcast8(double src, int g, int h, double (&
 // t0 = sum_k x0[k] b[k], t1 = sum_k x1[k] b[k] over the 16 columns of one sub-block (two partial sums each, fixed order);
 // column k of the packed image at X + k * len (+ 64 for the second row of the lane); HAS0 / HAS1: which of the lane's two
 // rows take part (compile time)
-template <int DIAG, bool HAS0, bool HAS1>
+template <bool HAS0, bool HAS1>
 __device__ __forceinline__ void sweep_dot16(const double* __restrict__ X, int len, double src, int g, int lane,
                                             double& t0, double& t1) {
     double t0a = 0.0, t0b = 0.0, t1a = 0.0, t1b = 0.0;
@@ -776,7 +725,6 @@ __device__ __forceinline__ void sweep_dot16(const double* __restrict__ X, int le
     t1 = t1a + t1b;
 }
 // wave 0: the 128 values of the diagonal step; lane l holds rows l (u0) and 64 + l (u1) on entry (v) and on return (z)
-template <int DIAG>
 __device__ __forceinline__ double2_t sweep_diag_fwd(const double* __restrict__ X, int lane, double u0, double u1) {
     // (inlined, behind a compiler barrier: as a call the callee saves 48 registers to scratch on the chain; without the
     // barrier the image reads drift up into the streaming loop and its registers spill)
@@ -789,19 +737,9 @@ __device__ __forceinline__ double2_t sweep_diag_fwd(const double* __restrict__ X
         const double src = (J < 4) ? u0 : u1;
         double t0 = 0.0, t1 = 0.0;
         if (J < 4)
-            sweep_dot16<DIAG, true, true>(Xj, len, src, J & 3, lane, t0, t1);
+            sweep_dot16<true, true>(Xj, len, src, J & 3, lane, t0, t1);
         else
-            sweep_dot16<DIAG, false, true>(Xj, len, src, J & 3, lane, t0, t1);
-        if (DIAG == 2) {  // plain block substitution: the rows below take z_J, not u_J
-            const double zsrc = (J < 4) ? t0 : t1;
-            double s0 = 0.0, s1 = 0.0;
-            if (J < 4)
-                sweep_dot16<DIAG, true, true>(Xj, len, zsrc, J & 3, lane, s0, s1);
-            else
-                sweep_dot16<DIAG, false, true>(Xj, len, zsrc, J & 3, lane, s0, s1);
-            if (J < 4) t0 = (I0 == J) ? t0 : s0;
-            t1 = (4 + I0 == J) ? t1 : s1;
-        }
+            sweep_dot16<false, true>(Xj, len, src, J & 3, lane, t0, t1);
         if (J < 4) {
             u0 = (I0 == J) ? t0 : (I0 > J) ? u0 - t0 : u0;
             u1 = u1 - t1;
@@ -811,7 +749,6 @@ __device__ __forceinline__ double2_t sweep_diag_fwd(const double* __restrict__ X
     }
     return double2_t{u0, u1};
 }
-template <int DIAG>
 __device__ __forceinline__ double2_t sweep_diag_bwd(const double* __restrict__ X, int lane, double u0, double u1) {
     // (inlined, behind a compiler barrier: as a call the callee saves 48 registers to scratch on the chain; without the
     // barrier the image reads drift up into the streaming loop and its registers spill)
@@ -824,19 +761,9 @@ __device__ __forceinline__ double2_t sweep_diag_bwd(const double* __restrict__ X
         const double src = (I < 4) ? u0 : u1;
         double t0 = 0.0, t1 = 0.0;
         if (I >= 4)
-            sweep_dot16<DIAG, true, true>(Xi, len, src, I & 3, lane, t0, t1);
+            sweep_dot16<true, true>(Xi, len, src, I & 3, lane, t0, t1);
         else
-            sweep_dot16<DIAG, true, false>(Xi, len, src, I & 3, lane, t0, t1);
-        if (DIAG == 2) {
-            const double zsrc = (I < 4) ? t0 : t1;
-            double s0 = 0.0, s1 = 0.0;
-            if (I >= 4)
-                sweep_dot16<DIAG, true, true>(Xi, len, zsrc, I & 3, lane, s0, s1);
-            else
-                sweep_dot16<DIAG, true, false>(Xi, len, zsrc, I & 3, lane, s0, s1);
-            t0 = (J0 == I) ? t0 : s0;
-            if (I >= 4) t1 = (4 + J0 == I) ? t1 : s1;
-        }
+            sweep_dot16<true, false>(Xi, len, src, I & 3, lane, t0, t1);
         if (I >= 4) {
             u1 = (4 + J0 == I) ? t1 : (4 + J0 < I) ? u1 - t1 : u1;
             u0 = u0 - t0;
@@ -851,24 +778,22 @@ __global__ __launch_bounds__(256) void negate_kernel(double* __restrict__ v, int
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (int64_t)gridDim.x * 256) v[i] = -v[i];
 }
 
-// REV (DIAG = 1 only): the same sweep on U = L' from the far end -- the backward substitution x = L^-T y as sums over the
+// REV: the same sweep on U = L' from the far end -- the backward substitution x = L^-T y as sums over the
 // ROWS of U's blocks: block r of the chain is block nblk-1-r of the matrix, its sources lie to the right of the diagonal,
 // the diagonal step is the backward one on the block's second image.  The mid-size factorisation leaves U in a buffer of
 // its own (lower_to_upper_kernel); two accumulators per thread where the transposed product on L (trsv_bwd_sweep_kernel)
 // needs sixteen and a column reduction through LDS per block: 3.3 us per hop instead of 4.3.  out: optional second copy
 // of the solution (plain stores; the polled copy y may then be scratch memory).
-template <int DIAG, bool REV = false>
+template <bool REV = false>
 __global__ __launch_bounds__(1024) void trsv_fwd_sweep_kernel(const double* __restrict__ L, int64_t lda,
                                                               const double* __restrict__ winv,
                                                               const double* __restrict__ b,
                                                               double* __restrict__ y, int64_t n,
                                                               int32_t* __restrict__ ctl, double* __restrict__ fault,
                                                               int vec, SweepPlan plan, double* __restrict__ out, int kb) {
-    static_assert(!REV || DIAG == 1, "the sweep on U runs the substituting diagonal step");
     __shared__ double xs[2][NB];
     __shared__ double red[16][NB];
-    __shared__ double vs[NB];
-    __shared__ double ximg[DIAG ? XIMG_DOUBLES : 1];
+    __shared__ double ximg[XIMG_DOUBLES];
     __shared__ int s_r;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) s_r = atomicAdd(&ctl[REV ? 2 : 1], 1);
@@ -895,31 +820,20 @@ __global__ __launch_bounds__(1024) void trsv_fwd_sweep_kernel(const double* __re
     const int64_t row0 = (int64_t)r * NB;
     const int w = (int)((n - row0 < NB) ? (n - row0) : NB);
     const bool ok0 = row0 + 2 * lane < n, ok1 = row0 + 2 * lane + 1 < n;
-    // DIAG = 0: the inverse diagonal block (column-major image, zero padded, 16-byte aligned) in registers;
-    // else: this block's forward image (16 x 16 inverses on the diagonal, normalised sub-blocks below) packed into LDS
-    double2_t W0[4], W1[4];
+    // this block's image (16 x 16 inverses on the diagonal, normalised sub-blocks off it; REV: the second of its pair) packed into LDS
     double xv[16];
-    if (owner) {
-        const double* Wcm = winv + (int64_t)r * WBLK + (REV ? NB * NB : 0);
-        if (DIAG == 0) {
-            sweep_load_half(Wcm + 2 * lane + (int64_t)(wave * 4) * NB, NB, true, true, true, W0);
-            sweep_load_half(Wcm + 2 * lane + (int64_t)(64 + wave * 4) * NB, NB, true, true, true, W1);
-        } else {
-            ximg_load(Wcm, tid, xv);
-        }
-    }
+    if (owner) ximg_load(winv + (int64_t)r * WBLK + (REV ? NB * NB : 0), tid, xv);
     double a0 = 0.0, a1 = 0.0;
     const double* Lr = L + row0 + 2 * lane + (int64_t)(wave * 4) * lda;  // this thread's corner of tile (r, 0)
     auto col = [&](int j) { return (int64_t)(REV ? nblk - 1 - j : j) * NB * lda; };  // tile column of source j of the chain
     double2_t A[4], B[4];
     if (j1 > j0) sweep_load_half(Lr + col(j0), lda, ok0, ok1, vec, A);
-    if (DIAG != 0 && owner) ximg_store<REV>(xv, ximg, tid);  // (visible to wave 0 after any later barrier)
+    if (owner) ximg_store<REV>(xv, ximg, tid);  // (visible to wave 0 after any later barrier)
     // the right-hand side of this block, fetched NOW: read behind the last barrier it is an L2 round trip on every hop
     double b0 = 0.0, b1 = 0.0;
     if (owner) {
-        const int i0 = DIAG != 0 ? lane : (tid & (NB - 1)), i1 = 64 + lane;
-        b0 = i0 < w ? b[row0 + i0] : 0.0;
-        if (DIAG != 0) b1 = i1 < w ? b[row0 + i1] : 0.0;
+        b0 = lane < w ? b[row0 + lane] : 0.0;
+        b1 = 64 + lane < w ? b[row0 + 64 + lane] : 0.0;
     }
     for (int j = j0; j < j1; ++j) {
         const double* Tj = Lr + col(j);
@@ -944,25 +858,13 @@ __global__ __launch_bounds__(1024) void trsv_fwd_sweep_kernel(const double* __re
     red[wave][2 * lane] = a0;
     red[wave][2 * lane + 1] = a1;
     __syncthreads();
-    if (DIAG == 0 || !owner) {
+    if (!owner) {
         if (tid < NB) {
             double sum = red[0][tid];
 #pragma unroll
             for (int q = 1; q < 16; ++q) sum += red[q][tid];
-            if (!owner) {
-                st_sc1_f64(plan.part + ((int64_t)rl * plan.maxc + c) * NB + tid, sum);
-            } else {
-                double far = 0.0;  // the partial sums of this block's other jobs, in column order
-                for (int cc = clo; cc < c; ++cc)
-                    far += sweep_poll_one(plan.part + ((int64_t)rl * plan.maxc + cc) * NB + tid, fault);
-                vs[tid] = (tid < w) ? (b0 - (far + sum)) : 0.0;
-            }
+            st_sc1_f64(plan.part + ((int64_t)rl * plan.maxc + c) * NB + tid, sum);
         }
-        if (!owner) return;
-        __syncthreads();
-        const double z0 = sweep_block_product(W0, W1, vs, red, tid, lane, wave);  // z = W v
-        if (tid < w) st_sc1_f64(y + row0 + tid, z0);
-        if (out && tid < w) out[row0 + tid] = z0;
         return;
     }
     if (wave != 0) return;  // (the image was complete before the first barrier of this workgroup)
@@ -976,7 +878,7 @@ __global__ __launch_bounds__(1024) void trsv_fwd_sweep_kernel(const double* __re
     double far0, far1;  // the partial sums of this block's other jobs, in column order
     sweep_far2(plan.part + (int64_t)rl * plan.maxc * NB, clo, c, lane, fault, far0, far1);
     const double u0 = lane < w ? b0 - (far0 + s0) : 0.0, u1 = 64 + lane < w ? b1 - (far1 + s1) : 0.0;
-    const double2_t z = REV ? sweep_diag_bwd<DIAG>(ximg, lane, u0, u1) : sweep_diag_fwd<DIAG>(ximg, lane, u0, u1);
+    const double2_t z = REV ? sweep_diag_bwd(ximg, lane, u0, u1) : sweep_diag_fwd(ximg, lane, u0, u1);
     if (lane < w) st_sc1_f64(y + row0 + lane, z.x);
     if (64 + lane < w) st_sc1_f64(y + row0 + 64 + lane, z.y);
     if (out) {
@@ -1012,7 +914,6 @@ __global__ __launch_bounds__(256) void sweep_prep_kernel(unsigned long long* __r
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (int64_t)gridDim.x * 256) v[i] = SWEEP_SENTINEL;
 }
 
-template <int DIAG>
 __global__ __launch_bounds__(1024) void trsv_bwd_sweep_kernel(const double* __restrict__ L, int64_t lda,
                                                               const double* __restrict__ winv,
                                                               const double* __restrict__ y,
@@ -1020,10 +921,9 @@ __global__ __launch_bounds__(1024) void trsv_bwd_sweep_kernel(const double* __re
                                                               int32_t* __restrict__ ctl, double* __restrict__ fault,
                                                               int vec, SweepPlan plan, int kb) {
     __shared__ double xs[2][NB];
-    __shared__ double red[DIAG ? 1 : 16][NB];
     __shared__ double vs[NB];
     __shared__ double colred[NB][65];  // column-sum staging, padded against bank conflicts
-    __shared__ double ximg[DIAG ? XIMG_DOUBLES : 1];
+    __shared__ double ximg[XIMG_DOUBLES];
     __shared__ int s_r;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nblk = (int)((n + NB - 1) / NB);
@@ -1047,19 +947,9 @@ __global__ __launch_bounds__(1024) void trsv_bwd_sweep_kernel(const double* __re
     const int r = nblk - 1 - rr;
     const int64_t col0 = (int64_t)r * NB;
     const int w = (int)((n - col0 < NB) ? (n - col0) : NB);
-    // DIAG = 0: W' v through the row-major image (Wrm[c + r*NB] = W(r, c): output index c is the fast one), in registers;
-    // else: this block's backward image packed into LDS
-    double2_t W0[4], W1[4];
+    // this block's backward image (the second one of its pair) packed into LDS
     double xv[16];
-    if (owner) {
-        const double* Wrm = winv + (int64_t)r * WBLK + NB * NB;
-        if (DIAG == 0) {
-            sweep_load_half(Wrm + 2 * lane + (int64_t)(wave * 4) * NB, NB, true, true, true, W0);
-            sweep_load_half(Wrm + 2 * lane + (int64_t)(64 + wave * 4) * NB, NB, true, true, true, W1);
-        } else {
-            ximg_load(Wrm, tid, xv);
-        }
-    }
+    if (owner) ximg_load(winv + (int64_t)r * WBLK + NB * NB, tid, xv);
     // this thread's columns: col0 + h*64 + wave*4 + q; rows 2*lane, 2*lane+1 of the row block j
     double acc[2][4];
 #pragma unroll
@@ -1080,12 +970,11 @@ __global__ __launch_bounds__(1024) void trsv_bwd_sweep_kernel(const double* __re
         rows_ok(jhi, o0, o1);
         sweep_load_half(Lc + (int64_t)jhi * NB, lda, o0, o1, vec, A);
     }
-    if (DIAG != 0 && owner) ximg_store<true>(xv, ximg, tid);
+    if (owner) ximg_store<true>(xv, ximg, tid);
     double y0 = 0.0, y1 = 0.0;  // this block of the right-hand side, fetched now (see the forward kernel)
     if (owner) {
-        const int i0 = DIAG != 0 ? lane : (tid & (NB - 1)), i1 = 64 + lane;
-        y0 = i0 < w ? y[col0 + i0] : 0.0;
-        if (DIAG != 0) y1 = i1 < w ? y[col0 + i1] : 0.0;
+        y0 = lane < w ? y[col0 + lane] : 0.0;
+        y1 = 64 + lane < w ? y[col0 + 64 + lane] : 0.0;
     }
     for (int j = jhi; j > jlo; --j) {
         bool o0, o1;
@@ -1129,86 +1018,17 @@ __global__ __launch_bounds__(1024) void trsv_bwd_sweep_kernel(const double* __re
         if (tid < NB) st_sc1_f64(plan.part + ((int64_t)rr * plan.maxc + c) * NB + tid, vs[tid]);
         return;
     }
-    if (DIAG == 0) {
-        if (tid < NB) {
-            double far = 0.0;
-            for (int cc = clo; cc < c; ++cc)
-                far += sweep_poll_one(plan.part + ((int64_t)rr * plan.maxc + cc) * NB + tid, fault);
-            vs[tid] = (tid < w) ? (y0 - (far + vs[tid])) : 0.0;
-        }
-        __syncthreads();
-        const double x0 = sweep_block_product(W0, W1, vs, red, tid, lane, wave);  // x = W' v
-        if (tid < w) st_sc1_f64(x + col0 + tid, x0);
-        return;
-    }
     if (wave != 0) return;  // wave 0 alone from here, no further barrier
     double far0, far1;
     sweep_far2(plan.part + (int64_t)rr * plan.maxc * NB, clo, c, lane, fault, far0, far1);
     const double u0 = lane < w ? y0 - (far0 + vs[lane]) : 0.0, u1 = 64 + lane < w ? y1 - (far1 + vs[64 + lane]) : 0.0;
-    const double2_t z = sweep_diag_bwd<DIAG>(ximg, lane, u0, u1);
+    const double2_t z = sweep_diag_bwd(ximg, lane, u0, u1);
     if (lane < w) st_sc1_f64(x + col0 + lane, z.x);
     if (64 + lane < w) st_sc1_f64(x + col0 + 64 + lane, z.y);
 }
 
-// ---- panel times inverse for ONE 128-column block: L[rows, :] = C[rows, :] W'  (W = inverse of the block's factor) ----
-// The GEMM kernel does this product with a 128 x 128 tile per workgroup: at most n/128 workgroups, one round, 14 us of
-// MFMA per tile behind a staged prologue -- 23 us per launch at n = 5 000, forty times per factorisation.  Here a workgroup
-// takes 32 ROWS (four times as many workgroups; in place is safe: it reads only the rows it writes), every operand goes
-// straight from L2 to registers in the MFMA operand layout with all loads of a wave in flight at once, and the zero half
-// of the lower-triangular W is skipped: column tile jt (16 columns) meets nonzeros of W only in k < 16 (jt + 1), so a
-// wave that takes the tiles w and 7 - w runs 36 of the 64 k-steps.  D[j][i] = sum_k W(j, k) C(i, k): A-operand <- W
-// (Wcm[j + k*128]), B-operand <- C rows (C[i + k*ld]); lane l holds D[(l>>4) + 4v][l & 15] -> stores walk i.
-__global__ __launch_bounds__(256) void panel_inv_kernel(double* __restrict__ C, int64_t ld, const double* __restrict__ Wcm,
-                                                        int64_t rows) {
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lo = lane & 15, hi = lane >> 4;
-    const int64_t i0 = (int64_t)blockIdx.x * 32;  // (rows up to the padded order exist: the caller's leading dimension)
-    const int jt0 = wave, jt1 = 7 - wave;          // this wave's column tiles; jt0 < jt1
-    const int ns0 = 4 * (jt0 + 1), ns1 = 4 * (jt1 + 1);  // k-steps (of 4) that meet nonzeros of W
-    const double* Cp = C + i0 + lo + (int64_t)hi * ld;
-    const double* W0 = Wcm + 16 * jt0 + lo + hi * NB;
-    const double* W1 = Wcm + 16 * jt1 + lo + hi * NB;
-    double b[32][2], a1[32], a0[16];
-#pragma unroll
-    for (int q = 0; q < 32; ++q) {
-        if (q < ns1) {  // wave-uniform
-            b[q][0] = Cp[(int64_t)(4 * q) * ld];
-            b[q][1] = Cp[(int64_t)(4 * q) * ld + 16];
-            a1[q] = W1[4 * q * NB];
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 16; ++q)
-        if (q < ns0) a0[q] = W0[4 * q * NB];
-    double4_t d0[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, d1[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-#pragma unroll
-    for (int q = 0; q < 32; ++q) {
-        if (q < ns1) {
-            d1[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[q], b[q][0], d1[0], 0, 0, 0);
-            d1[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[q], b[q][1], d1[1], 0, 0, 0);
-        }
-        if (q < 16 && q < ns0) {
-            d0[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[q], b[q][0], d0[0], 0, 0, 0);
-            d0[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[q], b[q][1], d0[1], 0, 0, 0);
-        }
-    }
-    // every load of the workgroup has been consumed before the first store (all four waves read all 32 rows)
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const int64_t gi = i0 + 16 * it + lo;
-        if (gi < rows) {
-#pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                C[gi + (int64_t)(16 * jt0 + hi + 4 * v) * ld] = d0[it][v];
-                C[gi + (int64_t)(16 * jt1 + hi + 4 * v) * ld] = d1[it][v];
-            }
-        }
-    }
-}
-
 // ---- panel solve for ONE 128-column block by BLOCK SUBSTITUTION: L[rows, blk] = C[rows, blk] L_kk^-T --------------------
-// Multiplying the panel by the explicit inverse of the 128 x 128 diagonal block (panel_inv_kernel above, rounds 1-3) costs
+// Multiplying the panel by the explicit inverse of the 128 x 128 diagonal block (rounds 1-3, removed) costs
 // cond(L_kk) in the backward error of the factorisation where LAPACK's dtrsm substitutes (tools/numerics/
 // blockchol_emul.py: on condensed LPs the device's distance from LAPACK has a tail of tens of times the distance between
 // two CPU executions, and neither a correctly rounded inverse nor a Newton-Schulz step removes it -- it is the product
@@ -1320,28 +1140,20 @@ __global__ __launch_bounds__(256) void panel_sub16_kernel(double* __restrict__ C
 // Below n ~ 10 000 the left-looking schedule above is a chain of short dependent launches (per block: update with
 // split-K, its reduction, the diagonal kernel, panel times inverse -- 120 us, of which the matrix pipes are busy a
 // fraction).  Here step k is
-//   chol_mid_step_kernel  every tile (i, j), k <= j <= i, receives the update of panel k-1: C_ij -= L_i,k-1 L_j,k-1'
-//                         (K = 128 always, no split-K; a tile accumulates its updates in the order k = 0, 1, ..), and
-//                         the workgroup holding tile (k, k) goes on to factor and invert it without leaving the CU:
-//                         the updated tile passes from the accumulators to the LDS image of potf2_inv_body;
-//   panel times inverse   L_ik = C_ik W_k' (the GEMM kernel, as in madqp_chol_panel_solve).
-// Workgroups have 512 threads and the diagonal kernel's LDS (one per CU).  That is schedule MODE 0 with two = 0, the
-// form of round 3 (still selectable); round 4 applies the SAME tile-panel products at other times: MODE 1 (default)
-// takes the units of a step from a plan (see "which trailing columns a block step visits" further down), MODE 0
-// with two = 1 visits every second tile column with two panels.  Every tile still accumulates its panels in the
-// order 0, 1, .., so the factor has the same bits under all of them.  In MODE 0 with more tiles than CUs a workgroup
-// runs two tiles at once: waves 0-3 and waves 4-7 each work like one workgroup of gemm_tn_f64_kernel on their own
-// half of the LDS, in lockstep (equal K: both halves execute the same barriers).
+//   chol_mid_step_kernel  trailing tiles (i, j), k <= j <= i, receive pending updates C_ij -= L_i,p L_j,p' -- which tiles,
+//                         with which panels p < k, the plan of the handle decides (see "which trailing columns a block
+//                         step visits" further down; K = 128 per panel, no split-K; a tile accumulates its panels in the
+//                         order 0, 1, .., so the factor has the same bits under every plan) --, and workgroup 0 gives the
+//                         diagonal tile (k, k) its last panel (mid_diag_syrk) and factors it without leaving the CU;
+//   panel solve           L_ik = C_ik L_kk^-T (madqp_chol_panel_solve).
+// Workgroups have 512 threads and the diagonal kernel's LDS (one per CU).  (The schedules of rounds 3-4 that this one
+// replaced -- every panel in every step, two panels every second step, the diagonal tile through the GEMM loop -- were
+// removed; their numbers: DESIGN.md 5.2.)
 struct MidArgs {
     double* A;
     int64_t lda, n;
     int32_t nblk, k;
-    int32_t pack;  // tiles per workgroup (1 or 2); the diagonal tile always has its workgroup to itself
-    int32_t npair;  // pack == 2: workgroups 1 .. npair take two tiles, the ones behind them one (see chol_factor_enqueue)
-    int32_t lite;   // the diagonal workgroup factors only (MODE 1); the inverse images follow in one launch at the end
-    int32_t dsyrk;  // the diagonal workgroup updates its tile with mid_diag_syrk (all eight waves, operand fetched at once)
-    int32_t two;    // two panels per trailing pass (see chol_factor_enqueue): workgroup 1 = the next diagonal tile (one panel)
-    const uint32_t* plan;  // the units of this step (mid_plan_build, mid_plan.inc) or nullptr; one tile per workgroup then
+    const uint32_t* plan;  // the units of this step (mid_plan_build, mid_plan.inc)
     double* winv;
     int32_t* info;
 };
@@ -1376,10 +1188,8 @@ static_assert(NB * XS_LD <= P2_S_DOUBLES + P2_WD_DOUBLES, "the operand image fit
 #else
 #define DS_STAMP(slot)
 #endif
-// zero_upper: the strictly upper sub-tiles are zeroed (the work area of the in-kernel inverse; the factor-only diagonal
-// kernel never touches them)
 __device__ __forceinline__ void mid_diag_syrk(const double* __restrict__ Ckk, const double* __restrict__ R, int64_t lda, int nb,
-                                              double* __restrict__ smem, int kstep, bool zero_upper) {
+                                              double* __restrict__ smem, int kstep) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lo = lane & 15, hi = lane >> 4;
     // this wave's tiles: row pair (p, 7 - p) has 9 lower tiles, waves 2p / 2p + 1 take the first 5 / last 4 of them
@@ -1433,8 +1243,7 @@ __device__ __forceinline__ void mid_diag_syrk(const double* __restrict__ Ckk, co
     __syncthreads();  // every wave has read its fragments: the image becomes potf2's S[c * LDS_LD + r]
     DS_STAMP(6);
     // 3. lower tiles -> S (upper triangle of the diagonal sub-tiles zero, identity beyond the order of a short last block);
-    //    the strictly upper sub-tiles, which nobody computes, are the inverse's work area and must be zero: every
-    //    off-diagonal lower tile (I, J) zeroes its mirror image (J, I) -- all 28 of them, no index arithmetic
+    //    the strictly upper sub-tiles, which nobody computes, the factor-only diagonal kernel never touches
 #pragma unroll
     for (int u = 0; u < 5; ++u) {
         if (u >= cnt) continue;
@@ -1444,221 +1253,108 @@ __device__ __forceinline__ void mid_diag_syrk(const double* __restrict__ Ckk, co
             double x = -acc[u][v];
             if (r >= nb || c >= nb) x = (r == c) ? 1.0 : 0.0;
             smem[c * LDS_LD + r] = (r >= c) ? x : 0.0;
-            if (zero_upper && tI[u] != tJ[u]) smem[(16 * tI[u] + hi + 4 * v) * LDS_LD + 16 * tJ[u] + lo] = 0.0;  // element (16 J + lo, 16 I + hi + 4 v)
         }
     }
     __syncthreads();
 }
 
-// MODE 0: the tiles of the step in launch order (pack / npair / two); 1: planned units (a.plan).
-template <int MODE>
+// Workgroup 0: the diagonal tile (k, k).  Workgroup 1 + u: unit u of this step's list (mid_plan_build) -- one trailing tile
+// (row, column) and the panels it receives in one product, on waves 0-3 like one workgroup of gemm_tn_f64_kernel; the
+// other four waves keep its barriers company.  (Measured and dropped: two units per workgroup in the steps of more than
+// one round of tiles -- 6.15 against 5.77 ms per factorisation at n = 8 000.)
 __global__ __launch_bounds__(MID_THREADS) void chol_mid_step_kernel(MidArgs a) {
     __shared__ __attribute__((aligned(16))) double smem[P2_S_DOUBLES + P2_WD_DOUBLES];
-    static_assert(P2_S_DOUBLES + P2_WD_DOUBLES >= 8 * TILE_DOUBLES, "two GEMM halves fit the diagonal kernel's LDS");
+    static_assert(P2_S_DOUBLES + P2_WD_DOUBLES >= 4 * TILE_DOUBLES, "the GEMM stages fit the diagonal kernel's LDS");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = wave >> 2, w4 = wave & 3;
-    const int wi = w4 & 1, wj = w4 >> 1;
-    const int lo = lane & 15, hi = lane >> 4;
-    const int k = a.k, rem = a.nblk - k;
-    const bool diag = (blockIdx.x == 0);
+    const int k = a.k;
     MID_STAMP(0);
-    int ip = 0, jp = 0, kpan = 1;  // tile (k + ip, k + jp); panels this tile receives (the last kpan ones before k)
-    int pan0 = k - 1;              // ... starting with this one
-    bool active;
-    if (MODE != 0) {
-        // Planned units (round 4, mid_plan_build): workgroup 1 + u takes unit u of this step's list -- one trailing tile
-        // (row, column) and the panels it receives in one product; the other four waves keep its barriers company.
-        // (Measured and dropped: two units per workgroup in the steps of more than one round of tiles -- 6.15 against
-        // 5.77 ms per factorisation at n = 8 000.)
-        active = (half == 0);
-        if (!diag) {
-            const uint32_t e = a.plan[(int)blockIdx.x - 1];
-            ip = (int)(e & 255u) - k;
-            jp = (int)((e >> 8) & 255u) - k;
-            pan0 = (int)((e >> 16) & 255u);
-            kpan = (int)(e >> 24);
-        }
-        kpan = __builtin_amdgcn_readfirstlane(kpan);
-        pan0 = __builtin_amdgcn_readfirstlane(pan0);
-    } else if (MODE == 0 && !a.two) {
-        // tile t = i'(i'+1)/2 + j' (0 <= j' <= i' < rem) is (k + i', k + j'); t = 0, the diagonal tile, is workgroup 0
-        const int ntiles = rem * (rem + 1) / 2;
-        const int wg = (int)blockIdx.x - 1;  // 0-based among the workgroups of the trailing tiles
-        const bool paired = a.pack == 2 && wg < a.npair;
-        const int t = diag ? 0 : (paired || a.pack == 1 ? 1 + a.pack * wg + half : 1 + 2 * a.npair + (wg - a.npair));
-        active = diag ? (half == 0) : (t < ntiles && (paired ? true : half == 0));
-        if (active && !diag) {
-            ip = (int)((sqrtf(1.0f + 8.0f * (float)t) - 1.0f) * 0.5f);
-            while (ip * (ip + 1) / 2 > t) --ip;
-            while ((ip + 1) * (ip + 2) / 2 <= t) ++ip;
-            jp = t - ip * (ip + 1) / 2;
-        }
-    } else if (MODE == 0) {
-        // Two panels per pass (round 4).  Step k touches only the tile COLUMNS of its own parity, k, k+2, k+4, ..: each
-        // receives the two panels k-2 and k-1 in ONE product (K = 256; step 1: panel 0 alone), so a trailing tile is read
-        // and written every second step -- half the HBM traffic that bound the first 17 steps.  Column k itself is in
-        // that class, so the panel of this step is up to date; its diagonal tile is the diagonal workgroup's (one panel:
-        // the tile got panel k-2 as "next diagonal tile" in step k-1), and workgroup 1 gives the NEXT diagonal tile
-        // (k+1, k+1) panel k-1 alone, so that step k+1 again finds a tile that lacks one panel (one SYRK, K = 128).
-        const bool has_exc = (k + 1 < a.nblk);
-        const int wg = (int)blockIdx.x - 1 - (has_exc ? 1 : 0);  // 0-based among the workgroups of the class tiles
-        int ncls = rem - 1;
-        for (int c = 1; 2 * c < rem; ++c) ncls += rem - 2 * c;
-        if (diag) {
-            active = (half == 0);
-        } else if (has_exc && blockIdx.x == 1) {  // the next diagonal tile, alone in its workgroup (its K differs)
-            active = (half == 0);
-            ip = jp = 1;
-        } else {
-            const bool paired = a.pack == 2 && wg < a.npair;
-            const int u = paired || a.pack == 1 ? a.pack * wg + half : 2 * a.npair + (wg - a.npair);
-            active = u < ncls && (paired ? true : half == 0);
-            kpan = (k >= 2) ? 2 : 1;
-            if (active) {
-                if (u < rem - 1) {
-                    jp = 0;
-                    ip = 1 + u;
-                } else {
-                    int v = u - (rem - 1), c = 1;
-                    while (v >= rem - 2 * c) {
-                        v -= rem - 2 * c;
-                        ++c;
-                    }
-                    jp = 2 * c;
-                    ip = jp + v;
-                }
-            }
-        }
-        kpan = __builtin_amdgcn_readfirstlane(kpan);
-        pan0 = k - kpan;
+    if (blockIdx.x == 0) {
+        // C_kk - R R' -> the LDS image S[c*LDS_LD + r] (lower triangle, identity padding) -> factor
+        const int64_t i0 = (int64_t)k * NB;
+        const int nb = (int)((a.n - i0 < NB) ? (a.n - i0) : NB);
+        double* Akk = a.A + i0 + i0 * a.lda;
+        if (k > 0) mid_diag_syrk(Akk, a.A + i0 + (int64_t)(k - 1) * NB * a.lda, a.lda, nb, smem, k);
+        MID_STAMP(1);
+        MID_STAMP(2);
+        double* Wcm = a.winv + (int64_t)k * WBLK;
+        potf2_inv_body<MID_THREADS, 1>(Akk, a.lda, nb, Wcm, Wcm + NB * NB, a.info, (int32_t)i0, smem, smem + P2_S_DOUBLES,
+                                       /*tile_in_lds=*/k > 0);
+        MID_STAMP(3);
+        return;
     }
-    ip = __builtin_amdgcn_readfirstlane(ip);  // wave-uniform: the LDS-DMA rows are addressed from scalar registers
-    jp = __builtin_amdgcn_readfirstlane(jp);
-    const int64_t i0 = (int64_t)(k + ip) * NB, j0 = (int64_t)(k + jp) * NB;
-    const int64_t npad = (int64_t)a.nblk * NB;
-    double* lds = smem + half * (4 * TILE_DOUBLES);
+    // (a step has units only once there are panels: k > 0)
+    const uint32_t e = a.plan[(int)blockIdx.x - 1];
+    // wave-uniform: the LDS-DMA rows are addressed from scalar registers
+    const int bi = __builtin_amdgcn_readfirstlane((int)(e & 255u));
+    const int bj = __builtin_amdgcn_readfirstlane((int)((e >> 8) & 255u));
+    const int pan0 = __builtin_amdgcn_readfirstlane((int)((e >> 16) & 255u));
+    const int kpan = __builtin_amdgcn_readfirstlane((int)(e >> 24));
+    const int64_t i0 = (int64_t)bi * NB, j0 = (int64_t)bj * NB;
+    if (wave >= 4) {
+        const int nbar = kpan * (NB / BK) + 1;
+        for (int b = 0; b < nbar; ++b) __builtin_amdgcn_s_barrier();
+        return;
+    }
+    const int wi = wave & 1, wj = wave >> 1;
+    const int lo = lane & 15, hi = lane >> 4;
+    GemmArgs g{};
+    g.X = a.A + (int64_t)pan0 * NB * a.lda;  // kpan panels from pan0 on: their columns are contiguous
+    g.Y = g.X;
+    g.ldx = g.ldy = a.lda;
+    g.M = g.N = a.n;
+    g.Mread = g.Nread = (int64_t)a.nblk * NB;
+    g.K = kpan * NB;
+    // the accumulators start at -C_ij (loads in flight while the first stage is staged; rows up to the padded
+    // order exist, what lies beyond n or above the diagonal is never stored) and come back negated
     double4_t acc[4][4];
-
-    const bool own_syrk = diag && k > 0 && a.dsyrk;  // (uniform over the workgroup)
-    if (own_syrk) {
-        mid_diag_syrk(a.A + i0 + i0 * a.lda, a.A + i0 + (int64_t)(k - 1) * NB * a.lda, a.lda,
-                      (int)((a.n - i0 < NB) ? (a.n - i0) : NB), smem, k, /*zero_upper=*/!a.lite);
-        MID_STAMP(1);
-    } else if (k > 0) {
-        GemmArgs g{};
-        g.X = a.A + (int64_t)pan0 * NB * a.lda;  // kpan panels from pan0 on: their columns are contiguous
-        g.Y = g.X;
-        g.ldx = g.ldy = a.lda;
-        g.M = g.N = a.n;
-        g.Mread = g.Nread = npad;
-        g.K = kpan * NB;
-        if (!active) {  // the other half of the workgroup has a tile: keep its barriers company (same K: see the pairing)
-            const int nbar = kpan * (NB / BK) + 1;
-            for (int b = 0; b < nbar; ++b) __builtin_amdgcn_s_barrier();
-        } else {
-            // the accumulators start at -C_ij (loads in flight while the first stage is staged; rows up to the padded
-            // order exist, what lies beyond n or above the diagonal is never stored) and come back negated
 #pragma unroll
-            for (int ti = 0; ti < 4; ++ti)
+    for (int ti = 0; ti < 4; ++ti)
 #pragma unroll
-                for (int tj = 0; tj < 4; ++tj)
+        for (int tj = 0; tj < 4; ++tj)
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        int64_t gj = j0 + wj * 64 + tj * 16 + hi + 4 * v;
-                        gj = (gj < a.n) ? gj : a.n - 1;  // columns beyond n: any value will do, no branch
-                        acc[ti][tj][v] = -a.A[i0 + wi * 64 + ti * 16 + lo + gj * a.lda];
-                    }
-            mainloop_dma(g, i0, j0, lds, wi, wj, lane, w4, acc);
-        }
-        MID_STAMP(1);
-        if (active && !diag) {
+            for (int v = 0; v < 4; ++v) {
+                int64_t gj = j0 + wj * 64 + tj * 16 + hi + 4 * v;
+                gj = (gj < a.n) ? gj : a.n - 1;  // columns beyond n: any value will do, no branch
+                acc[ti][tj][v] = -a.A[i0 + wi * 64 + ti * 16 + lo + gj * a.lda];
+            }
+    mainloop_dma(g, i0, j0, smem, wi, wj, lane, wave, acc);
+    MID_STAMP(1);
 #pragma unroll
-            for (int ti = 0; ti < 4; ++ti) {
-                const int64_t gi = i0 + wi * 64 + ti * 16 + lo;
+    for (int ti = 0; ti < 4; ++ti) {
+        const int64_t gi = i0 + wi * 64 + ti * 16 + lo;
 #pragma unroll
-                for (int tj = 0; tj < 4; ++tj) {
+        for (int tj = 0; tj < 4; ++tj) {
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int64_t gj = j0 + wj * 64 + tj * 16 + hi + 4 * v;
-                        if (gi < a.n && gj < a.n && gi >= gj) a.A[gi + gj * a.lda] = -acc[ti][tj][v];
-                    }
-                }
+            for (int v = 0; v < 4; ++v) {
+                const int64_t gj = j0 + wj * 64 + tj * 16 + hi + 4 * v;
+                if (gi < a.n && gj < a.n && gi >= gj) a.A[gi + gj * a.lda] = -acc[ti][tj][v];
             }
         }
-        MID_STAMP(7);
     }
-    if (!diag) return;
-
-    // the diagonal tile: accumulators -> LDS image S[c*LDS_LD + r] (lower triangle, identity padding), factor, invert
-    double* S = smem;
-    const int nb = (int)((a.n - i0 < NB) ? (a.n - i0) : NB);
-    if (k > 0 && !own_syrk) {
-        // (the main loop ends with a barrier after its last LDS read: the staging buffers are free)
-        if (half == 0) {
-#pragma unroll
-            for (int ti = 0; ti < 4; ++ti) {
-                const int r = wi * 64 + ti * 16 + lo;
-#pragma unroll
-                for (int tj = 0; tj < 4; ++tj) {
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int c = wj * 64 + tj * 16 + hi + 4 * v;
-                        double x = -acc[ti][tj][v];
-                        if (r >= nb || c >= nb) x = (r == c) ? 1.0 : 0.0;
-                        S[c * LDS_LD + r] = (r >= c) ? x : 0.0;  // the upper triangle is the inverse's work area
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    MID_STAMP(2);
-    double* Wcm = a.winv + (int64_t)k * WBLK;
-    if (a.lite)
-        potf2_inv_body<MID_THREADS, 1>(a.A + i0 + i0 * a.lda, a.lda, nb, Wcm, Wcm + NB * NB, a.info, (int32_t)i0, S,
-                                       smem + P2_S_DOUBLES, /*tile_in_lds=*/k > 0);
-    else
-        potf2_inv_body<MID_THREADS, 0>(a.A + i0 + i0 * a.lda, a.lda, nb, Wcm, Wcm + NB * NB, a.info, (int32_t)i0, S,
-                                       smem + P2_S_DOUBLES, /*tile_in_lds=*/k > 0);
-    MID_STAMP(3);
+    MID_STAMP(7);
 }
 
 }  // namespace
 
-// ---- the A/B switches of this file, read from the environment in ONE place ---------------
+// ---- the parameters and fallback switches of this file, read from the environment in ONE place ----
 struct CholModes {
-    bool panel_inv;    // MADQP_CHOL_PANEL=inv: panel solves multiply with the 128 x 128 inverse (rounds 1-3)
-    bool lite;         // MADQP_CHOL_LITE (1): factor-only diagonal kernels + one inversion launch per factorisation
-    bool pp;           // MADQP_CHOL_PP (1): panel times inverse by panel_inv_kernel; 0: the GEMM kernel
-    int sweep_diag;    // MADQP_SWEEP_DIAG: 1 (default), 2 = sub16, 0 = inv (see sweep_diag_mode)
     bool sweep_upper;  // MADQP_SWEEP_UPPER (1): backward sweep of a mid-size factor on U = L'
     int32_t sweep_chunk;      // MADQP_SWEEP_CHUNK (64): tiles of a block row per sweep job
     bool sweep_band;          // MADQP_SWEEP_BAND (1): under a bandwidth the sweeps stay inside the band; 0: whole block rows
     int64_t mid_max;          // MADQP_CHOL_MID_MAX (13312): largest order of the mid-size schedule
-    bool mid_dsyrk, mid_two, mid_lazy;  // MADQP_CHOL_MID_DSYRK / _TWO / _LAZY (1): see factor_mid
     int mid_cap;              // MADQP_CHOL_MID_CAP (0 = from the CU count; experiments)
     int64_t wt_min, wt_max;   // MADQP_CHOL_WMIN / WMAX (6, 20): outer panel width in blocks
     int64_t band_w;           // MADQP_CHOL_BAND_W (0 = the rule of band_plan.inc): outer panel in blocks where a band limits it
 };
 static CholModes chol_modes_from_env() {
-    auto is = [](const char* name, const char* v) { return getenv(name) && strcmp(getenv(name), v) == 0; };
     auto num = [](const char* name, int64_t dflt) { return getenv(name) ? atoll(getenv(name)) : dflt; };
     auto on = [&](const char* name) { return num(name, 1) != 0; };
     CholModes m{};
-    m.panel_inv = is("MADQP_CHOL_PANEL", "inv");
-    m.lite = on("MADQP_CHOL_LITE");
-    m.pp = on("MADQP_CHOL_PP");
-    m.sweep_diag = is("MADQP_SWEEP_DIAG", "inv") ? 0 : is("MADQP_SWEEP_DIAG", "sub16") ? 2 : 1;
     m.sweep_upper = on("MADQP_SWEEP_UPPER");
     m.sweep_chunk = (int32_t)std::max<int64_t>(1, num("MADQP_SWEEP_CHUNK", 64));
     m.sweep_band = on("MADQP_SWEEP_BAND");
     m.mid_max = num("MADQP_CHOL_MID_MAX", 13312);
-    m.mid_dsyrk = on("MADQP_CHOL_MID_DSYRK");
-    // two panels per trailing pass (see the kernel): needs the diagonal workgroup's own SYRK
-    m.mid_two = m.mid_dsyrk && on("MADQP_CHOL_MID_TWO");
-    // planned visits (mid_plan_build) unless switched off; the two-panel schedule otherwise
-    m.mid_lazy = m.mid_dsyrk && on("MADQP_CHOL_MID_LAZY");
     m.mid_cap = (int)num("MADQP_CHOL_MID_CAP", 0);
     m.wt_min = num("MADQP_CHOL_WMIN", 6);
     m.wt_max = num("MADQP_CHOL_WMAX", 20);
@@ -1669,14 +1365,6 @@ static const CholModes& chol_modes() {  // filled once, at the first use
     static const CholModes m = chol_modes_from_env();
     return m;
 }
-// factor-only diagonal kernels + one inversion launch per factorisation (round 4); MADQP_CHOL_LITE=0: factor and invert in
-// the diagonal kernel as before.  Needs the block-substitution panel solve (the product with the 128-inverse reads the image).
-static bool chol_lite() { return chol_modes().lite && !chol_modes().panel_inv; }
-// The diagonal step of the sweeps: 1 = unit block substitution with normalised images (default), 2 = plain block
-// substitution over the 16 x 16 sub-blocks (MADQP_SWEEP_DIAG=sub16), 0 = the product with the stored 128 x 128 inverse of
-// rounds 1-4 (MADQP_SWEEP_DIAG=inv; also whenever the diagonal kernels factor AND invert: MADQP_CHOL_LITE=0 /
-// MADQP_CHOL_PANEL=inv, whose images are full inverses).
-static int sweep_diag_mode() { return chol_lite() ? chol_modes().sweep_diag : 0; }
 
 extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out) {
     ARG_TRY(ctx, ctx && out && n >= 0);
@@ -1897,8 +1585,9 @@ struct CholTarget {
     int64_t lda, n;
     double* winv;   // n/128 blocks of WBLK doubles (per problem)
     int32_t* info;  // one int (per problem)
-    bool lite;      // the diagonal kernel only factors (potf2_inv_kernel<1>); false: it factors and inverts (<0>)
-    bool batched = false;  // false: B = 1 and no batch part -- launches take no GemmBatch and the default Potf2Batch / PanelBatch
+    // false: B = 1 and no batch part -- launches take no GemmBatch and the default Potf2Batch / PanelBatch, and the diagonal
+    // kernel only factors (potf2_inv_kernel<1>); true: it factors and inverts (<0>: what the batched sweeps multiply with)
+    bool batched = false;
     int64_t B = 1, sA = 0, sW = 0;  // problems (list: slots) and their strides in A and winv (doubles)
     const int32_t* skip = nullptr;
     const int32_t* list = nullptr;  // compacted form (GemmBatch::list)
@@ -1948,89 +1637,45 @@ static int32_t panel_update(const CholTarget& t, int64_t row0, int64_t k0, int64
 
 // what the factor-only diagonal kernels leave out of the serial spine, for all blocks j0/128 .. in ONE launch: the
 // off-diagonal parts of the sweep images
-static int32_t invert_blocks(madqp_chol* s, double* A, int64_t lda, int64_t j0, int64_t w) {
-    if (w <= 0 || !chol_lite()) return MADQP_OK;
+static int32_t sweep_images(madqp_chol* s, double* A, int64_t lda, int64_t j0, int64_t w) {
+    if (w <= 0) return MADQP_OK;
     madqp_ctx* ctx = s->ctx;
     ProfScope ps(ctx, MADQP_PROF_POTRF_DIAG);
-    const unsigned nblk = (unsigned)((w + NB - 1) / NB);
-    if (sweep_diag_mode() == 0)
-        hipLaunchKernelGGL(potf2_invert_kernel, dim3(nblk), dim3(P2_KTHREADS), 0, ctx->stream, A, lda, s->n, j0, s->winv);
-    else
-        hipLaunchKernelGGL(sweep_image_kernel, dim3(nblk), dim3(256), 0, ctx->stream, A, lda, s->n, j0, s->winv,
-                           sweep_diag_mode() != 2 ? 1 : 0);
+    hipLaunchKernelGGL(sweep_image_kernel, dim3((unsigned)((w + NB - 1) / NB)), dim3(256), 0, ctx->stream, A, lda, s->n, j0, s->winv);
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
-}
-template <int DIAG>
-static void launch_sweep(bool bwd, unsigned grid, hipStream_t st, const double* L, int64_t ld, const double* winv, const double* in,
-                         double* out, int64_t n, int32_t* ctl, double* fault, int vec, const SweepPlan& plan, int kb) {
-    if (bwd)
-        hipLaunchKernelGGL(trsv_bwd_sweep_kernel<DIAG>, dim3(grid), dim3(1024), 0, st, L, ld, winv, in, out, n, ctl, fault, vec, plan,
-                           kb);
-    else
-        hipLaunchKernelGGL(trsv_fwd_sweep_kernel<DIAG>, dim3(grid), dim3(1024), 0, st, L, ld, winv, in, out, n, ctl, fault, vec, plan,
-                           (double*)nullptr, kb);
 }
 // kb: the band of the sweep in blocks (band_plan.inc), -1 for the whole block rows
 static void launch_sweep(bool bwd, unsigned grid, hipStream_t st, const double* L, int64_t ld, const double* winv, const double* in,
                          double* out, int64_t n, int32_t* ctl, double* fault, int vec, const SweepPlan& plan, int kb = -1) {
-    switch (sweep_diag_mode()) {
-        case 0: launch_sweep<0>(bwd, grid, st, L, ld, winv, in, out, n, ctl, fault, vec, plan, kb); break;
-        case 2: launch_sweep<2>(bwd, grid, st, L, ld, winv, in, out, n, ctl, fault, vec, plan, kb); break;
-        default: launch_sweep<1>(bwd, grid, st, L, ld, winv, in, out, n, ctl, fault, vec, plan, kb); break;
-    }
+    if (bwd)
+        hipLaunchKernelGGL(trsv_bwd_sweep_kernel, dim3(grid), dim3(1024), 0, st, L, ld, winv, in, out, n, ctl, fault, vec, plan, kb);
+    else
+        hipLaunchKernelGGL(trsv_fwd_sweep_kernel<false>, dim3(grid), dim3(1024), 0, st, L, ld, winv, in, out, n, ctl, fault, vec, plan,
+                           (double*)nullptr, kb);
 }
 
-// The panel solve of ONE block of w <= 128 columns: X (rows x w, leading dimension ldx; rows_read >= rows of them exist
-// in memory) <- X L^-T for the factored diagonal block L (ldl) whose inverse image is Wcm.  Three forms:
-//   block substitution with the 16 x 16 diagonal inverses (panel_sub16_kernel): the default, every whole block;
-//   MADQP_CHOL_PANEL=inv brings back the products with the 128 x 128 inverse of rounds 1-3 (for the A/B numbers in
-//   DESIGN.md) -- by panel_inv_kernel where the caller asks for it (inv = PANEL_INV_KERNEL: rows_read must be the rows
-//   up to the padded order) -- or by the GEMM kernel, which also serves a short last block.
+// The panel solve of ONE 128-column block: X (rows x 128, leading dimension ldx; rows_read >= rows of them exist in memory)
+// <- X L^-T for the factored diagonal block L (ldl), by block substitution with the 16 x 16 diagonal inverses that the
+// diagonal kernel left in the image Wcm (panel_sub16_kernel).  A short block (w < 128) is the last of its matrix or tile in
+// every caller and has no rows below it.
 // batch: a batched target, for its batch part (the same solve for its B problems); nullptr: one matrix.
 int32_t madqp_chol_panel_solve(madqp_ctx* ctx, double* X, int64_t ldx, int64_t rows, int64_t rows_read, const double* L,
-                               int64_t ldl, const double* Wcm, int64_t w, PanelInvForm inv, const CholTarget* batch) {
+                               int64_t ldl, const double* Wcm, int64_t w, const CholTarget* batch) {
     if (rows <= 0) return MADQP_OK;
+    ARG_TRY(ctx, w == NB);
     ARG_TRY(ctx, rows_read >= rows && (!batch || (batch->B >= 1 && batch->B <= 65535)));
-    if (w == NB && !chol_modes().panel_inv) {
-        ProfScope ps(ctx, MADQP_PROF_POTRF_TRSM);
-        const PanelBatch bt = batch ? PanelBatch{batch->sA, batch->sA, batch->sW, batch->skip, batch->list, batch->count}
-                                    : PanelBatch{0, 0, 0, nullptr};
-        hipLaunchKernelGGL(panel_sub16_kernel, dim3((unsigned)((rows + 63) / 64), (unsigned)(batch ? batch->B : 1)), dim3(256), 0,
-                           ctx->stream, X, ldx, L, ldl, Wcm, rows, rows_read, bt);
-        LAUNCH_CHECK(ctx);
-        return MADQP_OK;
-    }
-    // whole block and few rows below it (one register-heavy workgroup per CU: beyond ~24 000 rows -- 3 rounds -- the GEMM
-    // kernel's 128-row tiles, which read W once per 128 rows, are the faster form: n = 50 000 measured 1 316-1 319 against
-    // 1 311-1 315 ms per iteration with this kernel on every block)
-    if (w == NB && inv == PANEL_INV_KERNEL && !batch && rows_read % 32 == 0 && chol_modes().pp && rows <= 24576) {
-        ProfScope ps(ctx, MADQP_PROF_POTRF_TRSM);
-        hipLaunchKernelGGL(panel_inv_kernel, dim3((unsigned)(rows_read / 32)), dim3(256), 0, ctx->stream, X, ldx, Wcm, rows);
-        LAUNCH_CHECK(ctx);
-        return MADQP_OK;
-    }
-    // out[i,j] = sum_k C[i,k] W(j,k); in place: a single tile column, every workgroup reads
-    // exactly the rows it writes and finishes reading (K = w, all stages) before its stores.
-    GemmArgs g{};
-    g.X = X;
-    g.ldx = ldx;
-    g.Y = Wcm;  // Y[j + k*NB] = W(j,k)
-    g.ldy = NB;
-    g.C = X;
-    g.ldc = ldx;
-    g.alpha = 1.0;
-    g.beta = 0.0;
-    g.M = rows;
-    g.N = w;
-    g.K = w;
-    g.Mread = rows_read;  // (the GEMM kernel treats 0 and M alike)
-    g.Nread = NB;         // the inverse block image is always 128 x 128, zero padded
-    return batch ? target_gemm(*batch, g, MADQP_PROF_POTRF_TRSM, batch->sW, 0) : madqp_gemm_tn(ctx, g, MADQP_PROF_POTRF_TRSM);
+    ProfScope ps(ctx, MADQP_PROF_POTRF_TRSM);
+    const PanelBatch bt = batch ? PanelBatch{batch->sA, batch->sA, batch->sW, batch->skip, batch->list, batch->count}
+                                : PanelBatch{0, 0, 0, nullptr};
+    hipLaunchKernelGGL(panel_sub16_kernel, dim3((unsigned)((rows + 63) / 64), (unsigned)(batch ? batch->B : 1)), dim3(256), 0,
+                       ctx->stream, X, ldx, L, ldl, Wcm, rows, rows_read, bt);
+    LAUNCH_CHECK(ctx);
+    return MADQP_OK;
 }
 
 // One 128-column block whose entries already carry every update from the columns to its left:
-// factor the diagonal block (and invert it), then L[below, jb] = C[below, jb] * W_jj'.
+// factor the diagonal block (a batched target: and invert it), then L[below, jb] = C[below, jb] L_jj^-T.
 // rows_below >= 0 (band schedule): the panel solve covers that many rows only -- whole 128-row tiles, or up to n.
 static int32_t factor_block(const CholTarget& t, int64_t jb, int64_t w, int64_t rows_below = -1) {
     madqp_ctx* ctx = t.ctx;
@@ -2039,16 +1684,16 @@ static int32_t factor_block(const CholTarget& t, int64_t jb, int64_t w, int64_t 
     {
         ProfScope ps(ctx, MADQP_PROF_POTRF_DIAG);
         const Potf2Batch bt = t.batched ? Potf2Batch{t.sA, t.sW, 1, t.skip, t.list, t.count} : Potf2Batch{0, 0, 0, nullptr};
-        const auto diag_kernel = t.lite ? potf2_inv_kernel<1> : potf2_inv_kernel<0>;
+        const auto diag_kernel = t.batched ? potf2_inv_kernel<0> : potf2_inv_kernel<1>;
         hipLaunchKernelGGL(diag_kernel, dim3((unsigned)t.B), dim3(P2_KTHREADS), 0, ctx->stream, Ajj, t.lda, (int)w, Wcm,
                            Wcm + NB * NB, t.info, (int32_t)jb, bt);
         LAUNCH_CHECK(ctx);
     }
-    // the rows below the block; panel_inv_kernel serves one matrix with rows up to the padded order only
+    // the rows below the block
     const int64_t rows = rows_below >= 0 ? rows_below : t.n - jb - w;
     const int64_t rows_pad = rows_below >= 0 ? (rows + NB - 1) / NB * NB : t.npad() - jb - w;
     return madqp_chol_panel_solve(ctx, Ajj + w, t.lda, rows, t.padded() ? rows_pad : rows, Ajj, t.lda, Wcm, w,
-                                  !t.batched && t.padded() ? PANEL_INV_KERNEL : PANEL_INV_GEMM, t.batched ? &t : nullptr);
+                                  t.batched ? &t : nullptr);
 }
 
 // Recursive left-looking factorisation of the columns [j0, j0+w), which already carry the updates
@@ -2065,7 +1710,7 @@ static int32_t factor_range(const CholTarget& t, int64_t j0, int64_t w) {
 }
 // the one matrix of a handle as a target
 static CholTarget chol_target(madqp_chol* s, double* A, int64_t lda) {
-    CholTarget t{s->ctx, A, lda, s->n, s->winv, s->d_info, chol_lite()};
+    CholTarget t{s->ctx, A, lda, s->n, s->winv, s->d_info};
     t.packed = s->packed;
     return t;
 }
@@ -2082,7 +1727,7 @@ static CholTarget chol_target(madqp_chol* s, double* A, int64_t lda) {
 // used up is visited whatever the budget.  `rounds` is the smallest count for which no visit ever needs more than
 // MID_Q panels: 1 up to n = 5 120 on 256 CUs (every step then fits the shadow of the chain: 40 steps of ~47 us at
 // n = 5 000 instead of 8 of them at ~90 us), 2-4 up to 10 240, 5-6 up to 13 312.  The plan depends on (number of blocks, cap) only.
-// builds and uploads the plan of s (once); false: no plan (the caller runs the two-panel schedule)
+// builds and uploads the plan of s (once; nothing is queued); false: no plan (the caller takes the left-looking driver)
 static bool mid_plan_build(madqp_chol* s, int nblk, int cap) {
     if (s->mid_plan_state) return s->mid_plan_state > 0;
     s->mid_plan_state = -1;
@@ -2095,7 +1740,7 @@ static bool mid_plan_build(madqp_chol* s, int nblk, int cap) {
     std::vector<uint32_t> w;
     s->mid_units = new (std::nothrow) int32_t[2 * nblk];
     if (!s->mid_units) return false;
-    // every failure exit leaves the handle without a plan AND without its pieces (the fallback schedule runs next: no
+    // every failure exit leaves the handle without a plan AND without its pieces (the left-looking driver runs next: no
     // sticky HIP error may reach its first launch check)
     auto give_up = [&]() {
         (void)hipGetLastError();
@@ -2122,12 +1767,11 @@ static bool mid_plan_build(madqp_chol* s, int nblk, int cap) {
     return true;
 }
 
-// The mid-size schedule (chol_mid_step_kernel): right-looking, two launches per 128-column block, then the inverse images and
-// U = L'.  n > 128, s->npos == n, lda >= the padded order and even, A 16-byte aligned (chol_factor_enqueue checks).
+// The mid-size schedule (chol_mid_step_kernel): right-looking, two launches per 128-column block, then the sweep images and
+// U = L'.  n > 128, s->npos == n, lda >= the padded order and even, A 16-byte aligned, the plan built (chol_factor_enqueue checks).
 static int32_t factor_mid(madqp_chol* s, double* A, int64_t lda) {
     madqp_ctx* ctx = s->ctx;
     const int64_t n = s->n;
-    const CholModes& md = chol_modes();
     const int64_t npad_m = (n + NB - 1) / NB * NB;
     const int32_t nblk = (int32_t)(npad_m / NB);
     // one timer scope for the whole factorisation (80 short launches: a scope each costs 0.7 ms per factorisation
@@ -2139,55 +1783,20 @@ static int32_t factor_mid(madqp_chol* s, double* A, int64_t lda) {
         explicit ProfMute(madqp_ctx* ctx_) : c(ctx_), saved(ctx_->prof) { c->prof = 0; }
         ~ProfMute() { c->prof = saved; }
     } mute(ctx);
-    const bool planned = md.mid_lazy && mid_plan_build(s, nblk, md.mid_cap > 0 ? md.mid_cap : ctx->gemm_slots / 2 - 1);
     for (int32_t k = 0; k < nblk; ++k) {
-        if (planned) {
-            hipLaunchKernelGGL(chol_mid_step_kernel<1>, dim3((unsigned)(1 + s->mid_units[k])), dim3(MID_THREADS), 0,
-                               ctx->stream,
-                               MidArgs{A, lda, n, nblk, k, 1, 0, chol_lite() ? 1 : 0, 1, 0,
-                                       s->d_mid_plan + s->mid_units[nblk + k], s->winv, s->d_info});
-            LAUNCH_CHECK(ctx);
-        } else {
-            const int64_t rem = nblk - k;
-            int64_t nt, extra = 0;  // tiles shared out by pack/npair; workgroups before them besides the diagonal one
-            if (k == 0) {
-                nt = 0;
-            } else if (!md.mid_two) {
-                nt = rem * (rem + 1) / 2 - 1;
-            } else {
-                nt = rem - 1;  // column k below its diagonal tile, then columns k+2, k+4, ..
-                for (int64_t c = 1; 2 * c < rem; ++c) nt += rem - 2 * c;
-                extra = (k + 1 < nblk) ? 1 : 0;  // the next diagonal tile
-            }
-            // One workgroup per CU (LDS), one or two tiles each.  Up to a round of single tiles: singles; up to a round
-            // of pairs: pairs; beyond that -- two rounds -- as few pairs as two rounds of workgroups need, FIRST in the
-            // grid, singles behind them: a CU then works off three tiles (pair + single or three singles, 44 + 22 us)
-            // instead of four (two pairs, 88 us) whenever three per CU are enough (up to 765 tiles).
-            const int64_t cus = ctx->gemm_slots / 2 - 1 - extra;  // (the diagonal workgroup holds a CU)
-            int32_t pack = (nt > cus) ? 2 : 1, npair = 0;
-            unsigned grid = (unsigned)(1 + extra + (nt + pack - 1) / pack);
-            if (pack == 2) {
-                npair = (int32_t)((nt + 1) / 2);
-                if (nt > 2 * cus && nt - 2 * cus <= cus) {
-                    npair = (int32_t)(nt - 2 * cus);
-                    grid = (unsigned)(1 + extra + npair + (nt - 2 * (int64_t)npair));
-                }
-            }
-            hipLaunchKernelGGL(chol_mid_step_kernel<0>, dim3(grid), dim3(MID_THREADS), 0, ctx->stream,
-                               MidArgs{A, lda, n, nblk, k, pack, npair, chol_lite() ? 1 : 0, md.mid_dsyrk ? 1 : 0,
-                                       md.mid_two ? 1 : 0, nullptr, s->winv, s->d_info});
-            LAUNCH_CHECK(ctx);
-        }
-        // L[below, jb] = C[below, jb] L_kk^-T (the leading dimension is padded: panel_inv_kernel under MADQP_CHOL_PANEL=inv)
+        hipLaunchKernelGGL(chol_mid_step_kernel, dim3((unsigned)(1 + s->mid_units[k])), dim3(MID_THREADS), 0, ctx->stream,
+                           MidArgs{A, lda, n, nblk, k, s->d_mid_plan + s->mid_units[nblk + k], s->winv, s->d_info});
+        LAUNCH_CHECK(ctx);
+        // L[below, jb] = C[below, jb] L_kk^-T
         const int64_t jb = (int64_t)k * NB;
         const int32_t r = madqp_chol_panel_solve(ctx, A + (jb + NB) + jb * lda, lda, n - jb - NB, npad_m - jb - NB,
-                                                 A + jb + jb * lda, lda, s->winv + (int64_t)k * WBLK, NB, PANEL_INV_KERNEL);
+                                                 A + jb + jb * lda, lda, s->winv + (int64_t)k * WBLK, NB);
         if (r) return r;
     }
-    const int32_t ri = invert_blocks(s, A, lda, 0, n);  // the inverse images of all blocks, one launch (factor-only diagonal kernels)
+    const int32_t ri = sweep_images(s, A, lda, 0, n);  // of all blocks, one launch
     if (ri) return ri;
-    // U = L' for the backward sweep (trsv_fwd_sweep_kernel<1, true>): one pass over the factor, 37 us at n = 5 000
-    if (md.sweep_upper && s->utmp && sweep_diag_mode() == 1) {
+    // U = L' for the backward sweep (trsv_fwd_sweep_kernel<true>): one pass over the factor, 37 us at n = 5 000
+    if (chol_modes().sweep_upper && s->utmp) {
         if (!s->upper) {
             if (hipMalloc(&s->upper, (size_t)npad_m * npad_m * sizeof(double)) != hipSuccess) {
                 (void)hipGetLastError();
@@ -2218,7 +1827,7 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
                                                     : factor_block(t, o.row0, o.width, o.rows);
             if (r) return r;
         }
-        return invert_blocks(s, A, lda, 0, n);
+        return sweep_images(s, A, lda, 0, n);
     }
     // mid-size matrices: right-looking, two launches per 128-column block (chol_mid_step_kernel)
     // (measured on bench.py, m = 0.4 n, ms per iteration against the left-looking schedule: 3.34 / 3.90 at n = 3 000,
@@ -2226,8 +1835,11 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
     // the whole trailing matrix, which the left-looking schedule does not)
     // (round 5, with the backward sweep on U = L' behind this path -- ms per iteration, this path / left-looking: 19.1 / 21.0 at
     // n = 10 000, 23.7 / 25.4 at 11 000, 29.2 / 30.5 at 12 000, 35.5 / 36.4 at 13 000, 42.8 / 42.6 at 14 000, 60.8 / 58.1 at 16 000)
-    if (n <= chol_modes().mid_max && n > NB && s->npos == n && lda >= (n + NB - 1) / NB * NB && lda % 2 == 0 &&
-        (((uintptr_t)A) & 15) == 0)
+    // (the plan is built before anything of the schedule is queued; without one -- no memory for it, MADQP_CHOL_MID_MAX beyond
+    // 255 blocks, fewer than 4 GEMM slots -- the left-looking driver below serves every order)
+    const CholModes& md = chol_modes();
+    if (n <= md.mid_max && n > NB && s->npos == n && lda >= (n + NB - 1) / NB * NB && lda % 2 == 0 && (((uintptr_t)A) & 15) == 0 &&
+        mid_plan_build(s, (int)((n + NB - 1) / NB), md.mid_cap > 0 ? md.mid_cap : ctx->gemm_slots / 2 - 1))
         return factor_mid(s, A, lda);
     // Quasi-definite mode (npos < n): A = [P, .; B, -Q] with P, Q positive definite and Q's block STORED AS +Q.
     // A = L diag(I, -I) L' with L = [L11, 0; W, L22], W = B L11^-T, L22 L22' = Q + W W': the same left-looking
@@ -2250,7 +1862,7 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
         r = factor_range(t, J0, W);
         if (r) return r;
     }
-    return invert_blocks(s, A, lda, 0, n);
+    return sweep_images(s, A, lda, 0, n);
 }
 
 extern "C" int32_t madqp_chol_factor(madqp_chol* s, double* A, int64_t lda, int32_t* info_host) {
@@ -2316,7 +1928,7 @@ int32_t madqp_chol_factor_batched(madqp_ctx* ctx, double* A, int64_t lda, int64_
     if (n == 0) return MADQP_OK;
     HIP_TRY(ctx, hipMemsetAsync(info, 0, (size_t)B * sizeof(int32_t), ctx->stream));
     // (the diagonal kernel factors and inverts: the images are what the batched sweeps multiply with)
-    const CholTarget t{ctx, A, lda, n, winv, info, false, true, list ? slots : B, sA, sW, list ? nullptr : skip, list, count};
+    const CholTarget t{ctx, A, lda, n, winv, info, true, list ? slots : B, sA, sW, list ? nullptr : skip, list, count};
     return factor_range(t, 0, n);
 }
 
@@ -2354,7 +1966,7 @@ extern "C" int32_t madqp_chol_factor_panel(madqp_chol* s, int64_t j0, int64_t w)
     if (!s) return MADQP_ERR_ARG;
     ARG_TRY(s->ctx, panel_ok(s, j0, w) && s->bw < 0);
     const int32_t r = factor_range(chol_target(s, s->A, s->lda), j0, w);
-    return r ? r : invert_blocks(s, s->A, s->lda, j0, w);  // (the caller packs / reads the images of this panel next)
+    return r ? r : sweep_images(s, s->A, s->lda, j0, w);  // (the caller packs / reads the images of this panel next)
 }
 
 // buf = [info, 0 | inverse diagonal blocks of the panel | L[j0:n, j0+c] for c = 0..w-1]
@@ -2411,9 +2023,9 @@ extern "C" int32_t madqp_chol_solve(madqp_chol* s, double* rhs) {
         double* fault = ctx->d_res + MADQP_FAULT_SLOT;
         hipLaunchKernelGGL(sweep_prep_kernel, dim3((unsigned)std::min<int64_t>((s->utmp_len + 255) / 256, 256)), dim3(256), 0,
                            ctx->stream, reinterpret_cast<unsigned long long*>(s->utmp), s->utmp_len, s->d_info);
-        hipLaunchKernelGGL((trsv_fwd_sweep_kernel<1, false>), dim3(grid), dim3(1024), 0, ctx->stream, A, lda, s->winv,
+        hipLaunchKernelGGL(trsv_fwd_sweep_kernel<false>, dim3(grid), dim3(1024), 0, ctx->stream, A, lda, s->winv,
                            (const double*)rhs, yv, n, s->d_info, fault, 1, pf, (double*)nullptr, -1);
-        hipLaunchKernelGGL((trsv_fwd_sweep_kernel<1, true>), dim3(grid), dim3(1024), 0, ctx->stream, (const double*)s->upper,
+        hipLaunchKernelGGL(trsv_fwd_sweep_kernel<true>, dim3(grid), dim3(1024), 0, ctx->stream, (const double*)s->upper,
                            s->upper_ld, s->winv, (const double*)yv, xv, n, s->d_info, fault, 1, pb, rhs, -1);
         LAUNCH_CHECK(ctx);
         return MADQP_OK;

@@ -211,13 +211,12 @@ int32_t madqp_sparse_gram_band(madqp_ctx* ctx, int64_t n, const int64_t* rowptr,
                                const double* dvec, const int64_t* b_ptr, const int64_t* b_col, const double* b_val,
                                double* C, int64_t ldc, int64_t bw, int64_t extent);
 
-// chol.hip: the panel solve of one block of w <= 128 columns, X (rows x w) <- X L^-T (see there).  inv: how the products
-// with the 128 x 128 inverse (MADQP_CHOL_PANEL=inv) are formed -- the GEMM kernel, or panel_inv_kernel where it can serve.
-enum PanelInvForm { PANEL_INV_GEMM, PANEL_INV_KERNEL };
+// chol.hip: the panel solve of one 128-column block, X (rows x 128) <- X L^-T by block substitution (see there); w < 128 only
+// with rows <= 0 (a short block is the last of its matrix or tile).  (The products with the 128 x 128 inverse of rounds
+// 1-3 were removed; their A/B numbers: DESIGN.md 4.1 and 5.2.)
 struct CholTarget;
 int32_t madqp_chol_panel_solve(madqp_ctx* ctx, double* X, int64_t ldx, int64_t rows, int64_t rows_read, const double* L,
-                               int64_t ldl, const double* Wcm, int64_t w, PanelInvForm inv,
-                               const CholTarget* batch = nullptr);
+                               int64_t ldl, const double* Wcm, int64_t w, const CholTarget* batch = nullptr);
 // chol.hip: one triangular sweep over an order-w tile whose factor and inverse diagonal blocks are given (dist.hip):
 // trans = 0: v <- L^-1 v, trans = 1: v <- L^-T v.  tmp: w doubles, ctl: 4 ints of device scratch.
 int32_t madqp_trsv_tile(madqp_ctx* ctx, int32_t trans, const double* L, int64_t ld, const double* winv, double* v,

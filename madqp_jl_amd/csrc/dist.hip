@@ -255,12 +255,12 @@ int32_t dop_panel_local(Dev* dev, double* K, int64_t ld, int64_t lc, int64_t k, 
     return 0;
 }
 
-// X (rows x w, leading dimension ldx) <- X L^-T with the inverse 128-blocks W of L's diagonal (recursive, MFMA)
+// X (rows x w, leading dimension ldx) <- X L^-T with the images W of L's diagonal 128-blocks (recursive, MFMA)
 int32_t trsm_range(Dev* dev, double* X, int64_t ldx, int64_t rows, int64_t rread, const double* L, int64_t ldl,
                    const double* W, int64_t j0, int64_t wd) {
-    if (wd <= 128)  // one block: block substitution (chol.hip); a short last block of a tile: the product with its inverse image
+    if (wd <= 128)  // one block: block substitution (chol.hip); only the last tile has a short block, and no tile rows below it
         return madqp_chol_panel_solve(dev->ctx, X + j0 * ldx, ldx, rows, rread, L + j0 + j0 * ldl, ldl,
-                                      W + (j0 / 128) * (2 * 128 * 128), wd, PANEL_INV_GEMM);
+                                      W + (j0 / 128) * (2 * 128 * 128), wd);
     const int64_t h = ((wd + 127) / 128 + 1) / 2 * 128;
     int32_t r = trsm_range(dev, X, ldx, rows, rread, L, ldl, W, j0, h);
     if (r) return r;

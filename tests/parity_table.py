@@ -137,8 +137,7 @@ def main():
                     **{f"over_{t}": int((v > t).sum()) for t in (1, 2, 4, 8, 16)})
 
     out = dict(what="device (native driver) distance from the LAPACK oracle in units of the CPU noise floor; 0 = within the "
-                    "stated bar", library_panel=os.environ.get("MADQP_CHOL_PANEL", "sub16"),
-               library_sweep_diag=os.environ.get("MADQP_SWEEP_DIAG", "nrm16"),
+                    "stated bar",
                summary={f"refine{rs}": dict(vs_ensemble=summary(f"refine{rs}", "vs_ensemble"),
                                             vs_two_runs=summary(f"refine{rs}", "vs_two_runs"))
                         for rs in a.refine.split(",")},

@@ -58,10 +58,18 @@ def check(nblk, cap, rounds, rows, units):
 def test_plans_are_complete_and_in_order(lib, cap):
     for nblk in list(range(1, 34)) + [40, 47, 56, 63, 64, 79, 80]:
         rounds, rows, units = plan(lib, nblk, cap)
-        if rounds == 0:  # no plan within 64 rounds per step (a sliver of a GPU): the library keeps its older schedule
+        if rounds == 0:  # no plan within 64 rounds per step (a sliver of a GPU): the library takes its left-looking driver
             assert cap == 7 and nblk >= 40 and len(rows) == 0
             continue
         check(nblk, cap, rounds, rows, units)
+
+
+def test_reduced_caps_still_plan_the_orders_of_the_gpu_test(lib):
+    # tests/test_gpu_dense.py::test_mid_size_schedules_factor_the_same_matrix compares the factors under MADQP_CHOL_MID_CAP=63
+    # and =31 with the default's: without a plan those runs would take the left-looking driver and compare nothing
+    for n in (129, 257, 1000, 2500, 5001, 12900):
+        for cap in (63, 31):
+            assert plan(lib, (n + 127) // 128, cap)[0] >= 1, (n, cap)
 
 
 def test_one_round_per_step_up_to_forty_blocks_on_a_whole_gpu(lib):
