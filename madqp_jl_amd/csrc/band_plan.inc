@@ -1,7 +1,7 @@
 // Schedule of the band-limited left-looking factorisation (see chol.hip, "band driver") and, at the end, the job lists of
-// the triangular sweeps under a band: plain C++, shared by chol.hip and the CPU test builds
-// tests/csrc_band/band_plan_cpu.cpp and tests/csrc_band_sweep/band_sweep_cpu.cpp.  The matrix is dense, column-major and of order n with
-// half-bandwidth bw (A[i,j] = 0 for i - j > bw); a factor without pivoting stays inside the band, so every product and
+// the triangular sweeps under a band with band_sweep_range, the one place that says which tiles a sweep job reads: plain
+// C++17, shared by chol.hip (host code and both sweep kernels) and the CPU test build tests/csrc_band (one library, three
+// sanitized check programs).  The matrix is dense, column-major and of order n with half-bandwidth bw (A[i,j] = 0 for i - j > bw); a factor without pivoting stays inside the band, so every product and
 // every panel solve of the dense schedule is cut down to the rows and the k-range the band can reach.
 #include <algorithm>
 #include <cstdint>
@@ -124,18 +124,49 @@ static bool band_packed_layout(int64_t n, int64_t extent, int64_t ld_in, int64_t
 // reaches min(band_up(bw) + 127, n - 1) for n >= 128.  The backward sweep is the same in chain coordinates (position rr
 // is block nblk - 1 - rr, its tiles are counted from the last block row).
 static int64_t band_sweep_blocks(int64_t bw) { return band_up(bw) / BAND_NB; }
+// the first tile of block row r by the sentence above: what the CPU checks hold band_sweep_range (below) to, not used by it
 static int64_t band_sweep_lo(int64_t r, int64_t kb) { return kb < 0 ? 0 : std::max<int64_t>(0, r - kb); }
 static int64_t band_sweep_reach(int64_t n, int64_t kb) { return std::min(n - 1, kb * BAND_NB + BAND_NB - 1); }
 
-// The job list of one sweep over nblk block rows (ticket -> r | c << 20, ordered by (r, c)): chunk c of row r stands for
-// the tiles [c chunk, min(r, (c + 1) chunk)), and under a band only the chunks that meet [lo(r), r) are jobs -- c from
-// lo(r) / chunk on; the last chunk owns the row and is a job even where the row has no tile (r = 0, kb = 0).  kb < 0 or
-// kb >= nblk - 1: every chunk, the dense list.  Returns the most chunks any row has (the stride of the partial-sum slots).
+// What job (r, c) of a sweep reads -- both sweep kernels and every CPU check call this: the tiles [j0, j1) of block row r
+// (the backward sweep: of position r of the chain), whether the job owns the row (it holds the tile next to the diagonal
+// block, solves the block and publishes it), and clo, the first chunk whose partial sums the owner adds.  split: the row
+// is cut into chunks of `chunk` tiles along a job list; without one, job r is the whole row (c = 0).  Under a band of kb
+// blocks (negative: none) the tiles before r - kb hold nothing of the factor: they are not read, and the chunks before
+// the one that holds tile r - kb are no jobs and publish nothing.
+#ifdef __HIPCC__
+#define BAND_HOST_DEVICE __host__ __device__
+#else
+#define BAND_HOST_DEVICE
+#endif
+struct BandSweepRange {
+    int j0, j1, clo;
+    bool owner;
+};
+BAND_HOST_DEVICE static inline BandSweepRange band_sweep_range(int r, int c, int chunk, int kb, bool split) {
+    int j0 = 0, j1 = r, clo = 0;
+    if (split) {
+        j0 = c * chunk;
+        j1 = (j0 + chunk < r) ? j0 + chunk : r;
+    }
+    if (kb >= 0 && r > kb) {
+        const int lo = r - kb;
+        j0 = j0 > lo ? j0 : lo;
+        if (split) clo = lo / chunk;
+    }
+    return {j0, j1, clo, j1 == r};
+}
+
+// The job list of one sweep over nblk < 2^20 block rows (ticket -> r | c << 20, ordered by (r, c)): the chunks of row r
+// from the owner's first one (band_sweep_range) on; the last chunk owns the row and is a job even where the row has no
+// tile (r = 0, kb = 0).  kb < 0 or kb >= nblk - 1: every chunk, the dense list.  Returns the most chunks any row has (the
+// stride of the partial-sum slots).
 static int64_t band_sweep_jobs(int64_t nblk, int64_t kb, int64_t chunk, std::vector<int32_t>& jobs) {
     jobs.clear();
     for (int64_t r = 0; r < nblk; ++r) {
         const int64_t nc = std::max<int64_t>(1, (r + chunk - 1) / chunk);
-        for (int64_t c = std::min(band_sweep_lo(r, kb) / chunk, nc - 1); c < nc; ++c) jobs.push_back((int32_t)(r | (c << 20)));
+        const int64_t clo = band_sweep_range((int)r, 0, (int)chunk, (int)kb, true).clo;
+        for (int64_t c = std::min(clo, nc - 1); c < nc; ++c) jobs.push_back((int32_t)(r | (c << 20)));
     }
     return std::max<int64_t>(1, (nblk - 1 + chunk - 1) / chunk);
 }

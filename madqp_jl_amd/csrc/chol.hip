@@ -19,7 +19,8 @@
 // sub-blocks off it normalised with them) and turn the diagonal solves of the two triangular sweeps into eight
 // substitution steps on one wave; each sweep is ONE launch of
 // ticket-ordered workgroups handing the solved blocks on through a sentinel-tagged vector, HBM bound
-// (4 n^2 bytes); block rows longer than 64 tiles are streamed by several workgroups (SweepPlan).
+// (4 n^2 bytes); block rows longer than 64 tiles are streamed by several workgroups (SweepPlan).  Which tiles a sweep
+// job reads is decided in one place, band_sweep_range of band_plan.inc, which both sweep kernels and the CPU checks call.
 // Host side: ONE left-looking driver (panel_update / factor_block / factor_range) on a CholTarget -- one matrix
 // (madqp_chol_factor), a batch of small matrices at fixed strides (madqp_chol_factor_batched) or a panel of the multi-GPU
 // loop (madqp_chol_factor_panel, ...); ONE panel solve of a 128-column block (madqp_chol_panel_solve), shared with the
@@ -578,9 +579,10 @@ __device__ __forceinline__ void sweep_poll_block(const double* __restrict__ x, i
 // tiles c*chunk .. min(r, (c+1)*chunk) - 1 of block r (counted from the far end of the dependency chain); the job
 // holding the tile next to the diagonal owns the block, the others publish their 128 partial sums to
 // part[(r*maxc + c)*128 ..] the way solution blocks are published.  jobs == nullptr: one job per block.
-// Under a band of kb blocks (the kernels' last argument; negative: none) block r has the tiles lo = max(0, r - kb) .. r - 1
-// only: a job starts at max(c*chunk, lo), the chunks before lo / chunk are no jobs (band_plan.inc, band_sweep_jobs) and
-// the owner adds the partial sums from that chunk on.  The protocol -- tickets, sentinel, spin limit, order -- is the same.
+// Under a band of kb blocks (the kernels' last argument; negative: none) block r has the kb tiles next to its diagonal
+// block only: a job starts no earlier than the first of them, the chunks before it are no jobs (band_sweep_jobs) and the
+// owner adds the partial sums from that chunk on -- band_sweep_range (band_plan.inc) is the arithmetic, for the kernels and
+// the CPU checks alike.  The protocol -- tickets, sentinel, spin limit, order -- is the same.
 struct SweepPlan {
     const int32_t* jobs;  // ticket -> r | c << 20, ordered by (r, c): a job waits only for earlier tickets
     double* part;
@@ -798,22 +800,15 @@ __global__ __launch_bounds__(1024) void trsv_fwd_sweep_kernel(const double* __re
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) s_r = atomicAdd(&ctl[REV ? 2 : 1], 1);
     __syncthreads();
-    int r = s_r, c = 0, j0 = 0, j1 = r, clo = 0;
+    int r = s_r, c = 0;
     if (plan.jobs) {
         const int32_t job = plan.jobs[r];
         r = job & 0xFFFFF;
         c = job >> 20;
-        j0 = c * plan.chunk;
-        j1 = (j0 + plan.chunk < r) ? j0 + plan.chunk : r;
     }
-    // (these ranges are mirrored by the CPU checks of the job lists -- tests/band_sweep_cases.py `ranges` and
-    // tests/csrc_band_sweep/band_sweep_main.cpp `check` --: change them together)
-    if (kb >= 0 && r > kb) {  // the band: tiles before r - kb hold nothing of the factor and are not read
-        const int lo = r - kb;
-        j0 = j0 > lo ? j0 : lo;
-        if (plan.jobs) clo = lo / plan.chunk;
-    }
-    const bool owner = (j1 == r);
+    const BandSweepRange range = band_sweep_range(r, c, plan.chunk, kb, plan.jobs != nullptr);  // (band_plan.inc)
+    const int j0 = range.j0, j1 = range.j1, clo = range.clo;
+    const bool owner = range.owner;
     const int rl = r;  // the block's place in the chain (partial sums are filed under it)
     const int nblk = (int)((n + NB - 1) / NB);
     if (REV) r = nblk - 1 - r;  // from here on r is the block of the matrix
@@ -930,20 +925,15 @@ __global__ __launch_bounds__(1024) void trsv_bwd_sweep_kernel(const double* __re
     if (tid == 0) s_r = atomicAdd(&ctl[2], 1);
     __syncthreads();
     // block nblk-1-rr has rr tiles below its diagonal block; the job takes tiles k0 .. k1-1 counted from the last row
-    int rr = s_r, c = 0, k0 = 0, k1 = rr, clo = 0;
+    int rr = s_r, c = 0;
     if (plan.jobs) {
         const int32_t job = plan.jobs[rr];
         rr = job & 0xFFFFF;
         c = job >> 20;
-        k0 = c * plan.chunk;
-        k1 = (k0 + plan.chunk < rr) ? k0 + plan.chunk : rr;
     }
-    if (kb >= 0 && rr > kb) {  // the band, in chain coordinates (see the forward kernel, and the mirrors named there)
-        const int lo = rr - kb;
-        k0 = k0 > lo ? k0 : lo;
-        if (plan.jobs) clo = lo / plan.chunk;
-    }
-    const bool owner = (k1 == rr);
+    const BandSweepRange range = band_sweep_range(rr, c, plan.chunk, kb, plan.jobs != nullptr);  // in chain coordinates
+    const int k0 = range.j0, k1 = range.j1, clo = range.clo;
+    const bool owner = range.owner;
     const int r = nblk - 1 - rr;
     const int64_t col0 = (int64_t)r * NB;
     const int w = (int)((n - col0 < NB) ? (n - col0) : NB);
@@ -1366,6 +1356,13 @@ static const CholModes& chol_modes() {  // filled once, at the first use
     return m;
 }
 
+hipError_t madqp_chol_band::clear(int64_t n) {
+    const hipError_t e = d_jobs ? hipFree(d_jobs) : hipSuccess;
+    *this = madqp_chol_band{};
+    extent = n - 1;
+    return e;
+}
+
 extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out) {
     ARG_TRY(ctx, ctx && out && n >= 0);
     *out = nullptr;
@@ -1374,18 +1371,7 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
     s->ctx = ctx;
     s->n = n;
     s->npos = n;
-    s->bw = -1;
-    s->band_extent = n - 1;
-    s->band_ops = nullptr;
-    s->band_nops = 0;
-    s->packed = false;
-    s->factored = false;
-    s->A = nullptr;
-    s->lda = 0;
-    s->winv = nullptr;
-    s->tmp = nullptr;
-    s->d_jobs = nullptr;
-    s->d_info = nullptr;
+    (void)s->band.clear(n);  // (nothing to free yet)
     const int64_t nblk = std::max<int64_t>(1, (n + NB - 1) / NB);
     hipError_t e = hipMalloc(&s->winv, nblk * WBLK * sizeof(double));
     if (e == hipSuccess) e = hipMemset(s->winv, 0, nblk * WBLK * sizeof(double));  // the kernel writes lower parts only
@@ -1395,12 +1381,6 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
     const CholModes md = chol_modes_from_env();  // (read per handle: the tests build job lists with several chunks)
     s->sweep_chunk = md.sweep_chunk;
     s->sweep_band = md.sweep_band;
-    s->sweep_kb = -1;
-    s->sweep_maxc = 0;
-    s->sweep_njobs = 0;
-    s->band_njobs = 0;
-    s->d_jobs = nullptr;
-    s->d_band_jobs = nullptr;
     std::vector<int32_t> jobs;
     if (nblk - 1 > s->sweep_chunk && nblk < (1 << 20)) {
         s->sweep_maxc = (int32_t)band_sweep_jobs(nblk, -1, s->sweep_chunk, jobs);
@@ -1412,10 +1392,6 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
         e = hipMalloc(&s->d_jobs, jobs.size() * sizeof(int32_t));
         if (e == hipSuccess) e = hipMemcpy(s->d_jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     }
-    s->upper = nullptr;
-    s->upper_ld = 0;
-    s->upper_ok = false;
-    s->utmp = nullptr;
     s->utmp_len = 2 * nblk * NB + 2 * nblk * (int64_t)s->sweep_maxc * NB;
     if (e == hipSuccess && nblk > 1 && nblk <= 160) e = hipMalloc(&s->utmp, s->utmp_len * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&s->d_info, 8 * sizeof(int32_t));  // [0] info, [1..2] sweep tickets
@@ -1434,7 +1410,7 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
 extern "C" int32_t madqp_chol_set_signature(madqp_chol* s, int64_t npos) {
     if (!s) return MADQP_ERR_ARG;
     ARG_TRY(s->ctx, npos >= 0 && npos <= s->n && (npos % NB == 0 || npos == s->n));
-    ARG_TRY(s->ctx, s->bw < 0 || npos == s->n);  // the band schedule factors positive definite matrices only
+    ARG_TRY(s->ctx, s->band.bw < 0 || npos == s->n);  // the band schedule factors positive definite matrices only
     s->npos = npos;
     s->factored = false;
     return MADQP_OK;
@@ -1446,13 +1422,12 @@ extern "C" int32_t madqp_chol_destroy(madqp_chol* s) {
     if (s->winv) (void)hipFree(s->winv);
     if (s->tmp) (void)hipFree(s->tmp);
     if (s->d_jobs) (void)hipFree(s->d_jobs);
-    if (s->d_band_jobs) (void)hipFree(s->d_band_jobs);
+    (void)s->band.clear(s->n);
     if (s->d_info) (void)hipFree(s->d_info);
     if (s->d_mid_plan) (void)hipFree(s->d_mid_plan);
     if (s->upper) (void)hipFree(s->upper);
     if (s->utmp) (void)hipFree(s->utmp);
     delete[] s->mid_units;
-    delete[] s->band_ops;
     delete s;
     return MADQP_OK;
 }
@@ -1468,57 +1443,35 @@ extern "C" int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw) {
     if (!s) return MADQP_ERR_ARG;
     madqp_ctx* ctx = s->ctx;
     ARG_TRY(ctx, bw == -1 || (bw >= 0 && bw < s->n && s->npos == s->n));
-    delete[] s->band_ops;
-    s->band_ops = nullptr;
-    s->band_nops = 0;
-    s->bw = bw;
-    s->band_extent = s->n - 1;
-    s->packed = false;  // (the extent changes: packed storage is laid out for one extent -- madqp_chol_set_packed again)
     // the form of the sweeps changes with this call and what is stored may be the factor of another schedule: a solve
     // needs a new factorisation first (madqp_chol_solve refuses with MADQP_ERR_STATE until then)
     s->factored = false;
     s->A = nullptr;
     s->upper_ok = false;
-    s->sweep_kb = -1;
-    s->band_njobs = 0;
-    if (s->d_band_jobs) {  // (a solve on the stream may still read it)
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipFree(s->d_band_jobs));
-        s->d_band_jobs = nullptr;
-    }
+    // (the extent changes with the bandwidth and packed storage is laid out for one extent: madqp_chol_set_packed again)
+    if (s->band.d_jobs) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (a solve on the stream may still read the list)
+    HIP_TRY(ctx, s->band.clear(s->n));
     if (bw < 0) return MADQP_OK;
+    // the new state in a local: the handle takes it once the plan and the job list both stand, and keeps "no band" otherwise
+    madqp_chol_band b;
+    b.bw = bw;
+    const CholModes& md = chol_modes();
+    b.extent = band_plan(s->n, bw, ctx->gemm_slots, b.ops, md.wt_min, md.wt_max, md.band_w);
     if (s->sweep_band) {
-        const int64_t kb = band_sweep_blocks(bw);
+        b.sweep_kb = band_sweep_blocks(bw);
         if (s->d_jobs) {
             std::vector<int32_t> jobs;
-            band_sweep_jobs((s->n + NB - 1) / NB, kb, s->sweep_chunk, jobs);
-            hipError_t e = hipMalloc(&s->d_band_jobs, jobs.size() * sizeof(int32_t));
-            if (e == hipSuccess) e = hipMemcpy(s->d_band_jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+            band_sweep_jobs((s->n + NB - 1) / NB, b.sweep_kb, s->sweep_chunk, jobs);
+            hipError_t e = hipMalloc(&b.d_jobs, jobs.size() * sizeof(int32_t));
+            if (e == hipSuccess) e = hipMemcpy(b.d_jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice);
             if (e != hipSuccess) {
-                if (s->d_band_jobs) (void)hipFree(s->d_band_jobs);
-                s->d_band_jobs = nullptr;
-                s->bw = -1;
+                (void)b.clear(s->n);
                 return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_chol_set_bandwidth: %s", hipGetErrorString(e));
             }
-            s->band_njobs = (int32_t)jobs.size();
+            b.njobs = (int32_t)jobs.size();
         }
-        s->sweep_kb = kb;
     }
-    std::vector<BandOp> ops;
-    const CholModes& md = chol_modes();
-    s->band_extent = band_plan(s->n, bw, ctx->gemm_slots, ops, md.wt_min, md.wt_max, md.band_w);
-    s->band_ops = new (std::nothrow) BandOp[ops.size() + 1];
-    if (!s->band_ops) {
-        s->bw = -1;
-        s->sweep_kb = -1;
-        s->band_njobs = 0;
-        if (s->d_band_jobs) (void)hipFree(s->d_band_jobs);  // (uploaded with a blocking copy: nothing reads it yet)
-        s->d_band_jobs = nullptr;
-        s->band_extent = s->n - 1;
-        return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
-    }
-    std::copy(ops.begin(), ops.end(), s->band_ops);
-    s->band_nops = (int64_t)ops.size();
+    s->band = std::move(b);
     return MADQP_OK;
 }
 
@@ -1526,10 +1479,10 @@ extern "C" int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw) {
 // the dense sweeps), [1] workgroups per sweep, [2] tiles per job (MADQP_SWEEP_CHUNK).
 extern "C" int32_t madqp_chol_sweep_info(madqp_chol* s, int64_t* out_host) {
     if (!s || !out_host) return MADQP_ERR_ARG;
-    const bool band = s->sweep_kb >= 0;
+    const bool band = s->band.sweep_kb >= 0;
     const int64_t nblk = std::max<int64_t>(1, (s->n + NB - 1) / NB);
-    out_host[0] = band ? s->sweep_kb : -1;
-    out_host[1] = !s->d_jobs ? nblk : band ? s->band_njobs : s->sweep_njobs;
+    out_host[0] = band ? s->band.sweep_kb : -1;
+    out_host[1] = !s->d_jobs ? nblk : band ? s->band.njobs : s->sweep_njobs;
     out_host[2] = s->sweep_chunk;
     return MADQP_OK;
 }
@@ -1537,7 +1490,7 @@ extern "C" int32_t madqp_chol_sweep_info(madqp_chol* s, int64_t* out_host) {
 extern "C" int32_t madqp_chol_band_extent(madqp_chol* s, int64_t* extent_host) {
     if (!s) return MADQP_ERR_ARG;
     ARG_TRY(s->ctx, extent_host != nullptr);
-    *extent_host = s->bw >= 0 ? s->band_extent : s->n - 1;
+    *extent_host = s->band.extent;  // (n - 1 without a band)
     return MADQP_OK;
 }
 
@@ -1550,20 +1503,20 @@ static int64_t packed_ld_pad() {  // MADQP_BAND_LD_PAD: doubles added to ceil16(
 }
 extern "C" int32_t madqp_chol_packed_layout(madqp_chol* s, int64_t ld_in, int64_t* out_host) {
     if (!s) return MADQP_ERR_ARG;
-    ARG_TRY(s->ctx, out_host != nullptr && s->bw >= 0);
-    if (!band_packed_layout(s->n, s->band_extent, ld_in, out_host, packed_ld_pad()))
+    ARG_TRY(s->ctx, out_host != nullptr && s->band.bw >= 0);
+    if (!band_packed_layout(s->n, s->band.extent, ld_in, out_host, packed_ld_pad()))
         return madqp_fail(s->ctx, MADQP_ERR_ARG, "madqp_chol_packed_layout: ld = %lld is below the extent %lld", (long long)ld_in,
-                          (long long)s->band_extent);
+                          (long long)s->band.extent);
     return MADQP_OK;
 }
 extern "C" int32_t madqp_chol_set_packed(madqp_chol* s, int32_t on) {
     if (!s) return MADQP_ERR_ARG;
-    ARG_TRY(s->ctx, !on || (s->bw >= 0 && s->sweep_kb >= 0 && s->npos == s->n));
-    if (s->packed != (on != 0)) {  // what is stored was factored in the other layout
+    ARG_TRY(s->ctx, !on || (s->band.bw >= 0 && s->band.sweep_kb >= 0 && s->npos == s->n));
+    if (s->band.packed != (on != 0)) {  // what is stored was factored in the other layout
         s->factored = false;
         s->A = nullptr;
     }
-    s->packed = on != 0;
+    s->band.packed = on != 0;
     return MADQP_OK;
 }
 
@@ -1711,7 +1664,7 @@ static int32_t factor_range(const CholTarget& t, int64_t j0, int64_t w) {
 // the one matrix of a handle as a target
 static CholTarget chol_target(madqp_chol* s, double* A, int64_t lda) {
     CholTarget t{s->ctx, A, lda, s->n, s->winv, s->d_info};
-    t.packed = s->packed;
+    t.packed = s->band.packed;
     return t;
 }
 
@@ -1819,10 +1772,9 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
     const int64_t n = s->n;
     HIP_TRY(ctx, hipMemsetAsync(s->d_info, 0, sizeof(int32_t), ctx->stream));
     s->upper_ok = false;
-    if (s->bw >= 0) {  // band schedule, every n: the operations of band_plan.inc in their order, then the sweep images
+    if (s->band.bw >= 0) {  // band schedule, every n: the operations of band_plan.inc in their order, then the sweep images
         const CholTarget t = chol_target(s, A, lda);
-        for (int64_t i = 0; i < s->band_nops; ++i) {
-            const BandOp& o = s->band_ops[i];
+        for (const BandOp& o : s->band.ops) {
             const int32_t r = o.kind == BAND_UPDATE ? panel_update(t, o.row0, o.k0, o.width, o.kend, -1.0, o.rows)
                                                     : factor_block(t, o.row0, o.width, o.rows);
             if (r) return r;
@@ -1868,7 +1820,7 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
 extern "C" int32_t madqp_chol_factor(madqp_chol* s, double* A, int64_t lda, int32_t* info_host) {
     if (!s) return MADQP_ERR_ARG;
     madqp_ctx* ctx = s->ctx;
-    ARG_TRY(ctx, A && info_host && lda >= (s->packed ? std::max<int64_t>(s->band_extent, 1) : s->n));
+    ARG_TRY(ctx, A && info_host && lda >= (s->band.packed ? std::max<int64_t>(s->band.extent, 1) : s->n));
     s->factored = false;
     s->A = A;
     s->lda = lda;
@@ -1898,7 +1850,7 @@ __global__ void info_to_slot_kernel(const int32_t* __restrict__ info, double* __
 int32_t madqp_chol_factor_q(madqp_chol* s, double* A, int64_t lda, double* d_slot) {
     if (!s) return MADQP_ERR_ARG;
     madqp_ctx* ctx = s->ctx;
-    ARG_TRY(ctx, A && d_slot && lda >= (s->packed ? std::max<int64_t>(s->band_extent, 1) : s->n));
+    ARG_TRY(ctx, A && d_slot && lda >= (s->band.packed ? std::max<int64_t>(s->band.extent, 1) : s->n));
     s->A = A;
     s->lda = lda;
     s->factored = true;
@@ -1954,7 +1906,7 @@ extern "C" int32_t madqp_chol_factor_begin(madqp_chol* s, double* A, int64_t lda
     madqp_ctx* ctx = s->ctx;
     ARG_TRY(ctx, A && lda >= s->n);
     ARG_TRY(ctx, s->npos == s->n);  // the panel pieces factor positive definite matrices only
-    ARG_TRY(ctx, s->bw < 0);        // ... and know no band
+    ARG_TRY(ctx, s->band.bw < 0);        // ... and know no band
     s->factored = false;
     s->A = A;
     s->lda = lda;
@@ -1964,7 +1916,7 @@ extern "C" int32_t madqp_chol_factor_begin(madqp_chol* s, double* A, int64_t lda
 
 extern "C" int32_t madqp_chol_factor_panel(madqp_chol* s, int64_t j0, int64_t w) {
     if (!s) return MADQP_ERR_ARG;
-    ARG_TRY(s->ctx, panel_ok(s, j0, w) && s->bw < 0);
+    ARG_TRY(s->ctx, panel_ok(s, j0, w) && s->band.bw < 0);
     const int32_t r = factor_range(chol_target(s, s->A, s->lda), j0, w);
     return r ? r : sweep_images(s, s->A, s->lda, j0, w);  // (the caller packs / reads the images of this panel next)
 }
@@ -2036,9 +1988,9 @@ extern "C" int32_t madqp_chol_solve(madqp_chol* s, double* rhs) {
         const int vec = ((((uintptr_t)A) & 15) == 0) && (lda % 2 == 0);
         const int64_t nb64 = nblk;
         // under a bandwidth the band form: the tiles within sweep_kb blocks of the diagonal, its own (shorter) job list
-        const int kb = (int)s->sweep_kb;
-        const int32_t* jobs = kb >= 0 ? s->d_band_jobs : s->d_jobs;
-        const unsigned grid = jobs ? (unsigned)(kb >= 0 ? s->band_njobs : s->sweep_njobs) : nblk;
+        const int kb = (int)s->band.sweep_kb;
+        const int32_t* jobs = kb >= 0 ? s->band.d_jobs : s->d_jobs;
+        const unsigned grid = jobs ? (unsigned)(kb >= 0 ? s->band.njobs : s->sweep_njobs) : nblk;
         double* part_f = s->tmp + nb64 * NB;
         double* part_b = part_f + nb64 * s->sweep_maxc * NB;
         const SweepPlan pf{jobs, part_f, s->sweep_chunk, s->sweep_maxc};

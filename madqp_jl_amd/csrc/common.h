@@ -222,43 +222,49 @@ int32_t madqp_chol_panel_solve(madqp_ctx* ctx, double* X, int64_t ldx, int64_t r
 int32_t madqp_trsv_tile(madqp_ctx* ctx, int32_t trans, const double* L, int64_t ld, const double* winv, double* v,
                         int64_t w, double* tmp, int32_t* ctl);
 
+// The band state of a Cholesky handle (madqp_chol_set_bandwidth, madqp_chol_set_packed; band_plan.inc), cleared and
+// committed as one
+struct madqp_chol_band {
+    int64_t bw = -1;      // half-bandwidth (-1: none, the dense schedules and sweeps)
+    int64_t extent = 0;   // of the plan: the largest i - j the factorisation touches; n - 1 without a band
+    std::vector<struct BandOp> ops;  // the plan
+    bool packed = false;  // packed band storage: the lda of a factorisation is the packed leading dimension (>= extent)
+    // the sweeps under the band (MADQP_SWEEP_BAND): blocks a block row reads left of its diagonal block (-1: the dense
+    // sweeps), and the band's own job list where the dense sweeps have one
+    int64_t sweep_kb = -1;
+    int32_t* d_jobs = nullptr;
+    int32_t njobs = 0;
+    // back to "no band" for a handle of order n; frees the job list, which nothing on the stream may still read (chol.hip)
+    hipError_t clear(int64_t n);
+};
+
 struct madqp_chol {
-    madqp_ctx* ctx;
-    int64_t n;
-    double* winv;  // ceil(n/128) blocks of 128x128 (col-major, ld 128): inverse diagonal blocks
-    double* tmp;   // tmp_len doubles: the intermediate vector of a solve, then the sweeps' partial-sum slots
-    int64_t tmp_len;
-    int32_t* d_jobs;  // sweep job list (chol.hip SweepPlan), nullptr when every block row is one job
-    int32_t sweep_chunk, sweep_maxc, sweep_njobs;
-    // the sweeps under a bandwidth (madqp_chol_set_bandwidth; band_plan.inc): sweep_band = MADQP_SWEEP_BAND of this handle,
-    // sweep_kb = blocks a block row reads left of its diagonal block (-1: the dense sweeps), and the band's own job list
-    // where the dense sweeps have one
-    bool sweep_band;
-    int64_t sweep_kb;
-    int32_t* d_band_jobs;
-    int32_t band_njobs;
-    int32_t* d_info;
-    double* A;  // last factored matrix (borrowed)
-    int64_t lda;
-    bool factored;
-    int64_t npos;  // quasi-definite mode (madqp_chol_set_signature): A = L diag(I_npos, -I) L'; npos == n: Cholesky
+    madqp_ctx* ctx = nullptr;
+    int64_t n = 0;
+    double* winv = nullptr;  // ceil(n/128) blocks of 128x128 (col-major, ld 128): inverse diagonal blocks
+    double* tmp = nullptr;   // tmp_len doubles: the intermediate vector of a solve, then the sweeps' partial-sum slots
+    int64_t tmp_len = 0;
+    int32_t* d_jobs = nullptr;  // sweep job list (chol.hip SweepPlan), nullptr when every block row is one job
+    int32_t sweep_chunk = 0, sweep_maxc = 0, sweep_njobs = 0;
+    bool sweep_band = false;  // MADQP_SWEEP_BAND of this handle: under a bandwidth the sweeps stay inside the band
+    madqp_chol_band band;
+    int32_t* d_info = nullptr;
+    double* A = nullptr;  // last factored matrix (borrowed)
+    int64_t lda = 0;
+    bool factored = false;
+    int64_t npos = 0;  // quasi-definite mode (madqp_chol_set_signature): A = L diag(I_npos, -I) L'; npos == n: Cholesky
     // mid-size schedule (chol.hip, mid_plan_build): which trailing tiles each block step updates, with which panels;
     // built at the first factorisation.  d_mid_plan: the packed units of all steps (mid_plan.inc); mid_units[k] /
     // mid_units[nblk + k]: number of units of step k / where they start
-    uint32_t* d_mid_plan;
-    int32_t* mid_units;
-    int32_t mid_plan_state;  // state: 0 not built, 1 in use, -1 no plan (the two-panel schedule runs)
+    uint32_t* d_mid_plan = nullptr;
+    int32_t* mid_units = nullptr;
+    int32_t mid_plan_state = 0;  // state: 0 not built, 1 in use, -1 no plan (the two-panel schedule runs)
     // the backward sweep on U = L' (chol.hip, trsv_fwd_sweep_kernel<1, true>): U of the last mid-size factorisation (order
     // npad, allocated at the first one), and the scratch of such a solve -- [y | x | partial sums of both sweeps], filled
     // with the sentinel by one kernel per solve
-    double* upper;
-    int64_t upper_ld;
-    double* utmp;
-    int64_t utmp_len;
-    bool upper_ok;  // the last factorisation left U and substitution images
-    // band schedule (madqp_chol_set_bandwidth): half-bandwidth (-1: none), the plan of band_plan.inc and its extent
-    int64_t bw, band_extent, band_nops;
-    struct BandOp* band_ops;
-    // packed band storage (madqp_chol_set_packed): the lda of a factorisation is the packed leading dimension (>= extent)
-    bool packed;
+    double* upper = nullptr;
+    int64_t upper_ld = 0;
+    double* utmp = nullptr;
+    int64_t utmp_len = 0;
+    bool upper_ok = false;  // the last factorisation left U and substitution images
 };

@@ -531,6 +531,24 @@ extern "C" int32_t madqp_kkt_create(madqp_ctx* ctx, int64_t nx, int64_t m, int64
     return kkt_create_common(ctx, KKT_CONDENSED, nx, m, ns, ind_ineq_host, H, ldh, A, lda, nullptr, 0, out);
 }
 
+// The sparse object of either storage: kkt_create_common without dense A, then the six borrowed CSR pointers of A and A'.
+static int32_t kkt_create_sparse_common(madqp_ctx* ctx, int32_t mode, int64_t nx, int64_t m, int64_t ns,
+                                        const int64_t* ind_ineq_host, const double* H, int64_t ldh, const int64_t* a_ptr,
+                                        const int64_t* a_col, const double* a_val, const int64_t* at_ptr,
+                                        const int64_t* at_col, const double* at_val, madqp_kkt** out, bool packed) {
+    const int32_t r = kkt_create_common(ctx, mode == 1 ? KKT_NORMAL : mode == 2 ? KKT_AUGMENTED : KKT_CONDENSED, nx, m, ns,
+                                        ind_ineq_host, H, ldh, nullptr, 0, nullptr, 0, out, packed);
+    if (r) return r;
+    madqp_kkt* k = *out;
+    k->a_ptr = a_ptr;
+    k->a_col = a_col;
+    k->a_val = a_val;
+    k->at_ptr = at_ptr;
+    k->at_col = at_col;
+    k->at_val = at_val;
+    return MADQP_OK;
+}
+
 // Sparse front end: A as CSR (a_*: m rows, column indices < nx, ascending within a row) and A' as CSR
 // (at_*: nx rows, indices < m), both device, int64, borrowed.  mode 0: condensed K = H + Sigma_x + A' Theta A
 // (H dense, NULL, diagonal through madqp_kkt_set_hdiag or CSR through madqp_kkt_set_hcsr), mode 1: the reference's
@@ -543,18 +561,8 @@ extern "C" int32_t madqp_kkt_create_sparse(madqp_ctx* ctx, int32_t mode, int64_t
                                            madqp_kkt** out) {
     if (!ctx) return MADQP_ERR_ARG;
     ARG_TRY(ctx, (mode >= 0 && mode <= 2) && a_ptr && at_ptr && (!H || ldh >= nx) && !(mode == 1 && H));
-    int32_t r = kkt_create_common(ctx, mode == 1 ? KKT_NORMAL : mode == 2 ? KKT_AUGMENTED : KKT_CONDENSED, nx, m, ns,
-                                  ind_ineq_host, H, ldh,
-                                  nullptr, 0, nullptr, 0, out);
-    if (r) return r;
-    madqp_kkt* k = *out;
-    k->a_ptr = a_ptr;
-    k->a_col = a_col;
-    k->a_val = a_val;
-    k->at_ptr = at_ptr;
-    k->at_col = at_col;
-    k->at_val = at_val;
-    return MADQP_OK;
+    return kkt_create_sparse_common(ctx, mode, nx, m, ns, ind_ineq_host, H, ldh, a_ptr, a_col, a_val, at_ptr, at_col, at_val,
+                                    out, /*packed=*/false);
 }
 
 // The same object on PACKED band storage: no dense H (NULL, diagonal or CSR as above), mode 0 or 1, and no K at all until
@@ -566,17 +574,8 @@ extern "C" int32_t madqp_kkt_create_sparse_packed(madqp_ctx* ctx, int32_t mode, 
                                                   const double* at_val, madqp_kkt** out) {
     if (!ctx) return MADQP_ERR_ARG;
     ARG_TRY(ctx, (mode == 0 || mode == 1) && a_ptr && at_ptr);
-    int32_t r = kkt_create_common(ctx, mode == 1 ? KKT_NORMAL : KKT_CONDENSED, nx, m, ns, ind_ineq_host, nullptr, 0, nullptr, 0,
-                                  nullptr, 0, out, /*packed=*/true);
-    if (r) return r;
-    madqp_kkt* k = *out;
-    k->a_ptr = a_ptr;
-    k->a_col = a_col;
-    k->a_val = a_val;
-    k->at_ptr = at_ptr;
-    k->at_col = at_col;
-    k->at_val = at_val;
-    return MADQP_OK;
+    return kkt_create_sparse_common(ctx, mode, nx, m, ns, ind_ineq_host, nullptr, 0, a_ptr, a_col, a_val, at_ptr, at_col,
+                                    at_val, out, /*packed=*/true);
 }
 // a packed object has no storage before its bandwidth is set
 static int32_t kkt_storage_ready(madqp_kkt* k, const char* what) {

@@ -117,11 +117,7 @@ class HIPCondensedKKTSystem:
     def __init__(self, backend, st: State, nx, ind_ineq, H, A):
         """``create_kkt_system`` (src/KKT/normalkkt.jl:29-126).  ``H``: (nx, nx) symmetric
         tensor or None (LP); ``A``: (m, nx) row-major tensor; both are borrowed."""
-        self.be, self.st = backend, st
-        self.nx, self.m = int(nx), st.m
-        self.ind_ineq = [int(i) for i in ind_ineq]
-        self.ns = len(self.ind_ineq)
-        assert st.n == self.nx + self.ns
+        self._init_problem(backend, st, nx, ind_ineq)
         self.H, self.A = H, A
         if H is not None:
             assert H.is_contiguous() and H.shape == (nx, nx)
@@ -129,6 +125,14 @@ class HIPCondensedKKTSystem:
         self._h = backend.kkt_create(self.nx, self.m, self.ind_ineq, H, max(self.nx, 1), A,
                                      max(self.nx, 1))
         self.linear_solver = HIPCholeskySolver(backend, self._h)
+
+    def _init_problem(self, backend, st, nx, ind_ineq):
+        """what every constructor starts from: the backend, the shared state and the sizes it fixes"""
+        self.be, self.st = backend, st
+        self.nx, self.m = int(nx), st.m
+        self.ind_ineq = [int(i) for i in ind_ineq]
+        self.ns = len(self.ind_ineq)
+        assert st.n == self.nx + self.ns
         self.n_factorizations = 0
 
     def close(self):
@@ -212,16 +216,11 @@ class HIPNormalKKTSystem(HIPCondensedKKTSystem):
     def __init__(self, backend, st: State, nx, ind_ineq, H, At):
         if H is not None:
             raise ValueError("The KKT system NormalKKTSystem supports only linear programs.")  # :45-48
-        self.be, self.st = backend, st
-        self.nx, self.m = int(nx), st.m
-        self.ind_ineq = [int(i) for i in ind_ineq]
-        self.ns = len(self.ind_ineq)
-        assert st.n == self.nx + self.ns
+        self._init_problem(backend, st, nx, ind_ineq)
         self.H, self.A, self.At = None, None, At
         assert At.is_contiguous() and tuple(At.shape) == (self.nx, self.m)
         self._h = backend.kkt_create_normal(self.nx, self.m, self.ind_ineq, At, max(self.m, 1))
         self.linear_solver = HIPCholeskySolver(backend, self._h)
-        self.n_factorizations = 0
 
     def is_inertia_correct(self, num_pos, num_zero, num_neg):  # src/KKT/normalkkt.jl:132-134
         return num_zero == 0 and num_pos == self.m
@@ -238,11 +237,7 @@ class HIPAugmentedKKTSystem(HIPCondensedKKTSystem):
     """
 
     def __init__(self, backend, st: State, nx, ind_ineq, H, A):
-        self.be, self.st = backend, st
-        self.nx, self.m = int(nx), st.m
-        self.ind_ineq = [int(i) for i in ind_ineq]
-        self.ns = len(self.ind_ineq)
-        assert st.n == self.nx + self.ns
+        self._init_problem(backend, st, nx, ind_ineq)
         self.H, self.A = H, A
         diag = H is not None and H.dim() == 1
         if H is not None:
@@ -253,7 +248,6 @@ class HIPAugmentedKKTSystem(HIPCondensedKKTSystem):
         if diag:
             backend.kkt_set_hdiag(self._h, H)
         self.linear_solver = HIPQuasiDefiniteSolver(backend, self._h, self.nx, self.m)
-        self.n_factorizations = 0
 
     def is_inertia_correct(self, num_pos, num_zero, num_neg):  # src/KKT/normalkkt.jl:132-134, K2 inertia
         return num_zero == 0 and num_neg == self.m
@@ -266,11 +260,7 @@ class HIPScaledAugmentedKKTSystem(HIPAugmentedKKTSystem):
     iterates as the K2 form; every entry of the matrix stays bounded as the iterates converge."""
 
     def __init__(self, backend, st: State, nx, ind_ineq, H, A):
-        self.be, self.st = backend, st
-        self.nx, self.m = int(nx), st.m
-        self.ind_ineq = [int(i) for i in ind_ineq]
-        self.ns = len(self.ind_ineq)
-        assert st.n == self.nx + self.ns
+        self._init_problem(backend, st, nx, ind_ineq)
         self.H, self.A = H, A
         if H is not None:
             assert H.is_contiguous() and tuple(H.shape) == (nx, nx)
@@ -278,7 +268,6 @@ class HIPScaledAugmentedKKTSystem(HIPAugmentedKKTSystem):
         self._h = backend.kkt_create_scaled_augmented(self.nx, self.m, self.ind_ineq, H, max(self.nx, 1), A,
                                                       max(self.nx, 1))
         self.linear_solver = HIPQuasiDefiniteSolver(backend, self._h, self.nx, self.m)
-        self.n_factorizations = 0
 
     def initialize(self):  # MadNLP.initialize!(kkt): also the scaling factor (library owned) = 1
         self.be.kkt_initialize(self._h, self.st)
@@ -297,11 +286,8 @@ class _SparseMixin:
         ``bandwidth`` (int or "auto"): :meth:`set_bandwidth` at construction.  ``storage="packed"``: the object never
         allocates the dense K -- the band alone, laid out for that bandwidth (``madqp_kkt_create_sparse_packed``)."""
         check_storage(storage, bandwidth, self._band_form, H)
-        self.be, self.st = backend, st
-        self.nx, self.m = int(nx), st.m
-        self.ind_ineq = [int(i) for i in ind_ineq]
-        self.ns = len(self.ind_ineq)
-        assert st.n == self.nx + self.ns and (csr.m, csr.n) == (self.m, self.nx)
+        self._init_problem(backend, st, nx, ind_ineq)
+        assert (csr.m, csr.n) == (self.m, self.nx)
         self.H, self.A, self.csr = H, None, csr
         self._t_val = csr.t_val  # values of A' in CSR order, borrowed by the library
         hcsr = isinstance(H, DeviceSymCSR)
@@ -319,7 +305,6 @@ class _SparseMixin:
             assert H.is_contiguous() and H.numel() == self.nx
             backend.kkt_set_hdiag(self._h, H)
         self.linear_solver = HIPCholeskySolver(backend, self._h)
-        self.n_factorizations = 0
         if bandwidth is not None:
             self.set_bandwidth(bandwidth)
 

@@ -56,12 +56,14 @@ static int check(int64_t n, int64_t bw, int64_t ld_in, int64_t slots) {
                 for (int64_t r = 0; r < o.rows; ++r) store(o.row0 + o.width + r, o.row0 + c);
         }
     }
-    // the sweeps: block row r reads the tiles [lo, r) next to its diagonal block, whole, up to the padded order
+    // the sweeps: block row r reads the tiles next to its diagonal block that band_sweep_range gives the kernels (one job
+    // per row here), whole, up to the padded order
     const int64_t nblk = npad / BAND_NB, kb = band_sweep_blocks(bw);
-    for (int64_t r = 0; r < nblk; ++r)
-        for (int64_t j = band_sweep_lo(r, kb); j < r; ++j) {
+    for (int64_t r = 0; r < nblk; ++r) {
+        const BandSweepRange g = band_sweep_range((int)r, 0, 1, (int)kb, false);
+        for (int64_t j = g.j0; j < g.j1; ++j)
             read_tile(r * BAND_NB, BAND_NB, j * BAND_NB, BAND_NB);  // forward: L[r, j]; backward reads the same tile as L[j', r']
-        }
+    }
     for (int64_t j = 0; j < n; ++j)
         for (int64_t i = j; i < n && i - j <= extent; ++i)
             if (std::isnan(P[i + j * ld])) ++bad;

@@ -1,7 +1,7 @@
 // Test infrastructure: walks the sweep job lists of madqp_jl_amd/csrc/band_plan.inc over the shapes
-// tests/test_band_sweep_plan.py uses, the way the kernels of chol.hip read them, and checks every tile range, every wait
-// and every partial-sum slot -- a stand-alone program, built with -fsanitize=address,undefined by the Makefile here and run
-// once by the test; it is never loaded into Python.
+// tests/test_band_sweep_plan.py uses, through the band_sweep_range the kernels of chol.hip read them with, and checks
+// every tile range, every wait and every partial-sum slot -- a stand-alone program, built with
+// -fsanitize=address,undefined by the Makefile here and run once by the test; it is never loaded into Python.
 #include <cstdio>
 
 #include "../../madqp_jl_amd/csrc/band_plan.inc"
@@ -25,17 +25,15 @@ static int check(int64_t n, int64_t bw, int64_t chunk) {
         const int64_t key = r * maxc + c;
         if (key <= prev) ++bad;  // ascending in (r, c)
         prev = key;
-        // the kernels' ranges
-        const int64_t lo = band_sweep_lo(r, kb);
-        const int64_t j0 = std::max(c * chunk, lo), j1 = std::min(r, (c + 1) * chunk);
-        if (j0 > j1) ++bad;
-        for (int64_t j = j0; j < j1; ++j) {
+        const BandSweepRange g = band_sweep_range((int)r, (int)c, (int)chunk, (int)kb, true);  // what the kernels read
+        if (g.j0 > g.j1) ++bad;
+        for (int64_t j = g.j0; j < g.j1; ++j) {
             ++seen[(size_t)(r * nblk + j)];
             if (!owned[(size_t)j]) ++bad;  // the solution block j comes from an earlier ticket
         }
         ticket[(size_t)key] = (int64_t)t;
-        if (j1 == r) {  // the owner: waits for the chunks clo .. c - 1
-            for (int64_t cc = lo / chunk; cc < c; ++cc)
+        if (g.owner) {  // waits for the chunks clo .. c - 1
+            for (int64_t cc = g.clo; cc < c; ++cc)
                 if (ticket[(size_t)(r * maxc + cc)] < 0) ++bad;
             ++owned[(size_t)r];
         }

@@ -1,5 +1,5 @@
 """CPU: packed band storage for the band Cholesky (madqp_jl_amd/csrc/band_plan.inc: band_packed_layout; compiled for the
-CPU by tests/csrc_band_packed).  Entry (i, j) of the lower triangle lives at P[i + j ld], ld >= extent.  The plan of the
+CPU by tests/csrc_band).  Entry (i, j) of the lower triangle lives at P[i + j ld], ld >= extent.  The plan of the
 factorisation and the job lists of the sweeps are executed in numpy THROUGH that addressing, on buffers that hold NaN in
 every slot that is no band entry within the extent: a store outside the band lands on another column's entry or on a
 planted NaN, a read outside it brings a NaN into the band.  The layout arithmetic, LAPACK's band format and the refusals
@@ -16,9 +16,8 @@ import scipy.linalg as sla
 import torch
 
 import madqp_jl_amd as M
-from band_cases import ROOT, UPDATE, band_spd, banded_qp, plan
-from band_packed_cases import band_index, layout, lds_to_test, nan_kept, npad, pack, packed_lib, unpack, view
-from band_sweep_cases import sweep_lib
+from band_cases import (ROOT, UPDATE, band_index, band_lib, band_spd, banded_qp, layout, lds_to_test, nan_kept, npad, pack,
+                        plan, unpack, view)
 from test_band_sweep_plan import run_sweep
 
 CPU = torch.device("cpu")
@@ -82,7 +81,7 @@ def test_executed_plan_factors_the_packed_band(n, bw):
 def test_executed_sweeps_on_the_packed_factor(n, bw):
     _, Lref, b, xref = reference(n, bw)
     extent = plan(n, bw)[1]
-    kb = sweep_lib().band_sweep_blocks_c(bw)
+    kb = band_lib().band_sweep_blocks_c(bw)
     for ld in lds_to_test(n, extent):
         ld, doubles = layout(n, extent, ld)
         buf, addr = pack(Lref, extent, ld, doubles)
@@ -114,7 +113,7 @@ def test_no_two_band_entries_share_an_address(n, bw):
 def test_the_librarys_leading_dimension_and_size(n, bw):
     extent = plan(n, bw)[1]
     ld, doubles = layout(n, extent)
-    pad = packed_lib().band_packed_default_pad_c()
+    pad = band_lib().band_packed_default_pad_c()
     assert ld % 2 == 0 and ld >= extent + 1 and ld == (extent + 1 + 15) // 16 * 16 + pad
     assert doubles == npad(n) * (ld + 1) + 128
     assert (npad(n) - 1) * (ld + 1) + 2 <= doubles, "whole-tile reads up to the padded order stay inside"
@@ -159,9 +158,9 @@ def test_packed_storage_is_lapacks_lower_band_format(n, bw):
 
 # ---- the walk under the sanitizers --------------------------------------------------------------------------------------------
 def test_packed_walk_under_address_and_undefined_sanitizers():
-    """tests/csrc_band_packed/band_packed_main.cpp: a stand-alone program (never loaded into Python) that makes every
+    """tests/csrc_band/band_packed_main.cpp: a stand-alone program (never loaded into Python) that makes every
     store and every whole-tile read of the plan and the sweeps on a buffer of exactly the reported size."""
-    packed_lib()  # (runs make)
+    band_lib()  # (runs make)
     out = subprocess.run([os.path.join(ROOT, "tests", "_build", "band_packed_check")], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "BAD" not in out.stdout and out.stdout.count(" ok") >= 4 * len(SHAPES) + len(LARGE)

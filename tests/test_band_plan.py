@@ -16,7 +16,7 @@ import torch
 import madqp_jl_amd as M
 from madqp_jl_amd import preprocess as P
 from madqp_jl_amd.kkt import pattern_bandwidth
-from band_cases import (BLOCK, NB, ROOT, SLOTS, UPDATE, band_spd, banded_qp, dense_pattern_bandwidth, plan, plan_lib)
+from band_cases import (BLOCK, NB, ROOT, SLOTS, UPDATE, band_spd, banded_qp, band_lib, dense_pattern_bandwidth, plan)
 
 CPU = torch.device("cpu")
 NS = (1, 128, 129, 500, 1537, 2100)
@@ -119,7 +119,7 @@ def test_ranges_cover_the_band_once(n, bw):
 
 def dense_schedule(n, slots=SLOTS):
     """chol_factor_enqueue's left-looking schedule and factor_range's halving, as operations."""
-    lib = plan_lib()
+    lib = band_lib()
     ops = []
 
     def rng(j0, w):
@@ -241,7 +241,7 @@ def test_default_is_no_bandwidth():
 # ---- the plan under the sanitizers ----------------------------------------------------------------------------------------
 def test_plan_under_address_and_undefined_sanitizers():
     """tests/csrc_band/band_plan_main.cpp: a stand-alone program (never loaded into Python) that plans the shapes above."""
-    plan_lib()  # (runs make)
+    band_lib()  # (runs make)
     out = subprocess.run([os.path.join(ROOT, "tests", "_build", "band_plan_check")], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "BAD" not in out.stdout and out.stdout.count(" ok") >= len(SHAPES) + len(RANGE_ONLY)

@@ -1,5 +1,5 @@
 """CPU: the job lists of the triangular sweeps under a band (madqp_jl_amd/csrc/band_plan.inc: band_sweep_blocks,
-band_sweep_jobs; compiled for the CPU by tests/csrc_band_sweep).  The lists are checked against the tiles of the band, the
+band_sweep_jobs; compiled for the CPU by tests/csrc_band).  The lists are checked against the tiles of the band, the
 waits of the kernels and the extent of the factorisation's plan; both sweeps are executed in numpy along the lists, with
 partial sums per job and the owner's sum over them, on factors that hold NaN wherever the sweeps must not read.  The kernels
 that run the lists are held in tests/test_gpu_band_sweeps.py."""
@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 import scipy.linalg as sla
 
-from band_cases import NB, ROOT, band_spd, plan
-from band_sweep_cases import dense_jobs, ranges, sweep_jobs, sweep_lib
+from band_cases import NB, ROOT, band_lib, band_spd, dense_jobs, plan, ranges, sweep_jobs
 
 NS = (1, 128, 129, 500, 1537, 2100, 9000)
 CHUNKS = (1, 2, 3, 5, 64)
@@ -20,14 +19,13 @@ SHAPES = [(n, bw) for n in NS for bw in sorted({0, 1, 127, 128, 129, 300, 640, n
 
 @pytest.mark.parametrize("n,bw", SHAPES)
 def test_jobs_cover_the_band_once(n, bw):
-    lib = sweep_lib()
+    lib = band_lib()
     nblk = max(1, (n + NB - 1) // NB)
     kb = lib.band_sweep_blocks_c(bw)
     assert kb == (bw + 127) // 128
     reach = lib.band_sweep_reach_c(n, kb)
     assert reach == min(n - 1, kb * 128 + 127)
     extent = plan(n, bw)[1]
-    assert lib.band_plan_extent_c(n, bw, 512) == extent
     assert reach <= extent, "the sweeps stay inside the extent of the factorisation"
     for chunk in CHUNKS:
         jobs, maxc = sweep_jobs(nblk, kb, chunk)
@@ -115,7 +113,7 @@ def test_executed_sweeps_stay_inside_the_extent(n, bw):
     W = L  # in place: NaN above the diagonal and beyond the extent
     W[(d < 0) | (d > extent)] = np.nan
     del d
-    kb = sweep_lib().band_sweep_blocks_c(bw)
+    kb = band_lib().band_sweep_blocks_c(bw)
     for chunk in CHUNKS:
         y = run_sweep(W, b, n, kb, chunk, backward=False)
         x = run_sweep(W, y, n, kb, chunk, backward=True)
@@ -124,9 +122,9 @@ def test_executed_sweeps_stay_inside_the_extent(n, bw):
 
 
 def test_sweep_plan_under_address_and_undefined_sanitizers():
-    """tests/csrc_band_sweep/band_sweep_main.cpp: a stand-alone program (never loaded into Python) that walks the job
+    """tests/csrc_band/band_sweep_main.cpp: a stand-alone program (never loaded into Python) that walks the job
     lists of the shapes above the way the kernels read them."""
-    sweep_lib()  # (runs make)
+    band_lib()  # (runs make)
     out = subprocess.run([os.path.join(ROOT, "tests", "_build", "band_sweep_check")], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "BAD" not in out.stdout and out.stdout.count(" ok") >= len(SHAPES) * len(CHUNKS)

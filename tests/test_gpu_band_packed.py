@@ -16,8 +16,7 @@ import madqp_jl_amd as M
 from madqp_jl_amd import preprocess as P
 from oracle import mpc
 from parity import TRACE_KEYS, assert_parity
-from band_cases import band_spd, banded_qp, plan
-from band_packed_cases import band_index, layout, nan_kept, pack, unpack
+from band_cases import band_index, band_spd, banded_qp, layout, nan_kept, pack, plan, unpack
 from test_gpu_band import (OREG, REG, banded_device_qp, bits, boundary_control, condensed_case, dev, leading_dimension,
                            reference, whole_matrix)
 from test_gpu_band_sweeps import bars, create, planted, rhs

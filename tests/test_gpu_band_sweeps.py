@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import madqp_jl_amd as M
-from band_sweep_cases import workgroups
+from band_cases import workgroups
 from test_gpu_band import FACTOR_SHAPES, assembly_cases, bits, dev, leading_dimension, reference, whole_matrix
 
 pytestmark = pytest.mark.gpu
