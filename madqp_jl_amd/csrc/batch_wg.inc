@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(TPB) void bq_iter_post_kernel(BQ q) {
         WG_SYNC();
         dnorm = red[0];
         WG_SYNC();
-        wg::update_iterates_kernel(s, alpha_p, alpha_d);  // :332-335
+        wg::update_iterates_kernel(s, alpha_p, alpha_d, nullptr);  // :332-335
         WG_SYNC();
         // (the start point moves x AFTER initialize! evaluated the model, src/solver.jl:166-170 then :6-125: through the first
         // iteration f and c belong to the old point -- the reference's own loop has it so -- and an update of them would
@@ -1026,7 +1026,7 @@ __global__ __launch_bounds__(TPB) void bq_iter_post_kernel(BQ q) {
         else
             obj = wg_eval_model(q, s, pb, red, lds + 2 * NB);  // :338-340
         const double eps = 2.220446049250313e-16;
-        if (s.nlb || s.nub) wg::adjust_boundary_kernel(s, eps * mu, 1.8189894035458565e-12);  // :342
+        if (s.nlb || s.nub) wg::adjust_boundary_kernel(s, eps * mu, 1.8189894035458565e-12, nullptr, nullptr);  // :342
         WG_SYNC();
     }
     BSTAMP(15);

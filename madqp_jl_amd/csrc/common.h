@@ -14,6 +14,7 @@
 // last slot of the result block: device-side fault word (non-zero: a triangular sweep's hand-off timed out);
 // it rides along with every synchronising scalar read-back (madqp_read_results) and turns into MADQP_ERR_HIP
 #define MADQP_FAULT_SLOT (MADQP_RESULT_SLOTS - 1)
+#include "mpc_rules.inc"  // where the fused iteration keeps what in the block (MPC_SL_*, MPC_W_*), and its scalar rules
 
 struct ProfEvent {
     hipEvent_t a, b;
@@ -84,38 +85,36 @@ int32_t madqp_read_results(madqp_ctx* ctx, int count, double* out_host);
 // queued reductions (vec_kernels.hip, kkt.hip, chol.hip): results stay in ctx->d_res at the given slot until one
 // madqp_read_results fetches the block (slots 0 .. MADQP_FAULT_SLOT-1)
 int32_t madqp_q_compl(madqp_ctx* ctx, const madqp_state* st, int affine, double ap, double ad, const double* a8,
-                      int slot0);                                                               // 2 slots: sums
-int32_t madqp_q_alpha_max(madqp_ctx* ctx, const madqp_state* st, double tau, int slot0);        // 8 slots
+                      int slot0);                                                               // MPC_W_COMPL slots: sums
+int32_t madqp_q_alpha_max(madqp_ctx* ctx, const madqp_state* st, double tau, int slot0);        // MPC_W_ALPHA slots
 // the same with a scalar that stays in device memory (mpc.hip, body_fused: no read-back between predictor and corrector)
 int32_t madqp_q_alpha_max_dev(madqp_ctx* ctx, const madqp_state* st, double tau, const double* tau_dev, int slot0);
 int32_t madqp_set_correction_rhs_dev(madqp_ctx* ctx, const madqp_state* st, const double* mu_dev);
-// a8 != nullptr: the step lengths are min(a8[0], a8[2]), min(a8[4], a8[6]) read on the device (as madqp_q_compl's a8)
+// (vec_kernels.hip: with mu_dev, beta_min and beta_max are multiplied by *mu_dev on the device; a8 as madqp_q_compl's)
 int32_t madqp_set_extra_correction_dev(madqp_ctx* ctx, const madqp_state* st, double alpha_p, double alpha_d, double beta_min,
                                        double beta_max, const double* mu_dev, const double* a8 = nullptr);
-// Gondzio's trial step lengths min(alpha + delta, 1) from the 8-slot step-length block at `in`, written in the pattern
-// madqp_q_compl / madqp_set_extra_correction_dev read (slots out+0, +2: primal; out+4, +6: dual)
-int32_t madqp_q_mpc_trial_alpha(madqp_ctx* ctx, int in, int out, double delta);
-int32_t madqp_q_mpc_mu(madqp_ctx* ctx, int in, int out, int64_t nb, double mu_min, int step_rule, double step_param);
-int32_t madqp_q_mpc_muc(madqp_ctx* ctx, int in, int mu_curr_slot, int out, int64_t nb);
-// body_fused's decisions behind the corrector, on the device (vec_kernels.hip, mpc_decide_kernel): slots of the block
-struct MpcDecide {
-    int info, nrm_pred, nrm_corr, alpha, alpha_gz, trial, out;
-    int gondzio, max_ncorr, check_residual;
-    double tol_linear_solve;
-};
-int32_t madqp_q_mpc_decide(madqp_ctx* ctx, const MpcDecide* a);
+// One-thread kernels on the block, each a rule of mpc_rules.inc between the fields it names there:
+// GZ_ALPHA -> TRIAL_ALPHA; COMPL -> BARRIER; the two sums at compl_slot and mu_curr -> MUC; the block -> DECISION
+int32_t madqp_q_mpc_trial_alpha(madqp_ctx* ctx);
+int32_t madqp_q_mpc_mu(madqp_ctx* ctx, int64_t nb, double mu_min, int step_rule, double step_param);
+int32_t madqp_q_mpc_muc(madqp_ctx* ctx, int compl_slot, int64_t nb);
+int32_t madqp_q_mpc_decide(madqp_ctx* ctx, const MpcDecideOpt& opt);
 int32_t madqp_copy_if_dev(madqp_ctx* ctx, int64_t len, const double* src, double* dst, const double* flag_dev);
-int32_t madqp_update_iterates_dev(madqp_ctx* ctx, const madqp_state* st, const double* dec_dev);
-int32_t madqp_adjust_boundary_dev(madqp_ctx* ctx, const madqp_state* st, const double* dec_dev, const double* mu_dev);
+// madqp_update_iterates / madqp_adjust_boundary gated by the DECISION words in device memory (nullptr: the extern "C"
+// forms); with them the step lengths are the decided ones, and mu is read from *mu_dev
+int32_t madqp_update_iterates_dev(madqp_ctx* ctx, const madqp_state* st, double alpha_p, double alpha_d,
+                                  const double* dec_dev);
+int32_t madqp_adjust_boundary_dev(madqp_ctx* ctx, const madqp_state* st, double mu, const double* dec_dev,
+                                  const double* mu_dev);
 // the result block on its way to a pinned host copy, marked by an event: the host waits for the event, not for the stream
 int32_t madqp_results_post(madqp_ctx* ctx, double* h_dst, hipEvent_t ev);
 int32_t madqp_results_wait(madqp_ctx* ctx, const double* h_src, hipEvent_t ev, int count, double* out_host);
-int32_t madqp_q_inf(madqp_ctx* ctx, const madqp_state* st, int slot0);                          // 4 slots
+int32_t madqp_q_inf(madqp_ctx* ctx, const madqp_state* st, int slot0);                          // MPC_W_INF slots
 void madqp_inf_from_block(const double* out4, double* out3);
 int32_t madqp_q_norm_inf3(madqp_ctx* ctx, int64_t len, const double* a, const double* b, const double* c,
-                          int slot0);                                                           // 3 slots
-int32_t madqp_q_kkt_eval(madqp_kkt* k, const madqp_state* st, const double* q, const double* rhs, int slot0);  // 2
-int32_t madqp_q_kkt_factorize(madqp_kkt* k, int slot0);                                         // 1 slot: info
+                          int slot0);                                                           // MPC_W_NRM slots
+int32_t madqp_q_kkt_eval(madqp_kkt* k, const madqp_state* st, const double* q, const double* rhs, int slot0);  // MPC_W_EVAL
+int32_t madqp_q_kkt_factorize(madqp_kkt* k, int slot0);                                         // MPC_W_INFO slot: info
 // w = K^-1 p, optionally pcopy = p (kkt.hip: the condensed mode runs its per-variable passes fused)
 int32_t madqp_kkt_solve_from(madqp_kkt* k, const madqp_state* st, const double* p, double* w, double* pcopy);
 int32_t madqp_kkt_factor_result(madqp_kkt* k, int32_t info);

@@ -30,9 +30,9 @@
 // ends here has lost one assembly).  The host replays every decision from the block and fails loudly if the device's
 // differ; where the device said "the host takes over" (failed factorisation or verdict, a second Gondzio trial) the
 // iterates have not moved and the round-4 flow continues from the same block.  MADQP_MPC_AHEAD=0: the round-4 form.
-// Same kernels, the same arithmetic operation for operation (on the device where the scalar stays there), same order on
-// the stream: the iterates are bitwise those of the sequential form (tests/test_gpu_solver.py).  A failed first factorisation (the x100 retries of src/linear_solver.jl:6-17)
-// sends the rest of that iteration down the sequential form.
+// Same kernels, same arithmetic (mpc_rules.inc: each scalar rule is ONE host+device function, the block's fields are named
+// there once), same order on the stream: the iterates are bitwise those of the sequential form (tests/test_gpu_solver.py).
+// A failed first factorisation (the x100 retries of src/linear_solver.jl:6-17) sends the rest of that iteration down it.
 #include <cmath>
 #include <cstdlib>
 
@@ -109,8 +109,8 @@ int32_t factorize_regularized_system(madqp_mpc* s, int first_trial = 0) {
     return MADQP_OK;
 }
 
-// src/linear_solver.jl:19-45
-int32_t solve_system(madqp_mpc* s) {
+// solve_system! up to its reduction: d = K^-1 p, w1 = p - K d, the three norms into the result block at slot0
+int32_t solve_system_queue(madqp_mpc* s, int slot0) {
     const int64_t len = ntot(s->st);
     TRY(madqp_kkt_solve_from(s->kkt, &s->st, s->st.p, s->st.d, s->w1));   // d = K^-1 p, w1 = p
     TRY(madqp_kkt_mul_solved(s->kkt, &s->st, s->w1, s->st.d, -1.0, 1.0));  // d: the solve's result, untouched
@@ -120,13 +120,20 @@ int32_t solve_system(madqp_mpc* s) {
         TRY(madqp_copy(s->ctx, len, s->st.p, s->w1));
         TRY(madqp_kkt_mul(s->kkt, &s->st, s->w1, s->st.d, -1.0, 1.0));
     }
-    double nrm[3];
-    TRY(madqp_norm_inf3(s->ctx, len, s->w1, s->st.p, s->st.d, nrm));
-    const double ratio = nrm[0] / std::max(1.0, nrm[1]);
-    s->residual_ratio = ratio;
-    if (std::isnan(ratio) || (s->opt.check_residual && ratio > s->opt.tol_linear_solve))
+    return madqp_q_norm_inf3(s->ctx, len, s->w1, s->st.p, s->st.d, slot0);
+}
+int32_t residual_verdict(madqp_mpc* s, const double* nrm) {  // src/linear_solver.jl:36-43
+    s->residual_ratio = mpc_residual_ratio(nrm);
+    if (mpc_solve_failed(s->residual_ratio, s->opt.check_residual, s->opt.tol_linear_solve))
         return MADQP_NUM_NAN;  // MadNLP.SolveException
     return MADQP_OK;
+}
+// src/linear_solver.jl:19-45
+int32_t solve_system(madqp_mpc* s) {
+    TRY(solve_system_queue(s, 0));
+    double nrm[MPC_W_NRM];
+    TRY(madqp_read_results(s->ctx, MPC_W_NRM, nrm));
+    return residual_verdict(s, nrm);
 }
 
 // src/kernels.jl:290-305
@@ -134,14 +141,10 @@ int32_t fraction_to_boundary(madqp_mpc* s, double tau, double* ap, double* ad, d
                              int64_t* i4 = nullptr) {
     double a[4];
     int64_t ib[4];
-    TRY(madqp_get_alpha_max(s->ctx, &s->st, tau, a, ib));
-    *ap = std::min(a[0], a[1]);
-    *ad = std::min(a[2], a[3]);
-    if (a4)
-        for (int q = 0; q < 4; ++q) {
-            a4[q] = a[q];
-            i4[q] = ib[q];
-        }
+    if (!a4) a4 = a, i4 = ib;
+    TRY(madqp_get_alpha_max(s->ctx, &s->st, tau, a4, i4));
+    *ap = mpc_min(a4[0], a4[1]);
+    *ad = mpc_min(a4[2], a4[3]);
     return MADQP_OK;
 }
 
@@ -227,27 +230,25 @@ int32_t mehrotra_adaptive_step(madqp_mpc* s) {
 
 // src/solver.jl:200-251
 int32_t gondzio(madqp_mpc* s, double mu_curr) {
-    const double delta = 0.1, bmin = 0.1, bmax = 10.0, tau = 0.995;
     const int64_t len = ntot(s->st);
-    double alpha_p, alpha_d;
-    TRY(fraction_to_boundary(s, tau, &alpha_p, &alpha_d));
+    MpcSteps alpha;
+    TRY(fraction_to_boundary(s, MPC_GZ_TAU, &alpha.p, &alpha.d));
     for (int c = 0; c < s->opt.max_ncorr; ++c) {
-        const double ta_p = std::min(alpha_p + delta, 1.0), ta_d = std::min(alpha_d + delta, 1.0);
+        const MpcSteps ta = mpc_trial_alpha(alpha);
         double ga;
-        TRY(madqp_get_affine_complementarity_measure(s->ctx, &s->st, ta_p, ta_d, &ga));
-        const double mu = (ga / mu_curr) * (ga / mu_curr) * ga;
-        TRY(madqp_set_extra_correction(s->ctx, &s->st, ta_p, ta_d, bmin, bmax, mu));
+        TRY(madqp_get_affine_complementarity_measure(s->ctx, &s->st, ta.p, ta.d, &ga));
+        const double mu = mpc_muc(ga, mu_curr);
+        TRY(madqp_set_extra_correction(s->ctx, &s->st, ta.p, ta.d, MPC_GZ_BMIN, MPC_GZ_BMAX, mu));
         TRY(madqp_set_correction_rhs(s->ctx, &s->st, mu));
         TRY(madqp_copy(s->ctx, len, s->st.d, s->w2));
         TRY(solve_system(s));
-        double ha_p, ha_d;
-        TRY(fraction_to_boundary(s, tau, &ha_p, &ha_d));
-        if (ha_p < 1.005 * alpha_p || ha_d < 1.005 * alpha_d) {
+        MpcSteps ha;
+        TRY(fraction_to_boundary(s, MPC_GZ_TAU, &ha.p, &ha.d));
+        if (mpc_trial_dropped(ha, alpha)) {
             TRY(madqp_copy(s->ctx, len, s->w2, s->st.d));
             break;
         }
-        alpha_p = ha_p;
-        alpha_d = ha_d;
+        alpha = ha;
     }
     return MADQP_OK;
 }
@@ -374,22 +375,17 @@ int32_t body_after_factorization(madqp_mpc* s, madqp_mpc_info* info_host) {
     TRY(madqp_get_correction(ctx, &s->st));     // :297
     // update_barrier!(Mehrotra), src/kernels.jl:226-236 (field-order quirk: "any bound")
     TRY(madqp_get_complementarity_measure(ctx, &s->st, &mu_curr));
-    double sigma = 1.0;
-    if (s->st.nlb + s->st.nub > 0) {
-        const double t = mu_affine / mu_curr;
-        sigma = std::min(std::max(t * t * t, 1e-6), 10.0);  // t^3 as Julia's literal power forms it; the Python driver and mpc_mu_kernel too
-    }
-    s->mu = std::max(s->opt.mu_min, sigma * mu_curr);
+    const MpcBarrier bar = mpc_barrier(mu_affine, mu_curr, (double)(s->st.nlb + s->st.nub), s->opt.mu_min, s->opt.step_rule,
+                                       s->opt.step_param);
+    s->mu = bar.mu;
     TRY(madqp_set_correction_rhs(ctx, &s->st, s->mu));  // :307
     TRY(solve_system(s));
     if (s->opt.max_ncorr > 0) TRY(gondzio(s, mu_curr));  // :316-324
     // update_step!, src/kernels.jl:307-374
-    if (s->opt.step_rule == 0) {
-        TRY(fraction_to_boundary(s, s->opt.step_param, &s->alpha_p, &s->alpha_d));
-    } else if (s->opt.step_rule == 1) {
-        TRY(fraction_to_boundary(s, std::max(1.0 - s->mu, s->opt.step_param), &s->alpha_p, &s->alpha_d));
-    } else {
+    if (s->opt.step_rule == 2) {
         TRY(mehrotra_adaptive_step(s));
+    } else {
+        TRY(fraction_to_boundary(s, bar.tau, &s->alpha_p, &s->alpha_d));
     }
     TRY(madqp_norm_inf(ctx, s->st.n, s->st.d, &s->dnorm));             // print_iter, src/structure.jl:190
     TRY(madqp_update_iterates(ctx, &s->st, s->alpha_p, s->alpha_d));   // :332-335
@@ -406,31 +402,44 @@ int32_t body_sequential(madqp_mpc* s, madqp_mpc_info* info_host) {
     return body_after_factorization(s, info_host);
 }
 
-// solve_system! up to its reduction: d = K^-1 p, w1 = p - K d, the three norms into the result block at slot0
-int32_t solve_system_queue(madqp_mpc* s, int slot0) {
-    const int64_t len = ntot(s->st);
-    TRY(madqp_kkt_solve_from(s->kkt, &s->st, s->st.p, s->st.d, s->w1));  // d = K^-1 p, w1 = p
-    TRY(madqp_kkt_mul_solved(s->kkt, &s->st, s->w1, s->st.d, -1.0, 1.0));
-    for (int32_t it = 0; it < s->opt.refine_steps; ++it) {  // the refinement steps of solve_system, queued like the rest
-        TRY(madqp_kkt_solve(s->kkt, &s->st, s->w1));
-        TRY(madqp_axpy(s->ctx, len, 1.0, s->w1, s->st.d));
-        TRY(madqp_copy(s->ctx, len, s->st.p, s->w1));
-        TRY(madqp_kkt_mul(s->kkt, &s->st, s->w1, s->st.d, -1.0, 1.0));
-    }
-    return madqp_q_norm_inf3(s->ctx, len, s->w1, s->st.p, s->st.d, slot0);
+// One Gondzio trial, queued (src/solver.jl:216-230): mu_c formed on the device from the trial's affine sums, the
+// direction before it saved in w2, and behind the solve the trial block at `base` (MpcTrialBlock).  The trial's step
+// lengths min(alpha + delta, 1) are read on the device from ta_dev (TRIAL_ALPHA: the first trial) or, with nullptr, are ta.
+int32_t queue_gondzio_trial(madqp_mpc* s, const double* ta_dev, MpcSteps ta, int compl_slot, int base) {
+    madqp_ctx* ctx = s->ctx;
+    const double* res = ctx->d_res;
+    TRY(madqp_q_compl(ctx, &s->st, 1, ta.p, ta.d, ta_dev, compl_slot));
+    TRY(madqp_q_mpc_muc(ctx, compl_slot, s->st.nlb + s->st.nub));
+    TRY(madqp_set_extra_correction_dev(ctx, &s->st, ta.p, ta.d, MPC_GZ_BMIN, MPC_GZ_BMAX, res + MPC_SL_MUC, ta_dev));
+    TRY(madqp_set_correction_rhs_dev(ctx, &s->st, res + MPC_SL_MUC));
+    TRY(madqp_copy(ctx, ntot(s->st), s->st.d, s->w2));
+    TRY(solve_system_queue(s, base + MPC_TRIAL.nrm));
+    TRY(madqp_q_alpha_max(ctx, &s->st, MPC_GZ_TAU, base + MPC_TRIAL.alpha_gz));
+    TRY(madqp_q_alpha_max_dev(ctx, &s->st, 0.0, res + MPC_SL_TAU, base + MPC_TRIAL.alpha_tau));
+    return madqp_q_norm_inf3(ctx, s->st.n, s->st.d, nullptr, nullptr, base + MPC_TRIAL.dnorm);  // print_iter, src/structure.jl:190
 }
-int32_t residual_verdict(madqp_mpc* s, const double* nrm) {  // src/linear_solver.jl:36-43
-    const double ratio = nrm[0] / std::max(1.0, nrm[1]);
-    s->residual_ratio = ratio;
-    if (std::isnan(ratio) || (s->opt.check_residual && ratio > s->opt.tol_linear_solve)) return MADQP_NUM_NAN;
+
+// Phase (c), queued: the update of the iterates, the model at the new point and the residual norms of the next
+// termination test into PHASE_C.  dec: the DECISION words in device memory -- the two kernels with side effects do nothing
+// unless they say "go on" and take their scalars from the block, and a dropped trial's direction comes back first -- or
+// nullptr: the host has decided (s->alpha_p, s->alpha_d, s->mu).
+int32_t queue_phase_c(madqp_mpc* s, const double* dec) {
+    madqp_ctx* ctx = s->ctx;
+    if (dec && s->opt.max_ncorr > 0) TRY(madqp_copy_if_dev(ctx, ntot(s->st), s->w2, s->st.d, dec + MPC_DEC_RESTORE));
+    TRY(madqp_update_iterates_dev(ctx, &s->st, s->alpha_p, s->alpha_d, dec));                        // :332-335
+    TRY(madqp_q_kkt_eval(s->kkt, &s->st, s->q, s->rhs, MPC_SL_OBJ_LIN));                              // :338-340
+    TRY(madqp_adjust_boundary_dev(ctx, &s->st, s->mu, dec, dec ? ctx->d_res + MPC_SL_MU : nullptr));  // :342
+    TRY(madqp_kkt_jtprod(s->kkt, s->st.jacl, s->st.y));                                               // :259-283 of the next pass
+    TRY(madqp_q_inf(ctx, &s->st, MPC_SL_INF));
+    if (s->ahead) TRY(madqp_results_post(ctx, s->h_final, s->ev_final));
     return MADQP_OK;
 }
-inline double min_like_host(double a, double b) { return std::min(a, b); }  // fraction_to_boundary's combination
 
 // The same iteration with two blocking read-backs (see the head of this file).
 int32_t body_fused(madqp_mpc* s, madqp_mpc_info* info_host) {
     madqp_ctx* ctx = s->ctx;
-    const int64_t nb = s->st.nlb + s->st.nub;
+    const double* res = ctx->d_res;
+    const bool gz = s->opt.max_ncorr > 0;
     update_regularization(s);  // :288
     // (a) factorisation and predictor
     const bool have_k = s->prebuilt && s->pre_del_w == s->del_w && s->pre_del_c == s->del_c;  // queued by the last pass
@@ -441,79 +450,57 @@ int32_t body_fused(madqp_mpc* s, madqp_mpc_info* info_host) {
         TRY(madqp_kkt_set_aug_diagonal_reg(s->kkt, &s->st, s->del_w, s->del_c));
         TRY(madqp_kkt_build(s->kkt, &s->st));
     }
-    TRY(madqp_q_kkt_factorize(s->kkt, 15));
+    TRY(madqp_q_kkt_factorize(s->kkt, MPC_SL_INFO));
     s->n_factorizations += 1;
-    TRY(madqp_set_predictive_rhs(ctx, &s->st));                                  // :294
-    TRY(solve_system_queue(s, 0));
-    TRY(madqp_q_alpha_max(ctx, &s->st, 1.0, 3));                                 // :295
-    TRY(madqp_q_compl(ctx, &s->st, 1, 0.0, 0.0, ctx->d_res + 3, 11));            // :296, step lengths from the block
-    TRY(madqp_get_correction(ctx, &s->st));                                      // :297
-    TRY(madqp_q_compl(ctx, &s->st, 0, 0.0, 0.0, nullptr, 13));
-    // update_barrier! on the device: mu, the step rule's tau and mu_curr into the block (SL_MU ..) -- the corrector is
-    // queued behind the predictor without a read-back in between (round 4: a read-back costs 28 us and leaves the
-    // queue empty: the ~35 launches behind it are then issued at the host's 3.7 us each instead of the 1.6 us the
-    // GPU takes them at from a filled queue, tools/launch_probe.cpp)
-    const int SL_MU = 32, SL_TAU = 33, SL_MUCURR = 34, SL_NRM_B = 35, SL_ALPHA_B = 38, SL_DNORM_B = 46, SL_ALPHA_GZ = 49,
-              SL_MUC = 58;
-    TRY(madqp_q_mpc_mu(ctx, 11, SL_MU, nb, s->opt.mu_min, s->opt.step_rule, s->opt.step_param));
+    TRY(madqp_set_predictive_rhs(ctx, &s->st));                                                   // :294
+    TRY(solve_system_queue(s, MPC_SL_PRED_NRM));
+    TRY(madqp_q_alpha_max(ctx, &s->st, 1.0, MPC_SL_PRED_ALPHA));                                  // :295
+    TRY(madqp_q_compl(ctx, &s->st, 1, 0.0, 0.0, res + MPC_SL_PRED_ALPHA, MPC_SL_COMPL));          // :296, step lengths from the block
+    TRY(madqp_get_correction(ctx, &s->st));                                                       // :297
+    TRY(madqp_q_compl(ctx, &s->st, 0, 0.0, 0.0, nullptr, MPC_SL_COMPL + MPC_W_COMPL));
+    // update_barrier! on the device, into BARRIER: the corrector is queued behind the predictor without a read-back
+    TRY(madqp_q_mpc_mu(ctx, s->st.nlb + s->st.nub, s->opt.mu_min, s->opt.step_rule, s->opt.step_param));
     // (b) corrector.  The step rule's minima and |dx| are queued behind every direction that may turn out to be the
     // final one, so that the Gondzio loop below ends without a read-back of its own.
-    TRY(madqp_set_correction_rhs_dev(ctx, &s->st, ctx->d_res + SL_MU));  // :307
-    TRY(solve_system_queue(s, SL_NRM_B));
-    const bool gz = s->opt.max_ncorr > 0;
-    const double gz_tau = 0.995, gz_delta = 0.1, gz_bmin = 0.1, gz_bmax = 10.0;  // src/solver.jl:200-251
-    TRY(madqp_q_alpha_max_dev(ctx, &s->st, 0.0, ctx->d_res + SL_TAU, SL_ALPHA_B));
-    TRY(madqp_q_norm_inf3(ctx, s->st.n, s->st.d, nullptr, nullptr, SL_DNORM_B));  // print_iter, src/structure.jl:190
-    const int64_t len = ntot(s->st);
-    // gondzio(), first trial: queued behind the corrector, its step lengths min(alpha + delta, 1) and its mu_c formed on
-    // the device from the block -- the read-back that follows serves the corrector AND the trial
-    const int SL_TA = 64, SL_T_COMPL = 72, SL_T_NRM = 74, SL_T_AGZ = 77, SL_T_ATAU = 85, SL_T_DN = 93;
+    TRY(madqp_set_correction_rhs_dev(ctx, &s->st, res + MPC_SL_MU));  // :307
+    TRY(solve_system_queue(s, MPC_SL_CORR_NRM));
+    TRY(madqp_q_alpha_max_dev(ctx, &s->st, 0.0, res + MPC_SL_TAU, MPC_SL_CORR_ALPHA));
+    TRY(madqp_q_norm_inf3(ctx, s->st.n, s->st.d, nullptr, nullptr, MPC_SL_CORR_DNORM));  // print_iter, src/structure.jl:190
+    // gondzio(), first trial: queued behind the corrector, its step lengths and its mu_c formed on the device from the
+    // block -- the read-back that follows serves the corrector AND the trial
     if (gz) {
-        TRY(madqp_q_alpha_max(ctx, &s->st, gz_tau, SL_ALPHA_GZ));
-        TRY(madqp_q_mpc_trial_alpha(ctx, SL_ALPHA_GZ, SL_TA, gz_delta));
-        TRY(madqp_q_compl(ctx, &s->st, 1, 0.0, 0.0, ctx->d_res + SL_TA, SL_T_COMPL));
-        TRY(madqp_q_mpc_muc(ctx, SL_T_COMPL, SL_MUCURR, SL_MUC, nb));
-        TRY(madqp_set_extra_correction_dev(ctx, &s->st, 0.0, 0.0, gz_bmin, gz_bmax, ctx->d_res + SL_MUC, ctx->d_res + SL_TA));
-        TRY(madqp_set_correction_rhs_dev(ctx, &s->st, ctx->d_res + SL_MUC));
-        TRY(madqp_copy(ctx, len, s->st.d, s->w2));
-        TRY(solve_system_queue(s, SL_T_NRM));
-        TRY(madqp_q_alpha_max(ctx, &s->st, gz_tau, SL_T_AGZ));
-        TRY(madqp_q_alpha_max_dev(ctx, &s->st, 0.0, ctx->d_res + SL_TAU, SL_T_ATAU));  // in case this direction is kept
-        TRY(madqp_q_norm_inf3(ctx, s->st.n, s->st.d, nullptr, nullptr, SL_T_DN));      // and is the last one
+        TRY(madqp_q_alpha_max(ctx, &s->st, MPC_GZ_TAU, MPC_SL_GZ_ALPHA));
+        TRY(madqp_q_mpc_trial_alpha(ctx));
+        TRY(queue_gondzio_trial(s, res + MPC_SL_TRIAL_ALPHA, MpcSteps{0.0, 0.0}, MPC_SL_TRIAL_COMPL, MPC_SL_TRIAL));
     }
-    // The decisions of the read-back below, on the device too (SL_DEC ..), and behind them -- ahead of the read-back -- the
-    // update of the iterates and everything up to the next termination test's norms, as kernels that do nothing when
-    // the device's verdict is "the host takes over".  The block travels to the host twice: behind the decision (the host
-    // waits for THAT copy while the update runs) and behind the norms.
-    const int SL_DEC = 100, SL_C = 106;
-    double rb[MADQP_RESULT_SLOTS];
-    const int nrb = gz ? SL_T_DN + 3 : SL_DNORM_B + 3;
+    // Queued ahead: the decisions of the read-back below on the device too (DECISION) and phase (c) behind them; the
+    // block travels to the host behind the decision (the host waits for THAT copy while the update runs) and behind (c).
     // (Not in the first pass behind the start point: f and c are then the values initialize! left, from BEFORE the start
     // point moved x -- src/solver.jl:100-146 -- and an evaluation queued ahead would refresh them even where the host
     // takes over and the reference's loop goes on with the stale ones.)
+    double rb[MADQP_RESULT_SLOTS];
     const bool spec = s->ahead && s->moved;
     if (spec) {
-        MpcDecide dec{15, 0, SL_NRM_B, SL_ALPHA_B, SL_ALPHA_GZ, SL_T_NRM, SL_DEC, gz ? 1 : 0, s->opt.max_ncorr,
-                      s->opt.check_residual ? 1 : 0, s->opt.tol_linear_solve};
-        TRY(madqp_q_mpc_decide(ctx, &dec));
+        const MpcDecideOpt opt{gz ? 1 : 0, s->opt.max_ncorr, s->opt.check_residual ? 1 : 0, s->opt.tol_linear_solve};
+        TRY(madqp_q_mpc_decide(ctx, opt));
         TRY(madqp_results_post(ctx, s->h_early, s->ev_early));
-        if (gz) TRY(madqp_copy_if_dev(ctx, len, s->w2, s->st.d, ctx->d_res + SL_DEC + 3));
-        TRY(madqp_update_iterates_dev(ctx, &s->st, ctx->d_res + SL_DEC));                   // :332-335
-        TRY(madqp_q_kkt_eval(s->kkt, &s->st, s->q, s->rhs, SL_C));                          // :338-340
-        TRY(madqp_adjust_boundary_dev(ctx, &s->st, ctx->d_res + SL_DEC, ctx->d_res + SL_MU)); // :342
-        TRY(madqp_kkt_jtprod(s->kkt, s->st.jacl, s->st.y));                                 // :259-283 of the next pass
-        TRY(madqp_q_inf(ctx, &s->st, SL_C + 2));
-        TRY(madqp_results_post(ctx, s->h_final, s->ev_final));
-        TRY(madqp_results_wait(ctx, s->h_early, s->ev_early, SL_DEC + 4, rb));
+        TRY(queue_phase_c(s, res + MPC_SL_DECISION));
+        TRY(madqp_results_wait(ctx, s->h_early, s->ev_early, MPC_READ_DECISION, rb));
     } else {
-        TRY(madqp_read_results(ctx, nrb, rb));
+        TRY(madqp_read_results(ctx, gz ? MPC_READ_FIRST_TRIAL : MPC_READ_CORRECTOR, rb));
     }
     s->n_readbacks += 1;
-    const bool went = spec && rb[SL_DEC] != 0.0;  // the device has gone on: the host's decisions must be the same
+    // The host's replay of (b) from the block, with the rules the device used
+    const double* dec = rb + MPC_SL_DECISION;
+    const bool went = spec && dec[MPC_DEC_GO] != 0.0;  // the device has gone on: the host's decisions must be the same
     auto differ = [&]() {
         return madqp_fail(ctx, MADQP_ERR_HIP, "body_fused: the device's decisions behind the corrector are not the host's");
     };
-    s->last_info = (int32_t)rb[15];
+    auto verdict = [&](const double* nrm) {  // of a solve_system! call; a failed one cannot be behind a "go on"
+        const int32_t v = residual_verdict(s, nrm);
+        return (v && went) ? differ() : v;
+    };
+    s->last_info = (int32_t)rb[MPC_SL_INFO];
     TRY(madqp_kkt_factor_result(s->kkt, s->last_info));
     if (s->last_info != 0) {  // src/linear_solver.jl:6-17: what was queued behind the failed factorisation is void
         if (went) return differ();
@@ -522,76 +509,50 @@ int32_t body_fused(madqp_mpc* s, madqp_mpc_info* info_host) {
         TRY(factorize_regularized_system(s, 1));
         return body_after_factorization(s, info_host);
     }
-    {
-        int32_t v = residual_verdict(s, rb);  // the predictor's solve
-        if (!v) {
-            s->mu = rb[SL_MU];
-            v = residual_verdict(s, rb + SL_NRM_B);  // the corrector's
-        }
-        if (v) return went ? differ() : v;
-    }
-    s->alpha_p = min_like_host(rb[SL_ALPHA_B + 0], rb[SL_ALPHA_B + 2]);
-    s->alpha_d = min_like_host(rb[SL_ALPHA_B + 4], rb[SL_ALPHA_B + 6]);
-    s->dnorm = rb[SL_DNORM_B];
+    TRY(verdict(rb + MPC_SL_PRED_NRM));  // the predictor's solve
+    s->mu = rb[MPC_SL_MU];
+    TRY(verdict(rb + MPC_SL_CORR_NRM));  // the corrector's
+    auto take_step = [&](const double* a8, const double* dnorm) {  // update_step! from the block of the direction that stays
+        const MpcSteps a = mpc_steps(a8);
+        s->alpha_p = a.p;
+        s->alpha_d = a.d;
+        s->dnorm = *dnorm;
+    };
+    take_step(rb + MPC_SL_CORR_ALPHA, rb + MPC_SL_CORR_DNORM);
     if (gz) {  // the first trial is in the block; a further one (while the last was kept) costs a read-back of its own
-        double g_ap = min_like_host(rb[SL_ALPHA_GZ + 0], rb[SL_ALPHA_GZ + 2]);
-        double g_ad = min_like_host(rb[SL_ALPHA_GZ + 4], rb[SL_ALPHA_GZ + 6]);
-        const double* tb = rb + SL_T_NRM;  // norms [0..2], steps at gz_tau [3..10], steps at tau [11..18], |dx| [19]
-        double tr[32];
+        MpcSteps g = mpc_steps(rb + MPC_SL_GZ_ALPHA);
+        const double* tb = rb + MPC_SL_TRIAL;
+        double tr[MPC_READ_LATER_TRIAL];
         for (int c = 0; c < s->opt.max_ncorr; ++c) {
             if (c > 0) {
                 if (went) return differ();
-                const double ta_p = std::min(g_ap + gz_delta, 1.0), ta_d = std::min(g_ad + gz_delta, 1.0);
-                TRY(madqp_q_compl(ctx, &s->st, 1, ta_p, ta_d, nullptr, 0));
-                TRY(madqp_q_mpc_muc(ctx, 0, SL_MUCURR, SL_MUC, nb));
-                TRY(madqp_set_extra_correction_dev(ctx, &s->st, ta_p, ta_d, gz_bmin, gz_bmax, ctx->d_res + SL_MUC));
-                TRY(madqp_set_correction_rhs_dev(ctx, &s->st, ctx->d_res + SL_MUC));
-                TRY(madqp_copy(ctx, len, s->st.d, s->w2));
-                TRY(solve_system_queue(s, 0));
-                TRY(madqp_q_alpha_max(ctx, &s->st, gz_tau, 3));
-                TRY(madqp_q_alpha_max_dev(ctx, &s->st, 0.0, ctx->d_res + SL_TAU, 11));
-                TRY(madqp_q_norm_inf3(ctx, s->st.n, s->st.d, nullptr, nullptr, 19));
-                TRY(madqp_read_results(ctx, 22, tr));
+                TRY(queue_gondzio_trial(s, nullptr, mpc_trial_alpha(g), MPC_SL_LATER_COMPL, MPC_SL_LATER_TRIAL));
+                TRY(madqp_read_results(ctx, MPC_READ_LATER_TRIAL, tr));
                 s->n_readbacks += 1;
-                tb = tr;
+                tb = tr + MPC_SL_LATER_TRIAL;
             }
-            {
-                const int32_t v = residual_verdict(s, tb);
-                if (v) return went ? differ() : v;
-            }
-            const double ha_p = min_like_host(tb[3], tb[5]), ha_d = min_like_host(tb[7], tb[9]);
-            if (ha_p < 1.005 * g_ap || ha_d < 1.005 * g_ad) {
+            TRY(verdict(tb + MPC_TRIAL.nrm));
+            const MpcSteps h = mpc_steps(tb + MPC_TRIAL.alpha_gz);
+            if (mpc_trial_dropped(h, g)) {
                 if (went) {
-                    if (rb[SL_DEC + 3] == 0.0) return differ();  // (the device has put the direction back itself)
+                    if (dec[MPC_DEC_RESTORE] == 0.0) return differ();  // (the device has put the direction back itself)
                 } else {
-                    TRY(madqp_copy(ctx, len, s->w2, s->st.d));  // the direction before it, whose step is already known
+                    TRY(madqp_copy(ctx, ntot(s->st), s->w2, s->st.d));  // the direction before it, whose step is already known
                 }
                 break;
             }
-            if (went && c == 0 && rb[SL_DEC + 3] != 0.0) return differ();
-            g_ap = ha_p;
-            g_ad = ha_d;
-            s->alpha_p = min_like_host(tb[11], tb[13]);
-            s->alpha_d = min_like_host(tb[15], tb[17]);
-            s->dnorm = tb[19];
+            if (went && c == 0 && dec[MPC_DEC_RESTORE] != 0.0) return differ();
+            g = h;
+            take_step(tb + MPC_TRIAL.alpha_tau, tb + MPC_TRIAL.dnorm);
         }
     }
-    if (went && (rb[SL_DEC + 1] != s->alpha_p || rb[SL_DEC + 2] != s->alpha_d)) return differ();
+    if (went && (dec[MPC_DEC_ALPHA_P] != s->alpha_p || dec[MPC_DEC_ALPHA_D] != s->alpha_d)) return differ();
     // (c) update, objective, and the residuals the next termination test needs
-    if (!went) {
-        TRY(madqp_update_iterates(ctx, &s->st, s->alpha_p, s->alpha_d));  // :332-335
-        TRY(madqp_q_kkt_eval(s->kkt, &s->st, s->q, s->rhs, SL_C));        // :338-340
-        TRY(madqp_adjust_boundary(ctx, &s->st, s->mu));                   // :342
-        TRY(madqp_kkt_jtprod(s->kkt, s->st.jacl, s->st.y));               // :259-283 of the next pass
-        TRY(madqp_q_inf(ctx, &s->st, SL_C + 2));
-        if (s->ahead) TRY(madqp_results_post(ctx, s->h_final, s->ev_final));
-    }
+    if (!went) TRY(queue_phase_c(s, nullptr));
     if (s->ahead) {
-        // Queue the NEXT iteration's diagonal and assembly before waiting for the norms: the device does not run dry
-        // across the read-back and the driver's way around the loop (K is rebuilt from scratch every iteration; should
-        // the loop end here, a K nobody factors is all that happened)
-        // (not when this pass is the last one allowed, nor when the iterate it started from was already within 100 x the
-        // tolerance: the loop then usually ends behind this pass or the next, and the assembly would be for nobody)
+        // Queue the NEXT iteration's diagonal and assembly before waiting for the norms (see the head of this file) -- not
+        // when this pass is the last one allowed, nor when the iterate it started from was already within 100 x the
+        // tolerance: the loop then usually ends behind this pass or the next, and the assembly would be for nobody
         const double worst = std::max(s->inf_pr, std::max(s->inf_du, s->inf_compl));
         if (s->k + 1 < s->opt.max_iter && !(worst <= 100.0 * s->opt.tol)) {
             madqp_mpc nx = *s;  // the regularisation of the next pass, from a copy of the scalars
@@ -603,16 +564,15 @@ int32_t body_fused(madqp_mpc* s, madqp_mpc_info* info_host) {
             s->pre_del_c = nx.del_c;
             s->n_prebuilt += 1;
         }
-        TRY(madqp_results_wait(ctx, s->h_final, s->ev_final, SL_C + 6, rb));
+        TRY(madqp_results_wait(ctx, s->h_final, s->ev_final, MPC_READ_FINAL, rb));
     } else {
-        TRY(madqp_read_results(ctx, SL_C + 6, rb));
+        TRY(madqp_read_results(ctx, MPC_READ_FINAL, rb));
     }
     s->moved = true;
     s->k += 1;
     s->n_readbacks += 1;
-    const double* r = rb + SL_C;
-    s->obj = s->c0 + r[0] + 0.5 * r[1];
-    madqp_inf_from_block(r + 2, s->nrm_cached);
+    s->obj = s->c0 + rb[MPC_SL_OBJ_LIN] + 0.5 * rb[MPC_SL_OBJ_QUAD];
+    madqp_inf_from_block(rb + MPC_SL_INF, s->nrm_cached);
     s->head_cached = true;
     fill_info(s, info_host);
     return MADQP_OK;

@@ -103,134 +103,57 @@ extern "C" int32_t madqp_get_correction(madqp_ctx* ctx, const madqp_state* st) {
     return MADQP_OK;
 }
 
-extern "C" int32_t madqp_set_extra_correction(madqp_ctx* ctx, const madqp_state* st, double alpha_p,
-                                              double alpha_d, double beta_min, double beta_max,
-                                              double mu) {
-    CHECK_STATE();
-    ProfScope ps(ctx, MADQP_PROF_VEC);
-    LAUNCH(extra_correction_kernel, std::max(st->nlb, st->nub), *st, alpha_p, alpha_d,
-           beta_min * mu, beta_max * mu, nullptr, nullptr);
-    return MADQP_OK;
-}
-// the same with mu in device memory: the kernel forms beta_min * mu, beta_max * mu
+// mu_dev != nullptr: mu is read there and the kernel forms beta_min * mu, beta_max * mu; a8 != nullptr: the step lengths
+// are mpc_steps(a8), read on the device
 int32_t madqp_set_extra_correction_dev(madqp_ctx* ctx, const madqp_state* st, double alpha_p, double alpha_d,
                                        double beta_min, double beta_max, const double* mu_dev, const double* a8) {
     CHECK_STATE();
-    ARG_TRY(ctx, mu_dev != nullptr);
     ProfScope ps(ctx, MADQP_PROF_VEC);
     LAUNCH(extra_correction_kernel, std::max(st->nlb, st->nub), *st, alpha_p, alpha_d, beta_min, beta_max, mu_dev, a8);
     return MADQP_OK;
 }
-// min(alpha + delta, 1) for the primal and the dual step length of the block at res[in] (std::min's operand order twice,
-// as the host forms them), in the 8-slot pattern the step-length readers take
-__global__ void mpc_trial_alpha_kernel(double* __restrict__ res, int in, int out, double delta) {
-    if (threadIdx.x || blockIdx.x) return;
-    const double a0 = res[in], a1 = res[in + 2], a2 = res[in + 4], a3 = res[in + 6];
-    const double gp = ((a1 < a0) ? a1 : a0) + delta, gd = ((a3 < a2) ? a3 : a2) + delta;
-    const double tp = (1.0 < gp) ? 1.0 : gp, td = (1.0 < gd) ? 1.0 : gd;
-    res[out] = res[out + 2] = tp;
-    res[out + 4] = res[out + 6] = td;
-}
-int32_t madqp_q_mpc_trial_alpha(madqp_ctx* ctx, int in, int out, double delta) {
-    if (!ctx) return MADQP_ERR_ARG;
-    ARG_TRY(ctx, in >= 0 && in + 8 <= MADQP_FAULT_SLOT && out >= 0 && out + 8 <= MADQP_FAULT_SLOT);
-    ProfScope ps(ctx, MADQP_PROF_VEC);
-    hipLaunchKernelGGL(mpc_trial_alpha_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->d_res, in, out, delta);
-    LAUNCH_CHECK(ctx);
-    return MADQP_OK;
+extern "C" int32_t madqp_set_extra_correction(madqp_ctx* ctx, const madqp_state* st, double alpha_p,
+                                              double alpha_d, double beta_min, double beta_max,
+                                              double mu) {
+    return madqp_set_extra_correction_dev(ctx, st, alpha_p, alpha_d, beta_min * mu, beta_max * mu, nullptr, nullptr);
 }
 
 // ---- scalars of the iteration that never visit the host (mpc.hip, body_fused) -------------------------------------------
-// update_barrier!(Mehrotra) (src/kernels.jl:226-236) from the four complementarity sums of the result block:
-// res[out] = mu, res[out+1] = tau of the step rule, res[out+2] = mu_curr -- the arithmetic of the host form, operation
-// for operation ((mu_aff / mu_curr)^3 as t*t*t, which is what Julia's literal power is)
-__global__ void mpc_mu_kernel(double* __restrict__ res, int in, int out, double nb, double mu_min, int step_rule,
-                              double step_param) {
-    if (threadIdx.x || blockIdx.x) return;
-    const double mu_affine = nb > 0.0 ? (res[in] + res[in + 1]) / nb : 0.0;
-    const double mu_curr = nb > 0.0 ? (res[in + 2] + res[in + 3]) / nb : 0.0;
-    double sigma = 1.0;
-    if (nb > 0.0) {
-        const double t = mu_affine / mu_curr;
-        sigma = fmin(fmax(t * t * t, 1e-6), 10.0);
-    }
-    const double sm = sigma * mu_curr;
-    const double mu = (mu_min > sm) ? mu_min : sm;  // std::max(mu_min, sigma * mu_curr)
-    res[out] = mu;
-    const double om = 1.0 - mu;
-    res[out + 1] = (step_rule == 0) ? step_param : ((om > step_param) ? om : step_param);  // std::max(1 - mu, step_param)
-    res[out + 2] = mu_curr;
+// One thread and one rule of mpc_rules.inc each, between the fields of the result block that file names.
+#define ONE_THREAD if (threadIdx.x || blockIdx.x) return
+__global__ void mpc_trial_alpha_kernel(double* __restrict__ res) {
+    ONE_THREAD;
+    mpc_trial_alpha_block(res + MPC_SL_GZ_ALPHA, res + MPC_SL_TRIAL_ALPHA);
 }
-// gondzio_correction_direction! (src/solver.jl:200-251): mu_c = (ga / mu_curr)^2 ga from the two sums at res[in]
-__global__ void mpc_muc_kernel(double* __restrict__ res, int in, int mu_curr_slot, int out, double nb) {
-    if (threadIdx.x || blockIdx.x) return;
-    const double ga = nb > 0.0 ? (res[in] + res[in + 1]) / nb : 0.0;
-    const double mu_curr = res[mu_curr_slot];
-    res[out] = (ga / mu_curr) * (ga / mu_curr) * ga;
+__global__ void mpc_mu_kernel(double* __restrict__ res, double nb, double mu_min, int step_rule, double step_param) {
+    ONE_THREAD;
+    mpc_barrier_block(res + MPC_SL_COMPL, nb, mu_min, step_rule, step_param, res + MPC_SL_BARRIER);
 }
-int32_t madqp_q_mpc_mu(madqp_ctx* ctx, int in, int out, int64_t nb, double mu_min, int step_rule, double step_param) {
-    if (!ctx) return MADQP_ERR_ARG;
-    ARG_TRY(ctx, in >= 0 && in + 4 <= MADQP_FAULT_SLOT && out >= 0 && out + 3 <= MADQP_FAULT_SLOT);
-    ProfScope ps(ctx, MADQP_PROF_VEC);
-    hipLaunchKernelGGL(mpc_mu_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->d_res, in, out, (double)nb, mu_min, step_rule,
-                       step_param);
-    LAUNCH_CHECK(ctx);
-    return MADQP_OK;
+__global__ void mpc_muc_kernel(double* __restrict__ res, int compl_slot, double nb) {
+    ONE_THREAD;
+    res[MPC_SL_MUC] = mpc_muc(mpc_compl_mean(res + compl_slot, nb), res[MPC_SL_MUCURR]);
 }
-int32_t madqp_q_mpc_muc(madqp_ctx* ctx, int in, int mu_curr_slot, int out, int64_t nb) {
-    if (!ctx) return MADQP_ERR_ARG;
-    ARG_TRY(ctx, in >= 0 && in + 2 <= MADQP_FAULT_SLOT && out >= 0 && out < MADQP_FAULT_SLOT && mu_curr_slot >= 0 &&
-                     mu_curr_slot < MADQP_FAULT_SLOT);
-    ProfScope ps(ctx, MADQP_PROF_VEC);
-    hipLaunchKernelGGL(mpc_muc_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->d_res, in, mu_curr_slot, out, (double)nb);
-    LAUNCH_CHECK(ctx);
-    return MADQP_OK;
+__global__ void mpc_decide_kernel(double* res, MpcDecideOpt opt) {
+    ONE_THREAD;
+    mpc_decide(res, opt, res + MPC_SL_DECISION);
 }
-
-// The decisions body_fused takes from its read-back behind the corrector, taken on the device as well so that the
-// update of the iterates can be queued behind the corrector WITHOUT waiting for that read-back (mpc.hip): the residual
-// verdicts of both solve_system! calls (src/linear_solver.jl:36-43), the step lengths min(lower, upper) and, with
-// Gondzio corrections, whether the first trial is kept (src/solver.jl:231) -- the host's arithmetic, operation for
-// operation, on the same words.  res[out] = 1: the iteration goes on as queued (0: the host takes over: failed
-// factorisation, failed verdict, or a further trial to run); res[out+1], [out+2] = alpha_p, alpha_d;
-// res[out+3] = 1: the trial's direction is dropped, the one saved before it comes back.
-__global__ void mpc_decide_kernel(double* __restrict__ res, MpcDecide a) {
-    if (threadIdx.x || blockIdx.x) return;
-    auto bad = [&](const double* nrm) {
-        const double den = (1.0 < nrm[1]) ? nrm[1] : 1.0;  // std::max(1.0, nrm[1])
-        const double ratio = nrm[0] / den;
-        return (ratio != ratio) || (a.check_residual && ratio > a.tol_linear_solve);
-    };
-    auto mn = [](double x, double y) { return (y < x) ? y : x; };  // std::min(x, y)
-    bool go = res[a.info] == 0.0 && !bad(res + a.nrm_pred) && !bad(res + a.nrm_corr);
-    double ap = mn(res[a.alpha + 0], res[a.alpha + 2]), ad = mn(res[a.alpha + 4], res[a.alpha + 6]);
-    bool restore = false;
-    if (a.gondzio) {
-        const double g_ap = mn(res[a.alpha_gz + 0], res[a.alpha_gz + 2]), g_ad = mn(res[a.alpha_gz + 4], res[a.alpha_gz + 6]);
-        const double* tb = res + a.trial;  // norms [0..2], steps at Gondzio's tau [3..10], steps at the rule's tau [11..18]
-        go = go && !bad(tb);
-        const double ha_p = mn(tb[3], tb[5]), ha_d = mn(tb[7], tb[9]);
-        if (ha_p < 1.005 * g_ap || ha_d < 1.005 * g_ad) {
-            restore = go;
-        } else {
-            ap = mn(tb[11], tb[13]);
-            ad = mn(tb[15], tb[17]);
-            if (a.max_ncorr > 1) go = false;  // the next trial is the host's to queue
-        }
-    }
-    res[a.out] = go ? 1.0 : 0.0;
-    res[a.out + 1] = ap;
-    res[a.out + 2] = ad;
-    res[a.out + 3] = restore ? 1.0 : 0.0;
+#define LAUNCH_ONE_THREAD(kern, ...)                                                              \
+    do {                                                                                          \
+        if (!ctx) return MADQP_ERR_ARG;                                                           \
+        ProfScope ps(ctx, MADQP_PROF_VEC);                                                        \
+        hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, ctx->stream, ctx->d_res, ##__VA_ARGS__);   \
+        LAUNCH_CHECK(ctx);                                                                        \
+        return MADQP_OK;                                                                          \
+    } while (0)
+int32_t madqp_q_mpc_trial_alpha(madqp_ctx* ctx) { LAUNCH_ONE_THREAD(mpc_trial_alpha_kernel); }
+int32_t madqp_q_mpc_mu(madqp_ctx* ctx, int64_t nb, double mu_min, int step_rule, double step_param) {
+    LAUNCH_ONE_THREAD(mpc_mu_kernel, (double)nb, mu_min, step_rule, step_param);
 }
-int32_t madqp_q_mpc_decide(madqp_ctx* ctx, const MpcDecide* a) {
-    if (!ctx || !a) return MADQP_ERR_ARG;
-    ARG_TRY(ctx, a->out >= 0 && a->out + 4 <= MADQP_FAULT_SLOT);
-    ProfScope ps(ctx, MADQP_PROF_VEC);
-    hipLaunchKernelGGL(mpc_decide_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->d_res, *a);
-    LAUNCH_CHECK(ctx);
-    return MADQP_OK;
+int32_t madqp_q_mpc_muc(madqp_ctx* ctx, int compl_slot, int64_t nb) {
+    ARG_TRY(ctx, compl_slot >= 0 && compl_slot + MPC_W_COMPL <= MADQP_FAULT_SLOT);
+    LAUNCH_ONE_THREAD(mpc_muc_kernel, compl_slot, (double)nb);
 }
+int32_t madqp_q_mpc_decide(madqp_ctx* ctx, const MpcDecideOpt& opt) { LAUNCH_ONE_THREAD(mpc_decide_kernel, opt); }
 // dst = src where *flag != 0 (the dropped Gondzio trial's direction goes back, src/solver.jl:232)
 __global__ __launch_bounds__(TPB) void copy_if_kernel(int64_t len, const double* __restrict__ src, double* __restrict__ dst,
                                                       const double* __restrict__ flag) {
@@ -243,59 +166,6 @@ int32_t madqp_copy_if_dev(madqp_ctx* ctx, int64_t len, const double* src, double
     if (len == 0) return MADQP_OK;
     ProfScope ps(ctx, MADQP_PROF_VEC);
     LAUNCH(copy_if_kernel, len, len, src, dst, flag_dev);
-    return MADQP_OK;
-}
-// update_iterates / adjust_boundary with their scalars in the result block, and nothing done when dec[0] == 0
-__global__ __launch_bounds__(TPB) void update_iterates_dev_kernel(madqp_state s, const double* __restrict__ dec) {
-    if (dec[0] == 0.0) return;
-    const double ap = dec[1], ad = dec[2];
-    const double* dx = s.d;
-    const double* dy = s.d + s.n;
-    const double* dzl = dy + s.m;
-    const double* dzu = dzl + s.nlb;
-    int64_t L = s.n;
-    if (s.m > L) L = s.m;
-    if (s.nlb > L) L = s.nlb;
-    if (s.nub > L) L = s.nub;
-    GRID_STRIDE(i, L) {
-        if (i < s.n) s.x[i] += ap * dx[i];
-        if (i < s.m) s.y[i] += ad * dy[i];
-        if (i < s.nlb) s.zl[s.ind_lb[i]] += ad * dzl[i];
-        if (i < s.nub) s.zu[s.ind_ub[i]] += ad * dzu[i];
-    }
-}
-__global__ __launch_bounds__(TPB) void adjust_boundary_dev_kernel(madqp_state s, const double* __restrict__ dec,
-                                                                  const double* __restrict__ mu_dev, double eps, double c2) {
-    if (dec[0] == 0.0) return;
-    const double c1 = eps * *mu_dev;
-    const int64_t L = s.nlb > s.nub ? s.nlb : s.nub;
-    GRID_STRIDE(i, L) {
-        if (i < s.nlb) {
-            const int64_t j = s.ind_lb[i];
-            const double x = s.x[j], l = s.xl[j];
-            if (x - l < c1) s.xl[j] = l - c2 * fmax(1.0, fabs(x));
-        }
-        if (i < s.nub) {
-            const int64_t j = s.ind_ub[i];
-            const double x = s.x[j], u = s.xu[j];
-            if (u - x < c1) s.xu[j] = u + c2 * fmax(1.0, fabs(x));
-        }
-    }
-}
-int32_t madqp_update_iterates_dev(madqp_ctx* ctx, const madqp_state* st, const double* dec_dev) {
-    CHECK_STATE();
-    ARG_TRY(ctx, dec_dev != nullptr);
-    ProfScope ps(ctx, MADQP_PROF_VEC);
-    LAUNCH(update_iterates_dev_kernel, max4(st->n, st->m, st->nlb, st->nub), *st, dec_dev);
-    return MADQP_OK;
-}
-int32_t madqp_adjust_boundary_dev(madqp_ctx* ctx, const madqp_state* st, const double* dec_dev, const double* mu_dev) {
-    CHECK_STATE();
-    ARG_TRY(ctx, dec_dev && mu_dev);
-    ProfScope ps(ctx, MADQP_PROF_VEC);
-    if (std::max(st->nlb, st->nub) > 0)
-        LAUNCH(adjust_boundary_dev_kernel, std::max(st->nlb, st->nub), *st, dec_dev, mu_dev, 2.220446049250313e-16,
-               1.8189894035458565e-12);
     return MADQP_OK;
 }
 
@@ -331,7 +201,7 @@ static int32_t compl_launch(madqp_ctx* ctx, const madqp_state* st, int affine, d
     double out[2];
     r = madqp_read_results(ctx, 2, out);
     if (r) return r;
-    *mu_host = (out[0] + out[1]) / (double)(st->nlb + st->nub);
+    *mu_host = mpc_compl_mean(out, (double)(st->nlb + st->nub));
     return MADQP_OK;
 }
 extern "C" int32_t madqp_get_complementarity_measure(madqp_ctx* ctx, const madqp_state* st,
@@ -352,7 +222,6 @@ __global__ void alpha_none_kernel(double* __restrict__ res) {  // no bounds: alp
     }
 }
 }  // namespace
-int32_t madqp_q_alpha_max_dev(madqp_ctx* ctx, const madqp_state* st, double tau, const double* tau_dev, int slot0);
 int32_t madqp_q_alpha_max(madqp_ctx* ctx, const madqp_state* st, double tau, int slot0) {
     return madqp_q_alpha_max_dev(ctx, st, tau, nullptr, slot0);
 }
@@ -399,12 +268,16 @@ extern "C" int32_t madqp_get_alpha_max(madqp_ctx* ctx, const madqp_state* st, do
     return MADQP_OK;
 }
 
-extern "C" int32_t madqp_update_iterates(madqp_ctx* ctx, const madqp_state* st, double alpha_p,
-                                         double alpha_d) {
+int32_t madqp_update_iterates_dev(madqp_ctx* ctx, const madqp_state* st, double alpha_p, double alpha_d,
+                                  const double* dec_dev) {
     CHECK_STATE();
     ProfScope ps(ctx, MADQP_PROF_VEC);
-    LAUNCH(update_iterates_kernel, max4(st->n, st->m, st->nlb, st->nub), *st, alpha_p, alpha_d);
+    LAUNCH(update_iterates_kernel, max4(st->n, st->m, st->nlb, st->nub), *st, alpha_p, alpha_d, dec_dev);
     return MADQP_OK;
+}
+extern "C" int32_t madqp_update_iterates(madqp_ctx* ctx, const madqp_state* st, double alpha_p,
+                                         double alpha_d) {
+    return madqp_update_iterates_dev(ctx, st, alpha_p, alpha_d, nullptr);
 }
 // 4 slots: |c|, dual, complementarity lower / upper (madqp_inf_from_block combines the last two)
 int32_t madqp_q_inf(madqp_ctx* ctx, const madqp_state* st, int slot0) {
@@ -444,15 +317,19 @@ extern "C" int32_t madqp_get_inf(madqp_ctx* ctx, const madqp_state* st, double* 
     return MADQP_OK;
 }
 
-extern "C" int32_t madqp_adjust_boundary(madqp_ctx* ctx, const madqp_state* st, double mu) {
+int32_t madqp_adjust_boundary_dev(madqp_ctx* ctx, const madqp_state* st, double mu, const double* dec_dev,
+                                  const double* mu_dev) {
     CHECK_STATE();
     const double eps = 2.220446049250313e-16;
-    const double c1 = eps * mu;
+    const double c1 = mu_dev ? eps : eps * mu;  // (the kernel multiplies by *mu_dev)
     const double c2 = 1.8189894035458565e-12;  // eps^(3/4)
     ProfScope ps(ctx, MADQP_PROF_VEC);
     if (std::max(st->nlb, st->nub) > 0)
-        LAUNCH(adjust_boundary_kernel, std::max(st->nlb, st->nub), *st, c1, c2);
+        LAUNCH(adjust_boundary_kernel, std::max(st->nlb, st->nub), *st, c1, c2, dec_dev, mu_dev);
     return MADQP_OK;
+}
+extern "C" int32_t madqp_adjust_boundary(madqp_ctx* ctx, const madqp_state* st, double mu) {
+    return madqp_adjust_boundary_dev(ctx, st, mu, nullptr, nullptr);
 }
 
 extern "C" int32_t madqp_reduce_rhs(madqp_ctx* ctx, const madqp_state* st, double* w) {

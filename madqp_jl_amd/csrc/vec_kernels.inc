@@ -143,9 +143,9 @@ MQ_KERNEL correction_kernel(madqp_state s) {
 // read on the device instead of coming back from the host (the fused iteration of mpc.hip).
 __device__ __forceinline__ void alphas_from_block(const double* a8, double& ap, double& ad) {
     if (!a8) return;
-    const double a0 = a8[0], a1 = a8[2], a2 = a8[4], a3 = a8[6];
-    ap = (a1 < a0) ? a1 : a0;
-    ad = (a3 < a2) ? a3 : a2;
+    const MpcSteps a = mpc_steps(a8);
+    ap = a.p;
+    ad = a.d;
 }
 
 // mu_dev != nullptr: tmin, tmax are beta_min, beta_max and are multiplied by *mu_dev here (as the host does otherwise)
@@ -182,8 +182,14 @@ MQ_KERNEL extra_correction_kernel(madqp_state s, double ap, double ad,
     }
 }
 
-
-MQ_KERNEL update_iterates_kernel(madqp_state s, double ap, double ad) {
+// dec != nullptr (the DECISION words of mpc_rules.inc, in device memory): nothing moves unless the device's verdict was
+// "go on", and the step lengths are the ones it decided
+MQ_KERNEL update_iterates_kernel(madqp_state s, double ap, double ad, const double* __restrict__ dec) {
+    if (dec) {
+        if (dec[MPC_DEC_GO] == 0.0) return;
+        ap = dec[MPC_DEC_ALPHA_P];
+        ad = dec[MPC_DEC_ALPHA_D];
+    }
     const double* dx = s.d;
     const double* dy = s.d + s.n;
     const double* dzl = dy + s.m;
@@ -200,7 +206,11 @@ MQ_KERNEL update_iterates_kernel(madqp_state s, double ap, double ad) {
     }
 }
 
-MQ_KERNEL adjust_boundary_kernel(madqp_state s, double c1, double c2) {
+// dec as above; mu_dev != nullptr: c1 is eps and is multiplied by *mu_dev here (as the host does otherwise)
+MQ_KERNEL adjust_boundary_kernel(madqp_state s, double c1, double c2, const double* __restrict__ dec,
+                                 const double* __restrict__ mu_dev) {
+    if (dec && dec[MPC_DEC_GO] == 0.0) return;
+    if (mu_dev) c1 = c1 * *mu_dev;
     const int64_t L = s.nlb > s.nub ? s.nlb : s.nub;
     GRID_STRIDE(i, L) {
         if (i < s.nlb) {
