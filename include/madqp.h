@@ -269,7 +269,15 @@ int32_t madqp_chol_destroy(madqp_chol* s);
 int32_t madqp_chol_set_signature(madqp_chol* s, int64_t npos);
 /* MadNLP.factorize!: in-place lower Cholesky of the n x n matrix at A (blocked left-looking,
  * MFMA panel updates).  info_host: 0 = success, j>0 = leading minor of order j not positive
- * definite (LAPACK dpotrf convention; maps to is_factorized, src/utils.jl:54-62). */
+ * definite (LAPACK dpotrf convention; maps to is_factorized, src/utils.jl:54-62).
+ * The call never aborts on such a matrix (tests/test_gpu_chol_info.py holds each point, in every schedule):
+ *  - a pivot that is NaN is reported like one that is not positive (the test is !(pivot > 0));
+ *  - with several failing columns the first one is reported;
+ *  - the factorisation completes with unit pivots from column j on: the columns left of j are those of the factor of the
+ *    leading minor of order j - 1, what lies from column j on has no meaning;
+ *  - the strict upper triangle and the rows beyond n of each column (the padding of lda) are not written;
+ *  - the next madqp_chol_factor on the handle starts clean, whatever this one reported: its info, its factor and the
+ *    solves behind it are bitwise those of a new handle. */
 int32_t madqp_chol_factor(madqp_chol* s, double* A, int64_t lda, int32_t* info_host);
 /* MadNLP.solve!(linear_solver, rhs): rhs <- (L L')^-1 rhs in place (two triangular sweeps) */
 int32_t madqp_chol_solve(madqp_chol* s, double* rhs);
