@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "kkt_form.inc"
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
@@ -238,7 +239,7 @@ __global__ __launch_bounds__(256) void bq_prewrite_h_kernel(const double* __rest
 struct madqp_batch {
     madqp_ctx* ctx;
     BQ q;
-    std::vector<void*> owned;
+    DevOwner mem;  // every device buffer of the batch
     int32_t* d_active;
     // one lock-step iteration (13 launches + 2 masked retry rounds) captured once as a hipGraph and replayed on an internal stream
     hipStream_t sG = nullptr;
@@ -253,22 +254,6 @@ struct madqp_batch {
 };
 
 namespace {
-template <class T>
-int32_t dalloc(madqp_batch* b, T** p, int64_t count, bool zero = false) {
-    *p = nullptr;
-    const size_t bytes = (size_t)std::max<int64_t>(count, 1) * sizeof(T);
-    hipError_t e = hipMalloc(p, bytes);
-    if (e != hipSuccess)
-        return madqp_fail(b->ctx, MADQP_ERR_ALLOC, "madqp_batch_create: hipMalloc(%zu): %s", bytes,
-                          hipGetErrorString(e));
-    b->owned.push_back(*p);
-    if (zero) {
-        e = hipMemsetAsync(*p, 0, bytes, b->ctx->stream);
-        if (e != hipSuccess) return madqp_fail(b->ctx, MADQP_ERR_HIP, "hipMemset: %s", hipGetErrorString(e));
-    }
-    return MADQP_OK;
-}
-
 // build_kkt! + factorize! for every active problem: one assembly launch, ~2 nx/128 launches of Cholesky
 // retry == true: the masked x100-retry rounds -- the launches have RETRY_SLOTS problem slots in place of B problems and
 // work off the compacted list bq_retry_kernel has just written (usually empty: every workgroup leaves after one load;
@@ -336,8 +321,7 @@ extern "C" int32_t madqp_batch_destroy(madqp_batch* b) {
     if (b->evIn) (void)hipEventDestroy(b->evIn);
     if (b->evOut) (void)hipEventDestroy(b->evOut);
     if (b->sG) (void)hipStreamDestroy(b->sG);
-    for (void* p : b->owned) (void)hipFree(p);
-    delete b;
+    delete b;  // (its owner frees the buffers)
     return MADQP_OK;
 }
 
@@ -355,32 +339,23 @@ struct PatternHost {
 // slot map of one problem's ind_ineq (strictly increasing rows in [0, m)): row -> slack index or -1
 bool append_slots(const int64_t* ineq, int64_t ns, int64_t m, std::vector<int64_t>& slot) {
     const size_t base = slot.size();
-    slot.resize(base + (size_t)m, -1);
-    for (int64_t k = 0; k < ns; ++k) {
-        const int64_t r = ineq[k];
-        if (!(r >= 0 && r < m && (k == 0 || ineq[k - 1] < r))) return false;
-        slot[base + (size_t)r] = k;
-    }
-    return true;
+    slot.resize(base + (size_t)m);
+    return kkt_slot_map(ineq, ns, m, slot.data() + base);
 }
 
 int32_t create_batch(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, PatternHost& ph, const int64_t* ind_lb,
-                     const int64_t* ind_ub, std::vector<void*>&& owned, const madqp_batch_data* data,
+                     const int64_t* ind_ub, DevOwner& lists, const madqp_batch_data* data,
                      const madqp_mpc_options* opt, madqp_batch** out) {
     const int32_t normal = opt->kkt_form;
     // the condensed form needs delta_d < 0 on equality rows (conventions)
     if (!normal && ph.any_eq && !(opt->regularization != 0 && opt->delta_d < 0.0)) {
-        for (void* p : owned) (void)hipFree(p);
         return madqp_fail(ctx, MADQP_ERR_ARG, "bad argument: the condensed form needs delta_d < 0 on equality rows");
     }
     *out = nullptr;
     madqp_batch* b = new (std::nothrow) madqp_batch();
-    if (!b) {
-        for (void* p : owned) (void)hipFree(p);
-        return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
-    }
-    b->ctx = ctx;
-    b->owned = std::move(owned);
+    if (!b) return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
+    b->ctx = b->mem.ctx = ctx;
+    b->mem.take(lists);
     // measured at (512, 256): 512 threads per problem are faster up to B = 512 and equal at 1024
     static const int wide_max = getenv("MADQP_BATCH_WIDE_MAX") ? atoi(getenv("MADQP_BATCH_WIDE_MAX")) : 1024;
     b->wide = B <= wide_max;
@@ -417,7 +392,7 @@ int32_t create_batch(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, PatternHo
     int32_t r = MADQP_OK;
     int64_t *d_pat = nullptr, *d_ineq = nullptr, *d_slot = nullptr;
 #define BALLOC(ptr, count, ...)                                   \
-    if (r == MADQP_OK) r = dalloc(b, &(ptr), (count), ##__VA_ARGS__)
+    if (r == MADQP_OK) r = b->mem.alloc(&(ptr), (count), "madqp_batch_create", ##__VA_ARGS__)
     BALLOC(d_pat, B * PAT_LEN);
     BALLOC(d_ineq, (int64_t)ph.ineq.size());
     BALLOC(d_slot, (int64_t)ph.slot.size());
@@ -534,7 +509,8 @@ extern "C" int32_t madqp_batch_create(madqp_ctx* ctx, int64_t B, int64_t nx, int
     ph.nlb_total = B * nlb;
     ph.nub_total = B * nub;
     ph.any_eq = ns < m;
-    return create_batch(ctx, B, nx, m, ph, ind_lb, ind_ub, {}, data, opt, out);
+    DevOwner none(ctx);
+    return create_batch(ctx, B, nx, m, ph, ind_lb, ind_ub, none, data, opt, out);
 }
 
 extern "C" int32_t madqp_batch_create_patterns(madqp_ctx* ctx, int64_t B, int64_t nx, int64_t m, const int64_t* ineq_ptr,
@@ -591,23 +567,15 @@ extern "C" int32_t madqp_batch_create_patterns(madqp_ctx* ctx, int64_t B, int64_
     }
     if (ineq_ptr[B]) ph.ineq.assign(ind_ineq_host, ind_ineq_host + ineq_ptr[B]);
     // the bound lists: copied into arrays the batch owns
-    std::vector<void*> owned;
+    DevOwner lists(ctx);  // (freed here unless create_batch takes them)
     int64_t* d_lists[2] = {nullptr, nullptr};
     const int64_t* hl[2] = {ind_lb_host, ind_ub_host};
     const int64_t len[2] = {lb_ptr[B], ub_ptr[B]};
     for (int k = 0; k < 2; ++k) {
-        const size_t bytes = (size_t)std::max<int64_t>(len[k], 1) * sizeof(int64_t);
-        hipError_t e = hipMalloc(&d_lists[k], bytes);
-        if (e == hipSuccess) {
-            owned.push_back(d_lists[k]);
-            if (len[k]) e = hipMemcpy(d_lists[k], hl[k], len[k] * sizeof(int64_t), hipMemcpyHostToDevice);
-        }
-        if (e != hipSuccess) {
-            for (void* p : owned) (void)hipFree(p);
-            return madqp_fail(ctx, MADQP_ERR_HIP, "madqp_batch_create_patterns: bound lists: %s", hipGetErrorString(e));
-        }
+        if (int32_t r = lists.alloc(&d_lists[k], len[k], "madqp_batch_create_patterns: bound lists")) return r;
+        if (len[k]) HIP_TRY(ctx, hipMemcpy(d_lists[k], hl[k], len[k] * sizeof(int64_t), hipMemcpyHostToDevice));
     }
-    return create_batch(ctx, B, nx, m, ph, d_lists[0], d_lists[1], std::move(owned), data, opt, out);
+    return create_batch(ctx, B, nx, m, ph, d_lists[0], d_lists[1], lists, data, opt, out);
 }
 
 // one workgroup program for the whole batch: 512 or 256 threads per problem, from namespace W / N
@@ -797,14 +765,11 @@ extern "C" int32_t madqp_batch_set_trace(madqp_batch* b, int64_t capacity) {
     BQ& q = b->q;
     double* tr = nullptr;
     int32_t* cnt = nullptr;
-    const size_t before = b->owned.size();
-    int32_t r = dalloc(b, &tr, q.B * capacity * T_COUNT, true);
-    if (r == MADQP_OK) r = dalloc(b, &cnt, q.B, true);
+    const size_t before = b->mem.owned.size();
+    int32_t r = b->mem.alloc(&tr, q.B * capacity * T_COUNT, "madqp_batch_set_trace", true);
+    if (r == MADQP_OK) r = b->mem.alloc(&cnt, q.B, "madqp_batch_set_trace", true);
     if (r != MADQP_OK) {  // the handle stays usable, without a trace
-        while (b->owned.size() > before) {
-            (void)hipFree(b->owned.back());
-            b->owned.pop_back();
-        }
+        b->mem.release(before);
         (void)hipGetLastError();
         return r;
     }

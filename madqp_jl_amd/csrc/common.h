@@ -195,20 +195,89 @@ int32_t madqp_symv_lower(madqp_ctx* ctx, int64_t n, double alpha, const double* 
 int32_t madqp_symv_upper(madqp_ctx* ctx, int64_t n, double alpha, const double* H, int64_t ldh, const double* x,
                          double beta, double* y, int prof_cls);
 
-// sparse.hip
-int32_t madqp_spmv_csr(madqp_ctx* ctx, int64_t rows, const int64_t* rowptr, const int64_t* col, const double* val,
-                       double alpha, const double* x, double beta, double* y, int prof_cls);
-// rows of V as CSR (rowptr/col/val) and columns of V as CSR of V' (t_ptr/t_col/t_val); the base dense (base, ldbase),
-// a symmetric matrix with both triangles in CSR (b_ptr/b_col/b_val), or none
-int32_t madqp_sparse_gram(madqp_ctx* ctx, int64_t n, const int64_t* rowptr, const int64_t* col, const double* val,
-                          const int64_t* t_ptr, const int64_t* t_col, const double* t_val, const double* w,
-                          const double* base, int64_t ldbase, const double* dvec, const int64_t* b_ptr,
-                          const int64_t* b_col, const double* b_val, double* C, int64_t ldc);
+// sparse.hip: a CSR matrix in device memory (int64 indices, column indices ascending within a row), borrowed
+struct Csr {
+    const int64_t* ptr = nullptr;
+    const int64_t* col = nullptr;
+    const double* val = nullptr;
+};
+int32_t madqp_spmv_csr(madqp_ctx* ctx, int64_t rows, const Csr& a, double alpha, const double* x, double beta, double* y,
+                       int prof_cls);
+// C = base + diag(dvec) + V diag(w) V' (lower triangle) from the rows of V (v) and the rows of V' (vt); the base dense
+// (base, ldbase), a symmetric matrix with both triangles in CSR (b), or none
+int32_t madqp_sparse_gram(madqp_ctx* ctx, int64_t n, const Csr& v, const Csr& vt, const double* w, const double* base,
+                          int64_t ldbase, const double* dvec, const Csr& b, double* C, int64_t ldc);
 // the band form (madqp_kkt_set_bandwidth): column j over the rows j .. min(n-1, j+extent), zeros beyond j+bw; sparse or no base
-int32_t madqp_sparse_gram_band(madqp_ctx* ctx, int64_t n, const int64_t* rowptr, const int64_t* col, const double* val,
-                               const int64_t* t_ptr, const int64_t* t_col, const double* t_val, const double* w,
-                               const double* dvec, const int64_t* b_ptr, const int64_t* b_col, const double* b_val,
-                               double* C, int64_t ldc, int64_t bw, int64_t extent);
+int32_t madqp_sparse_gram_band(madqp_ctx* ctx, int64_t n, const Csr& v, const Csr& vt, const double* w, const double* dvec,
+                               const Csr& b, double* C, int64_t ldc, int64_t bw, int64_t extent);
+
+// gemm_f64.hip: lower triangle of C = base + diag(dvec) + B' diag(w) B (madqp_syrk_assemble without its ctx check)
+int32_t madqp_syrk_assemble_impl(madqp_ctx* ctx, int64_t n, int64_t kdim, const double* B, int64_t ldb, const double* w,
+                                 const double* base, int64_t ldbase, const double* dvec, double* C, int64_t ldc);
+
+// The device buffers an object owns (madqp_kkt, madqp_dkkt, madqp_batch): every allocation is recorded and freed by
+// release() or the destructor.  `who` is the caller's name for the message of a failure.
+struct DevOwner {
+    madqp_ctx* ctx = nullptr;
+    std::vector<void*> owned;
+    DevOwner() = default;
+    explicit DevOwner(madqp_ctx* c) : ctx(c) {}
+    DevOwner(const DevOwner&) = delete;
+    DevOwner& operator=(const DevOwner&) = delete;
+    ~DevOwner() { release(); }
+    // max(count, 1) elements, optionally zeroed on the stream
+    template <class T>
+    int32_t alloc(T** p, int64_t count, const char* who, bool zero = false) {
+        *p = nullptr;
+        const size_t bytes = (size_t)(count > 1 ? count : 1) * sizeof(T);
+        hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) {
+            *p = nullptr;
+            (void)hipGetLastError();
+            return madqp_fail(ctx, MADQP_ERR_ALLOC, "%s: hipMalloc(%zu): %s", who, bytes, hipGetErrorString(e));
+        }
+        owned.push_back(*p);
+        if (zero && (e = hipMemsetAsync(*p, 0, bytes, ctx->stream)) != hipSuccess)
+            return madqp_fail(ctx, MADQP_ERR_HIP, "%s: hipMemset: %s", who, hipGetErrorString(e));
+        return MADQP_OK;
+    }
+    // A grow-only buffer of *have elements (contents are not kept).  Kernels in flight may still read the old buffer, so
+    // the stream is synchronised before it is freed.  After a failure the buffer is gone: *p == nullptr, *have == 0.
+    template <class T>
+    int32_t grow(T** p, int64_t* have, int64_t want, const char* who) {
+        if (*p && want <= *have) return MADQP_OK;
+        if (*p) {
+            (void)hipStreamSynchronize(ctx->stream);
+            drop(*p);
+        }
+        *have = 0;
+        const int32_t r = alloc(p, want, who);
+        if (!r) *have = want;
+        return r;
+    }
+    // the buffers of another owner become this one's
+    void take(DevOwner& o) {
+        owned.insert(owned.end(), o.owned.begin(), o.owned.end());
+        o.owned.clear();
+    }
+    // frees the buffers recorded at position `from` and later (0: all of them)
+    void release(size_t from = 0) {
+        while (owned.size() > from) {
+            (void)hipFree(owned.back());
+            owned.pop_back();
+        }
+    }
+
+private:
+    void drop(void* q) {
+        for (size_t i = 0; i < owned.size(); ++i)
+            if (owned[i] == q) {
+                owned.erase(owned.begin() + (std::ptrdiff_t)i);
+                break;
+            }
+        (void)hipFree(q);
+    }
+};
 
 // chol.hip: the panel solve of one 128-column block, X (rows x 128) <- X L^-T by block substitution (see there); w < 128 only
 // with rows <= 0 (a short block is the last of its matrix or tile).  (The products with the 128 x 128 inverse of rounds

@@ -12,7 +12,8 @@
 
 #include <rccl/rccl.h>
 
-#include "common.h"
+#include "grid_kernels.h"
+#include "kkt_form.inc"
 
 namespace {
 struct Rccl {
@@ -625,16 +626,7 @@ extern "C" int32_t madqp_dist_bytes_sent(madqp_dist* d, int64_t* bytes_host) {
 // Iterates, right-hand sides and every scalar are replicated (n + m doubles); products with A, A' and H are summed over
 // the ranks with ONE all-reduce each (every lower tile of H and every column block of A has exactly one owner, the
 // diagonal-tile owner of that block), so all ranks see bitwise identical vectors and take identical branches.
-#define TPB 256
-#define MADQP_MAX_BLOCKS 1024
 namespace {
-#define MQ_KERNEL __global__ __launch_bounds__(TPB) void
-#define MQ_BLOCK blockIdx.x
-#define GRID_STRIDE(i, len) \
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < (len); i += (int64_t)gridDim.x * TPB)
-inline int dk_grid(int64_t len) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((len + TPB - 1) / TPB, MADQP_MAX_BLOCKS));
-}
 #include "kkt_kernels.inc"
 
 // S[k, :] = theta[k] * A[k, :] (root != 0: sqrt(theta[k])) for k < m, zero rows up to m16
@@ -683,37 +675,29 @@ __global__ __launch_bounds__(256) void dk_axpby_kernel(int64_t n, double alpha, 
 }  // namespace
 
 struct madqp_dkkt {
-    madqp_dist* d;
-    madqp_ctx* ctx;
-    int64_t nx, m, ns, m16;
-    const double* H;  // local tiles (ldh) or nullptr
-    int64_t ldh;
-    const double *AI, *AJ;
-    int64_t ldai, ldaj;
-    double* SJ;          // Theta * A_J (m16 x ncp), owned
-    int64_t* d_ind_ineq; // ns
-    int64_t* d_slot;     // m
-    int64_t* d_diag;     // local diagonal tiles: (li, lj, I) triples
-    int64_t ndiag;
+    madqp_dist* d = nullptr;
+    madqp_ctx* ctx = nullptr;
+    int64_t nx = 0, m = 0, ns = 0, m16 = 0;
+    const double* H = nullptr;  // local tiles (ldh) or nullptr
+    int64_t ldh = 0;
+    const double *AI = nullptr, *AJ = nullptr;
+    int64_t ldai = 0, ldaj = 0;
+    DevOwner mem;                   // every device buffer below
+    double* SJ = nullptr;           // Theta * A_J (m16 x ncp)
+    int64_t* d_ind_ineq = nullptr;  // ns
+    int64_t* d_slot = nullptr;      // m
+    int64_t* d_diag = nullptr;      // local diagonal tiles: (li, lj, I) triples
+    int64_t ndiag = 0;
     std::vector<int64_t> own_li;  // local tile rows whose A / H column block this rank owns for the mat-vecs
-    double *theta, *t, *u;        // m
-    double *gn, *gm;              // n + m contiguous: all-reduce buffer
-    double *xr, *yr, *yc;         // local-order scratch: mloc, mloc, nloc
+    double *theta = nullptr, *t = nullptr, *u = nullptr;  // m
+    double *gn = nullptr, *gm = nullptr;                  // n + m contiguous: all-reduce buffer
+    double *xr = nullptr, *yr = nullptr, *yc = nullptr;   // local-order scratch: mloc, mloc, nloc
 };
-
-#define DKL(kern, len, ...)                                                                       \
-    do {                                                                                          \
-        hipLaunchKernelGGL(kern, dim3(dk_grid(len)), dim3(TPB), 0, ctx->stream, __VA_ARGS__);     \
-        LAUNCH_CHECK(ctx);                                                                        \
-    } while (0)
 
 extern "C" int32_t madqp_dkkt_destroy(madqp_dkkt* k) {
     if (!k) return MADQP_OK;
     (void)hipStreamSynchronize(k->ctx->stream);
-    void* ptrs[] = {k->SJ, k->d_ind_ineq, k->d_slot, k->d_diag, k->theta, k->t, k->u, k->gn, k->xr, k->yr, k->yc};
-    for (void* ptr : ptrs)
-        if (ptr) (void)hipFree(ptr);
-    delete k;
+    delete k;  // (its owner frees the buffers)
     return MADQP_OK;
 }
 
@@ -726,16 +710,12 @@ extern "C" int32_t madqp_dkkt_create(madqp_dist* d, int64_t nx, int64_t m, int64
     ARG_TRY(ctx, nx == d->n && m >= 0 && ns >= 0 && ns <= m && (ns == 0 || ind_ineq_host));
     ARG_TRY(ctx, !Hloc || ldh >= d->ld);
     ARG_TRY(ctx, m == 0 || nx == 0 || (A_I && ld_ai >= d->ld && A_J && ld_aj >= d->ncp));
-    std::vector<int64_t> slot((size_t)std::max<int64_t>(m, 1), -1);
-    for (int64_t k = 0; k < ns; ++k) {
-        const int64_t r = ind_ineq_host[k];
-        ARG_TRY(ctx, r >= 0 && r < m && slot[r] < 0 && (k == 0 || ind_ineq_host[k - 1] < r));
-        slot[r] = k;
-    }
+    std::vector<int64_t> slot((size_t)std::max<int64_t>(m, 1));
+    ARG_TRY(ctx, kkt_slot_map(ind_ineq_host, ns, m, slot.data()));
     madqp_dkkt* k = new (std::nothrow) madqp_dkkt();
     if (!k) return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
     k->d = d;
-    k->ctx = ctx;
+    k->ctx = k->mem.ctx = ctx;
     k->nx = nx;
     k->m = m;
     k->ns = ns;
@@ -746,9 +726,6 @@ extern "C" int32_t madqp_dkkt_create(madqp_dist* d, int64_t nx, int64_t m, int64
     k->ldai = ld_ai;
     k->AJ = A_J;
     k->ldaj = ld_aj;
-    k->SJ = nullptr;
-    k->d_ind_ineq = k->d_slot = k->d_diag = nullptr;
-    k->theta = k->t = k->u = k->gn = k->gm = k->xr = k->yr = k->yc = nullptr;
     std::vector<int64_t> diag;
     for (int64_t li = 0; li < d->mt; ++li) {
         const int64_t I = li * d->P + d->p;
@@ -758,25 +735,27 @@ extern "C" int32_t madqp_dkkt_create(madqp_dist* d, int64_t nx, int64_t m, int64
         }
     }
     k->ndiag = (int64_t)diag.size() / 3;
-    const size_t mb = (size_t)std::max<int64_t>(m, 1) * sizeof(double);
-    hipError_t e = hipMalloc(&k->SJ, (size_t)std::max<int64_t>(k->m16 * d->ncp, 1) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&k->d_ind_ineq, (size_t)std::max<int64_t>(ns, 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(&k->d_slot, (size_t)std::max<int64_t>(m, 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(&k->d_diag, (size_t)std::max<int64_t>(3 * k->ndiag, 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(&k->theta, mb);
-    if (e == hipSuccess) e = hipMalloc(&k->t, mb);
-    if (e == hipSuccess) e = hipMalloc(&k->u, mb);
-    if (e == hipSuccess) e = hipMalloc(&k->gn, (size_t)std::max<int64_t>(nx + m, 1) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&k->xr, (size_t)d->ld * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&k->yr, (size_t)d->ld * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&k->yc, (size_t)d->ncp * sizeof(double));
-    if (e == hipSuccess && ns) e = hipMemcpy(k->d_ind_ineq, ind_ineq_host, ns * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && m) e = hipMemcpy(k->d_slot, slot.data(), m * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && k->ndiag)
+    const char* who = "madqp_dkkt_create";
+    int32_t r = k->mem.alloc(&k->SJ, k->m16 * d->ncp, who);
+    if (!r) r = k->mem.alloc(&k->d_ind_ineq, ns, who);
+    if (!r) r = k->mem.alloc(&k->d_slot, m, who);
+    if (!r) r = k->mem.alloc(&k->d_diag, 3 * k->ndiag, who);
+    if (!r) r = k->mem.alloc(&k->theta, m, who);
+    if (!r) r = k->mem.alloc(&k->t, m, who);
+    if (!r) r = k->mem.alloc(&k->u, m, who);
+    if (!r) r = k->mem.alloc(&k->gn, nx + m, who);
+    if (!r) r = k->mem.alloc(&k->xr, d->ld, who);
+    if (!r) r = k->mem.alloc(&k->yr, d->ld, who);
+    if (!r) r = k->mem.alloc(&k->yc, d->ncp, who);
+    hipError_t e = hipSuccess;
+    if (!r && ns) e = hipMemcpy(k->d_ind_ineq, ind_ineq_host, ns * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (!r && e == hipSuccess && m) e = hipMemcpy(k->d_slot, slot.data(), m * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (!r && e == hipSuccess && k->ndiag)
         e = hipMemcpy(k->d_diag, diag.data(), diag.size() * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
+    if (!r && e != hipSuccess) r = madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_dkkt_create: %s", hipGetErrorString(e));
+    if (r) {
         madqp_dkkt_destroy(k);
-        return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_dkkt_create: %s", hipGetErrorString(e));
+        return r;
     }
     k->gm = k->gn + nx;
     *out = k;
@@ -832,7 +811,7 @@ static int32_t dk_H_partial(madqp_dkkt* k, double alpha, const double* x) {
         return madqp_symv_upper(ctx, d->n, alpha, k->H, k->ldh, x, 1.0, k->gn, MADQP_PROF_GEMV);
     {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        DKL(dk_gather_kernel, d->mloc, d->mloc, nb, (int64_t)d->P, (int64_t)d->p, d->n, x, k->xr);
+        LAUNCH(dk_gather_kernel, d->mloc, d->mloc, nb, (int64_t)d->P, (int64_t)d->p, d->n, x, k->xr);
         HIP_TRY(ctx, hipMemsetAsync(k->yr, 0, (size_t)d->mloc * sizeof(double), ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(k->yc, 0, (size_t)d->nloc * sizeof(double), ctx->stream));
     }
@@ -853,8 +832,8 @@ static int32_t dk_H_partial(madqp_dkkt* k, double alpha, const double* x) {
         }
     }
     ProfScope ps(ctx, MADQP_PROF_VEC);
-    DKL(dk_scatter_add_kernel, d->mloc, d->mloc, nb, (int64_t)d->P, (int64_t)d->p, d->n, k->yr, alpha, k->gn);
-    DKL(dk_scatter_add_kernel, d->nloc, d->nloc, nb, (int64_t)d->Q, (int64_t)d->q, d->n, k->yc, alpha, k->gn);
+    LAUNCH(dk_scatter_add_kernel, d->mloc, d->mloc, nb, (int64_t)d->P, (int64_t)d->p, d->n, k->yr, alpha, k->gn);
+    LAUNCH(dk_scatter_add_kernel, d->nloc, d->nloc, nb, (int64_t)d->Q, (int64_t)d->q, d->n, k->yc, alpha, k->gn);
     return MADQP_OK;
 }
 static int32_t dk_zero(madqp_dkkt* k, double* ptr, int64_t count) {
@@ -870,7 +849,7 @@ extern "C" int32_t madqp_dkkt_build(madqp_dkkt* k, const madqp_state* st) {
     madqp_dist* d = k->d;
     {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        if (k->m) DKL(theta_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, st->du_diag, k->theta);
+        if (k->m) LAUNCH(theta_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, st->du_diag, k->theta);
         if (k->m16 && d->nloc) {
             const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((d->ncp + 255) / 256, 64));
             // one rank: A_I and A_J are the same columns, so K = H + S'S with ONE operand stream S = sqrt(Theta) A
@@ -922,19 +901,19 @@ extern "C" int32_t madqp_dkkt_solve(madqp_dkkt* k, const madqp_state* st, double
     if (k->m) {
         {
             ProfScope ps(ctx, MADQP_PROF_VEC);
-            DKL(condense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, wx, wy, k->t, k->u);
+            LAUNCH(condense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, wx, wy, k->t, k->u);
         }
         if ((r = dk_zero(k, k->gn, k->nx)) || (r = dk_At_partial(k, 1.0, k->u))) return r;
         if ((r = distcore::comm_allreduce(d, k->gn, k->nx, GRP_WORLD))) return r;
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        DKL(dk_axpby_kernel, k->nx, k->nx, 1.0, k->gn, 1.0, wx);  // rhs_x = r1_x + A' (theta t)
+        LAUNCH(dk_axpby_kernel, k->nx, k->nx, 1.0, k->gn, 1.0, wx);  // rhs_x = r1_x + A' (theta t)
     }
     if ((r = madqp_dist_solve(d, wx))) return r;
     if (k->m) {
         if ((r = dk_zero(k, k->gm, k->m)) || (r = dk_A_partial(k, 1.0, wx))) return r;
         if ((r = distcore::comm_allreduce(d, k->gm, k->m, GRP_WORLD))) return r;
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        DKL(decondense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, k->t, k->gm, wx, wy);
+        LAUNCH(decondense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, k->t, k->gm, wx, wy);
     }
     return madqp_finish_aug_solve(ctx, st, w);
 }
@@ -948,8 +927,8 @@ extern "C" int32_t madqp_dkkt_jtprod(madqp_dkkt* k, double* out, const double* y
     if ((r = dk_zero(k, k->gn, k->nx)) || (r = dk_At_partial(k, 1.0, y))) return r;
     if ((r = distcore::comm_allreduce(k->d, k->gn, k->nx, GRP_WORLD))) return r;
     ProfScope ps(ctx, MADQP_PROF_VEC);
-    if (k->nx) DKL(dk_axpby_kernel, k->nx, k->nx, 1.0, k->gn, 0.0, out);
-    if (k->ns) DKL(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, y, out + k->nx, 1.0, 0.0);
+    if (k->nx) LAUNCH(dk_axpby_kernel, k->nx, k->nx, 1.0, k->gn, 0.0, out);
+    if (k->ns) LAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, y, out + k->nx, 1.0, 0.0);
     return MADQP_OK;
 }
 
@@ -968,9 +947,9 @@ extern "C" int32_t madqp_dkkt_mul(madqp_dkkt* k, const madqp_state* st, double* 
     if ((r = distcore::comm_allreduce(k->d, k->gn, nx + k->m, GRP_WORLD))) return r;
     {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        if (nx) DKL(dk_axpby_kernel, nx, nx, alpha, k->gn, beta, w);
-        if (k->ns) DKL(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, v + n, w + nx, alpha, beta);
-        if (k->m) DKL(mul_rows_kernel, k->m, k->m, k->d_slot, k->gm, v + nx, w + n, alpha, beta);
+        if (nx) LAUNCH(dk_axpby_kernel, nx, nx, alpha, k->gn, beta, w);
+        if (k->ns) LAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, v + n, w + nx, alpha, beta);
+        if (k->m) LAUNCH(mul_rows_kernel, k->m, k->m, k->d_slot, k->gm, v + nx, w + n, alpha, beta);
     }
     return madqp_kktmul(ctx, st, w, v, alpha, beta);
 }
@@ -988,9 +967,9 @@ extern "C" int32_t madqp_dkkt_eval(madqp_dkkt* k, const madqp_state* st, const d
     if ((r = distcore::comm_allreduce(k->d, k->gn, nx + k->m, GRP_WORLD))) return r;
     double sums[2] = {0.0, 0.0};
     if (n) {
-        const int nb = dk_grid(n);
+        const int nb = grid_for(n);
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        if (k->H && nx) DKL(dk_axpby_kernel, nx, nx, 1.0, k->gn, 0.0, st->f);
+        if (k->H && nx) LAUNCH(dk_axpby_kernel, nx, nx, 1.0, k->gn, 0.0, st->f);
         hipLaunchKernelGGL(eval_grad_kernel, dim3(nb), dim3(TPB), 0, ctx->stream, n, nx, (k->H && nx) ? 1 : 0, q, st->x,
                            st->f, ctx->d_part);
         LAUNCH_CHECK(ctx);
@@ -999,8 +978,8 @@ extern "C" int32_t madqp_dkkt_eval(madqp_dkkt* k, const madqp_state* st, const d
     }
     if (k->m) {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        DKL(dk_axpby_kernel, k->m, k->m, 1.0, k->gm, 0.0, st->c);
-        DKL(eval_cons_kernel, k->m, k->m, k->d_slot, st->x + nx, rhs, st->c);
+        LAUNCH(dk_axpby_kernel, k->m, k->m, 1.0, k->gm, 0.0, st->c);
+        LAUNCH(eval_cons_kernel, k->m, k->m, k->d_slot, st->x + nx, rhs, st->c);
     }
     if (n) {
         if ((r = madqp_read_results(ctx, 2, sums))) return r;

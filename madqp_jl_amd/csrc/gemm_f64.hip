@@ -472,12 +472,9 @@ __global__ __launch_bounds__(256) void scale_rows_kernel(int64_t n, int64_t npad
 }
 }  // namespace
 
-// Lower triangle of C = base + diag(dvec) + B' diag(w) B, restricted to the column ranges
-// [ranges[2r], ranges[2r+1]) (rows >= the range start); ranges == nullptr: all columns.
-static int32_t syrk_assemble_impl(madqp_ctx* ctx, int64_t n, int64_t kdim, const double* B, int64_t ldb,
-                                  const double* w, const double* base, int64_t ldbase,
-                                  const double* dvec, double* C, int64_t ldc, int64_t nranges,
-                                  const int64_t* ranges) {
+// Lower triangle of C = base + diag(dvec) + B' diag(w) B (declared in common.h: kkt.hip assembles through it).
+int32_t madqp_syrk_assemble_impl(madqp_ctx* ctx, int64_t n, int64_t kdim, const double* B, int64_t ldb, const double* w,
+                                 const double* base, int64_t ldbase, const double* dvec, double* C, int64_t ldc) {
     ARG_TRY(ctx, n >= 0 && kdim >= 0 && C && ldc >= n && (kdim == 0 || (B && ldb >= n)));
     ARG_TRY(ctx, !base || ldbase >= n);
     const double* X = B ? B : C;  // K == 0: never dereferenced
@@ -509,15 +506,6 @@ static int32_t syrk_assemble_impl(madqp_ctx* ctx, int64_t n, int64_t kdim, const
         ldx = npad;
         K = kpad;
     }
-    if (ranges) {
-        bool any = false;
-        for (int64_t r = 0; r < nranges; ++r) {
-            ARG_TRY(ctx, 0 <= ranges[2 * r] && ranges[2 * r] <= ranges[2 * r + 1] && ranges[2 * r + 1] <= n &&
-                             ranges[2 * r] % BM == 0);
-            any = any || ranges[2 * r + 1] > ranges[2 * r];
-        }
-        if (!any) return MADQP_OK;
-    }
     GemmArgs g{};
     g.X = X;
     g.ldx = ldx;
@@ -536,14 +524,7 @@ static int32_t syrk_assemble_impl(madqp_ctx* ctx, int64_t n, int64_t kdim, const
     g.N = n;
     g.diag_off = 0;
     g.lower_only = 1;
-    return madqp_gemm_tn(ctx, g, MADQP_PROF_SYRK, ranges, ranges ? nranges : 0);  // one launch, masked columns
-}
-
-int32_t madqp_syrk_assemble_ranges(madqp_ctx* ctx, int64_t n, int64_t kdim, const double* B, int64_t ldb,
-                                   const double* w, const double* base, int64_t ldbase,
-                                   const double* dvec, double* C, int64_t ldc, int64_t nranges,
-                                   const int64_t* ranges) {
-    return syrk_assemble_impl(ctx, n, kdim, B, ldb, w, base, ldbase, dvec, C, ldc, nranges, ranges);
+    return madqp_gemm_tn(ctx, g, MADQP_PROF_SYRK);
 }
 
 extern "C" int32_t madqp_syrk_assemble(madqp_ctx* ctx, int64_t n, int64_t kdim, const double* B,
@@ -551,7 +532,7 @@ extern "C" int32_t madqp_syrk_assemble(madqp_ctx* ctx, int64_t n, int64_t kdim, 
                                        int64_t ldbase, const double* dvec, double* C,
                                        int64_t ldc) {
     ARG_TRY(ctx, ctx != nullptr);
-    return syrk_assemble_impl(ctx, n, kdim, B, ldb, w, base, ldbase, dvec, C, ldc, 0, nullptr);
+    return madqp_syrk_assemble_impl(ctx, n, kdim, B, ldb, w, base, ldbase, dvec, C, ldc);
 }
 
 // Test seam: one call of madqp_gemm_tn with every argument in the caller's hands, and a report of the launch form the

@@ -27,76 +27,64 @@
 // values -- pr_diag as it stands, Hessian entries times scaling_i scaling_j, Jacobian entries times scaling_j, du_diag
 // as it stands -- with the slack block eliminated as in the unscaled case (1/S_k becomes scaling_k^2 / pr_diag_k):
 // every entry stays bounded as the iterates converge.
-#include <algorithm>
-
-#include "common.h"
-
-#define TPB 256
-#define MADQP_MAX_BLOCKS 1024
-
-enum { KKT_CONDENSED = 0, KKT_NORMAL = 1, KKT_AUGMENTED = 2 };
+#include "grid_kernels.h"
+#include "kkt_form.inc"  // KKT_CONDENSED / KKT_NORMAL / KKT_AUGMENTED, the slot map, the orders, the bandwidth of a pattern
 
 struct madqp_kkt {
-    madqp_ctx* ctx;
-    int mode;
-    int64_t nx, m, ns;
-    const double* H;
-    int64_t ldh;
-    const double* A;  // m x nx, row k = constraint k contiguous (condensed mode)
-    int64_t lda;
-    const double* At;  // nx x m, row k = variable k contiguous (normal mode)
-    int64_t ldat;
-    // sparse front end (either mode): CSR of A (m rows) and CSR of A' (nx rows); A == At == nullptr then
-    const int64_t *a_ptr, *a_col, *at_ptr, *at_col;
-    const double *a_val, *at_val;
-    const double* hdiag;  // diagonal Hessian (nx), instead of the dense H; borrowed
+    madqp_ctx* ctx = nullptr;
+    int mode = KKT_CONDENSED;
+    int64_t nx = 0, m = 0, ns = 0;
+    const double* H = nullptr;
+    int64_t ldh = 0;
+    const double* A = nullptr;  // m x nx, row k = constraint k contiguous (condensed mode)
+    int64_t lda = 0;
+    const double* At = nullptr;  // nx x m, row k = variable k contiguous (normal mode)
+    int64_t ldat = 0;
+    Csr a, at;  // sparse front end (either mode): CSR of A (m rows) and CSR of A' (nx rows); A == At == nullptr then
+    const double* hdiag = nullptr;  // diagonal Hessian (nx), instead of the dense H; borrowed
     // sparse Hessian instead of the dense H (sparse front end, condensed or augmented): the full symmetric pattern in
     // CSR, nx rows, column indices ascending within a row; borrowed (madqp_kkt_set_hcsr)
-    const int64_t *h_ptr, *h_col;
-    const double* h_val;
-    double* sg;           // Sigma + [hdiag; 0] (n), owned; the solves divide by it
-    double *dn, *tn;  // normal mode: 1/Sigma (n) and an n-vector of scratch
-    int64_t* d_ind_ineq;  // ns
-    int64_t* d_slot;      // m: slack slot of a row, -1 for an equality row
-    double* K;
-    int64_t ldk;
-    double *theta, *t, *u;  // m
-    const double* u_is_A_of;  // condensed mode: u = A x for the primal part of this vector (the last solve's), or nullptr
-    int64_t np;             // augmented mode: nx rounded up to a multiple of 128 = row of the first constraint
-    double* b;              // augmented mode: right-hand side of order np + m
-    int scaled;             // augmented mode: K2.5 (see the header comment)
-    double *sfac, *sb;      // K2.5: scaling factor (n) and a scratch n-vector
-    madqp_chol* chol;
-    // refinement steps madqp_kkt_solve runs itself (madqp_kkt_set_refine; 0 = none, the default) and their two work vectors
-    int32_t refine;
-    double *rf_p, *rf_r;
-    int64_t rf_len;
+    Csr h;
+    DevOwner mem;          // every device buffer below
+    double* sg = nullptr;  // Sigma + [hdiag; 0] (n); the solves divide by it
+    double *dn = nullptr, *tn = nullptr;  // normal mode: 1/Sigma (n) and an n-vector of scratch
+    int64_t* d_ind_ineq = nullptr;        // ns
+    int64_t* d_slot = nullptr;            // m: slack slot of a row, -1 for an equality row
+    double* K = nullptr;
+    int64_t ldk = 0;
+    double *theta = nullptr, *t = nullptr, *u = nullptr;  // m
+    const double* u_is_A_of = nullptr;  // condensed mode: u = A x for the primal part of this vector (the last solve's), or nullptr
+    int64_t np = 0;         // augmented mode: nx rounded up to a multiple of 128 = row of the first constraint
+    double* b = nullptr;    // augmented mode: right-hand side of order np + m
+    int scaled = 0;         // augmented mode: K2.5 (see the header comment)
+    double *sfac = nullptr, *sb = nullptr;  // K2.5: scaling factor (n) and a scratch n-vector
+    madqp_chol* chol = nullptr;
+    // refinement steps madqp_kkt_solve runs itself (madqp_kkt_set_refine; 0 = none, the default) and their two work vectors,
+    // one grow-only buffer
+    int32_t refine = 0;
+    double* rf = nullptr;
+    int64_t rf_cap = 0;
     // fused per-variable passes of the condensed mode (solve_pre_kernel / solve_post_kernel / resid_tail_kernel below):
-    // where each variable sits in the two bound lists (-1: not there), built when the lists are first seen, and the
-    // reduced right-hand side of the slacks kept between the two passes around the sweeps
-    int32_t *pos_lb, *pos_ub;
-    const int64_t *pos_key_lb, *pos_key_ub;
-    int64_t pos_nlb, pos_nub, pos_n;
-    double* rs;
-    bool fuse;  // MADQP_KKT_FUSE != 0
+    // where each variable sits in the two bound lists (-1: not there), built when the lists are first seen (grow-only
+    // buffers, allocated with rs at the first fused pass), and the reduced right-hand side of the slacks kept between the
+    // two passes around the sweeps
+    int32_t *pos_lb = nullptr, *pos_ub = nullptr;
+    int64_t pos_lb_cap = 0, pos_ub_cap = 0;
+    bool pos_ok = false;  // the maps are those of the keys below
+    const int64_t *pos_key_lb = nullptr, *pos_key_ub = nullptr;
+    int64_t pos_nlb = 0, pos_nub = 0, pos_n = 0;
+    double* rs = nullptr;  // ns
+    bool fuse = true;      // MADQP_KKT_FUSE != 0
     // band-limited assembly and factorisation (madqp_kkt_set_bandwidth): half-bandwidth of K (-1: none) and the rows below
     // the diagonal the factorisation reaches (madqp_chol_band_extent), which every build rewrites
-    int64_t bw, band_extent;
+    int64_t bw = -1, band_extent = 0;
     // packed band storage (madqp_kkt_create_sparse_packed): no K until madqp_kkt_set_bandwidth allocates the band alone --
     // entry (i, j) at K[i + j ldk], ldk >= band_extent (band_plan.inc); k_doubles: what K holds, either form
-    bool packed;
-    int64_t k_doubles;
+    bool packed = false;
+    int64_t k_doubles = 0;
 };
 
 namespace {
-#define MQ_KERNEL __global__ __launch_bounds__(TPB) void
-#define MQ_BLOCK blockIdx.x
-#define GRID_STRIDE(i, len) \
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < (len); i += (int64_t)gridDim.x * TPB)
-inline int grid_for(int64_t len) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((len + TPB - 1) / TPB, MADQP_MAX_BLOCKS));
-}
-
 #include "kkt_kernels.inc"
 
 // ---- fused per-variable passes of the condensed mode ---------------------------------------------------------------------
@@ -397,70 +385,54 @@ __global__ __launch_bounds__(TPB) void k25_ones_kernel(int64_t n, double* a) {
 }
 }  // namespace
 
-#define KLAUNCH(kern, len, ...)                                                                 \
-    do {                                                                                        \
-        hipLaunchKernelGGL(kern, dim3(grid_for(len)), dim3(TPB), 0, ctx->stream, __VA_ARGS__);  \
-        LAUNCH_CHECK(ctx);                                                                      \
-    } while (0)
-
 // y(m) = alpha A x(nx) + beta y   /   y(nx) = alpha A' x(m) + beta y, from whichever layout is held
 static int32_t apply_A(madqp_kkt* k, double alpha, const double* x, double beta, double* y) {
-    if (k->a_ptr)
-        return madqp_spmv_csr(k->ctx, k->m, k->a_ptr, k->a_col, k->a_val, alpha, x, beta, y, MADQP_PROF_GEMV);
+    if (k->a.ptr) return madqp_spmv_csr(k->ctx, k->m, k->a, alpha, x, beta, y, MADQP_PROF_GEMV);
     if (k->A) return madqp_gemv_impl(k->ctx, 0, k->m, k->nx, alpha, k->A, k->lda, x, beta, y, MADQP_PROF_GEMV);
     return madqp_gemv_impl(k->ctx, 1, k->nx, k->m, alpha, k->At, k->ldat, x, beta, y, MADQP_PROF_GEMV);
 }
 static int32_t apply_At(madqp_kkt* k, double alpha, const double* x, double beta, double* y) {
-    if (k->a_ptr)
-        return madqp_spmv_csr(k->ctx, k->nx, k->at_ptr, k->at_col, k->at_val, alpha, x, beta, y, MADQP_PROF_GEMV);
+    if (k->a.ptr) return madqp_spmv_csr(k->ctx, k->nx, k->at, alpha, x, beta, y, MADQP_PROF_GEMV);
     if (k->A) return madqp_gemv_impl(k->ctx, 1, k->m, k->nx, alpha, k->A, k->lda, x, beta, y, MADQP_PROF_GEMV);
     return madqp_gemv_impl(k->ctx, 0, k->nx, k->m, alpha, k->At, k->ldat, x, beta, y, MADQP_PROF_GEMV);
+}
+// y(nx) = alpha H x(nx) + beta y for the Hessian the object holds (at most one kind), beta 0 or 1; nothing without one
+static bool kkt_has_H(const madqp_kkt* k) { return (k->H || k->hdiag || k->h.ptr) && k->nx; }
+static int32_t apply_H(madqp_kkt* k, double alpha, const double* x, double beta, double* y) {
+    madqp_ctx* ctx = k->ctx;
+    if (!kkt_has_H(k)) return MADQP_OK;
+    ARG_TRY(ctx, beta == 0.0 || beta == 1.0);
+    if (k->H)  // H is symmetric: its lower triangle is enough (gemv.hip: madqp_symv_lower)
+        return madqp_symv_lower(ctx, k->nx, alpha, k->H, k->ldh, x, beta, y, MADQP_PROF_GEMV);
+    if (k->h.ptr)  // both triangles are stored: one row-wise mat-vec, fixed order
+        return madqp_spmv_csr(ctx, k->nx, k->h, alpha, x, beta, y, MADQP_PROF_GEMV);
+    ProfScope ps(ctx, MADQP_PROF_VEC);
+    LAUNCH(hdiag_mul_kernel, k->nx, k->nx, alpha, k->hdiag, x, beta, y);
+    return MADQP_OK;
 }
 
 extern "C" int32_t madqp_kkt_destroy(madqp_kkt* k) {
     if (!k) return MADQP_OK;
     (void)hipStreamSynchronize(k->ctx->stream);
     if (k->chol) madqp_chol_destroy(k->chol);
-    if (k->d_ind_ineq) (void)hipFree(k->d_ind_ineq);
-    if (k->d_slot) (void)hipFree(k->d_slot);
-    if (k->K) (void)hipFree(k->K);
-    if (k->theta) (void)hipFree(k->theta);
-    if (k->t) (void)hipFree(k->t);
-    if (k->u) (void)hipFree(k->u);
-    if (k->sg) (void)hipFree(k->sg);
-    if (k->dn) (void)hipFree(k->dn);
-    if (k->tn) (void)hipFree(k->tn);
-    if (k->b) (void)hipFree(k->b);
-    if (k->sfac) (void)hipFree(k->sfac);
-    if (k->sb) (void)hipFree(k->sb);
-    if (k->rf_p) (void)hipFree(k->rf_p);
-    if (k->rf_r) (void)hipFree(k->rf_r);
-    if (k->pos_lb) (void)hipFree(k->pos_lb);
-    if (k->pos_ub) (void)hipFree(k->pos_ub);
-    if (k->rs) (void)hipFree(k->rs);
-    delete k;
+    delete k;  // (its owner frees the buffers)
     return MADQP_OK;
 }
 
+// Every creation function ends here.  a / at: the borrowed CSR of A and A' of the sparse front end (A == At == nullptr
+// then); packed: no K until madqp_kkt_set_bandwidth knows the band's extent.  On failure *out stays nullptr.
 static int32_t kkt_create_common(madqp_ctx* ctx, int mode, int64_t nx, int64_t m, int64_t ns,
                                  const int64_t* ind_ineq_host, const double* H, int64_t ldh,
                                  const double* A, int64_t lda, const double* At, int64_t ldat,
-                                 madqp_kkt** out, bool packed = false) {
+                                 const Csr& a, const Csr& at, bool packed, madqp_kkt** out) {
     ARG_TRY(ctx, out && nx >= 0 && m >= 0 && ns >= 0 && ns <= m);
     ARG_TRY(ctx, ns == 0 || ind_ineq_host);
     *out = nullptr;
-    std::vector<int64_t> slot((size_t)std::max<int64_t>(m, 1), -1);
-    for (int64_t k = 0; k < ns; ++k) {
-        const int64_t r = ind_ineq_host[k];
-        ARG_TRY(ctx, r >= 0 && r < m && slot[r] < 0);
-        ARG_TRY(ctx, k == 0 || ind_ineq_host[k - 1] < r);
-        slot[r] = k;
-    }
+    std::vector<int64_t> slot((size_t)std::max<int64_t>(m, 1));
+    ARG_TRY(ctx, kkt_slot_map(ind_ineq_host, ns, m, slot.data()));
     madqp_kkt* k = new (std::nothrow) madqp_kkt();
     if (!k) return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
-    memset(k, 0, sizeof(*k));
-    k->ctx = ctx;
-    k->bw = -1;
+    k->ctx = k->mem.ctx = ctx;
     k->mode = mode;
     k->nx = nx;
     k->m = m;
@@ -475,44 +447,34 @@ static int32_t kkt_create_common(madqp_ctx* ctx, int mode, int64_t nx, int64_t m
     k->lda = lda;
     k->At = At;
     k->ldat = ldat;
-    k->np = (nx + 127) / 128 * 128;
-    // order of the matrix that is factorised
-    const int64_t dim = (mode == KKT_NORMAL) ? m : (mode == KKT_AUGMENTED) ? k->np + m : nx;
-    const int64_t n = nx + ns;
-    // leading dimension and column count padded to a multiple of 128 (zero filled): every GEMM tile
-    // of the factorisation is a full tile (see GemmArgs::Mread)
-    const int64_t dpad = std::max<int64_t>(128, (dim + 127) / 128 * 128);
-    k->ldk = dpad;
-    const size_t mb = (size_t)std::max<int64_t>(m, 1) * sizeof(double);
-    const size_t nb = (size_t)std::max<int64_t>(n, 1) * sizeof(double);
-    // +128 doubles of slack after the last column (room for 16-byte tile loads at the edge)
-    hipError_t e = hipSuccess;
+    k->a = a;
+    k->at = at;
+    const KktOrders o = kkt_orders(mode, nx, m);
+    k->np = o.np;
     k->packed = packed;
-    if (packed) {  // the band alone, once its extent is known (madqp_kkt_set_bandwidth)
-        k->ldk = 0;
-    } else {
-        k->k_doubles = k->ldk * dpad + 128;
-        e = hipMalloc(&k->K, (size_t)k->k_doubles * sizeof(double));
-        if (e == hipSuccess) e = hipMemset(k->K, 0, (size_t)k->k_doubles * sizeof(double));
+    const int64_t n = nx + ns;
+    const char* who = "madqp_kkt_create";
+    int32_t r = MADQP_OK;
+    if (!packed) {  // (packed: the band alone, once its extent is known)
+        k->ldk = o.ldk;
+        k->k_doubles = o.k_doubles;
+        r = k->mem.alloc(&k->K, o.k_doubles, who, /*zero=*/true);
     }
-    if (e == hipSuccess) e = hipMalloc(&k->d_ind_ineq, (size_t)std::max<int64_t>(ns, 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(&k->d_slot, (size_t)std::max<int64_t>(m, 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMalloc(&k->theta, mb);
-    if (e == hipSuccess) e = hipMalloc(&k->t, mb);
-    if (e == hipSuccess) e = hipMalloc(&k->u, mb);
-    if (e == hipSuccess && mode == KKT_NORMAL) e = hipMalloc(&k->dn, nb);
-    if (e == hipSuccess && mode == KKT_NORMAL) e = hipMalloc(&k->tn, nb);
-    if (e == hipSuccess && mode == KKT_AUGMENTED) e = hipMalloc(&k->b, (size_t)std::max<int64_t>(dim, 1) * sizeof(double));
-    if (e == hipSuccess && ns)
-        e = hipMemcpy(k->d_ind_ineq, ind_ineq_host, ns * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess && m)
-        e = hipMemcpy(k->d_slot, slot.data(), m * sizeof(int64_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        madqp_kkt_destroy(k);
-        return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_kkt_create(nx=%lld, m=%lld): %s",
-                          (long long)nx, (long long)m, hipGetErrorString(e));
-    }
-    int32_t r = madqp_chol_create(ctx, dim, &k->chol);
+    if (!r) r = k->mem.alloc(&k->d_ind_ineq, ns, who);
+    if (!r) r = k->mem.alloc(&k->d_slot, m, who);
+    if (!r) r = k->mem.alloc(&k->theta, m, who);
+    if (!r) r = k->mem.alloc(&k->t, m, who);
+    if (!r) r = k->mem.alloc(&k->u, m, who);
+    if (!r && mode == KKT_NORMAL) r = k->mem.alloc(&k->dn, n, who);
+    if (!r && mode == KKT_NORMAL) r = k->mem.alloc(&k->tn, n, who);
+    if (!r && mode == KKT_AUGMENTED) r = k->mem.alloc(&k->b, o.stored_order, who);
+    hipError_t e = hipSuccess;
+    if (!r && ns) e = hipMemcpy(k->d_ind_ineq, ind_ineq_host, ns * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (!r && e == hipSuccess && m) e = hipMemcpy(k->d_slot, slot.data(), m * sizeof(int64_t), hipMemcpyHostToDevice);
+    if (!r && e != hipSuccess)
+        r = madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_kkt_create(nx=%lld, m=%lld): %s", (long long)nx, (long long)m,
+                       hipGetErrorString(e));
+    if (!r) r = madqp_chol_create(ctx, o.stored_order, &k->chol);
     if (!r && mode == KKT_AUGMENTED) r = madqp_chol_set_signature(k->chol, k->np);
     if (r) {
         madqp_kkt_destroy(k);
@@ -528,32 +490,14 @@ extern "C" int32_t madqp_kkt_create(madqp_ctx* ctx, int64_t nx, int64_t m, int64
     if (!ctx) return MADQP_ERR_ARG;
     ARG_TRY(ctx, !H || ldh >= nx);
     ARG_TRY(ctx, m == 0 || nx == 0 || (A && lda >= nx));
-    return kkt_create_common(ctx, KKT_CONDENSED, nx, m, ns, ind_ineq_host, H, ldh, A, lda, nullptr, 0, out);
-}
-
-// The sparse object of either storage: kkt_create_common without dense A, then the six borrowed CSR pointers of A and A'.
-static int32_t kkt_create_sparse_common(madqp_ctx* ctx, int32_t mode, int64_t nx, int64_t m, int64_t ns,
-                                        const int64_t* ind_ineq_host, const double* H, int64_t ldh, const int64_t* a_ptr,
-                                        const int64_t* a_col, const double* a_val, const int64_t* at_ptr,
-                                        const int64_t* at_col, const double* at_val, madqp_kkt** out, bool packed) {
-    const int32_t r = kkt_create_common(ctx, mode == 1 ? KKT_NORMAL : mode == 2 ? KKT_AUGMENTED : KKT_CONDENSED, nx, m, ns,
-                                        ind_ineq_host, H, ldh, nullptr, 0, nullptr, 0, out, packed);
-    if (r) return r;
-    madqp_kkt* k = *out;
-    k->a_ptr = a_ptr;
-    k->a_col = a_col;
-    k->a_val = a_val;
-    k->at_ptr = at_ptr;
-    k->at_col = at_col;
-    k->at_val = at_val;
-    return MADQP_OK;
+    return kkt_create_common(ctx, KKT_CONDENSED, nx, m, ns, ind_ineq_host, H, ldh, A, lda, nullptr, 0, {}, {}, false, out);
 }
 
 // Sparse front end: A as CSR (a_*: m rows, column indices < nx, ascending within a row) and A' as CSR
 // (at_*: nx rows, indices < m), both device, int64, borrowed.  mode 0: condensed K = H + Sigma_x + A' Theta A
 // (H dense, NULL, diagonal through madqp_kkt_set_hdiag or CSR through madqp_kkt_set_hcsr), mode 1: the reference's
 // normal equations A Sigma^-1 A' (LP only, or H diagonal), mode 2: the augmented system [H + Sigma_x, A'; A, -D] (H as in
-// mode 0).
+// mode 0).  (The modes of the interface are the KKT_* values.)
 extern "C" int32_t madqp_kkt_create_sparse(madqp_ctx* ctx, int32_t mode, int64_t nx, int64_t m, int64_t ns,
                                            const int64_t* ind_ineq_host, const double* H, int64_t ldh,
                                            const int64_t* a_ptr, const int64_t* a_col, const double* a_val,
@@ -561,21 +505,21 @@ extern "C" int32_t madqp_kkt_create_sparse(madqp_ctx* ctx, int32_t mode, int64_t
                                            madqp_kkt** out) {
     if (!ctx) return MADQP_ERR_ARG;
     ARG_TRY(ctx, (mode >= 0 && mode <= 2) && a_ptr && at_ptr && (!H || ldh >= nx) && !(mode == 1 && H));
-    return kkt_create_sparse_common(ctx, mode, nx, m, ns, ind_ineq_host, H, ldh, a_ptr, a_col, a_val, at_ptr, at_col, at_val,
-                                    out, /*packed=*/false);
+    return kkt_create_common(ctx, mode, nx, m, ns, ind_ineq_host, H, ldh, nullptr, 0, nullptr, 0, {a_ptr, a_col, a_val},
+                             {at_ptr, at_col, at_val}, /*packed=*/false, out);
 }
 
 // The same object on PACKED band storage: no dense H (NULL, diagonal or CSR as above), mode 0 or 1, and no K at all until
 // madqp_kkt_set_bandwidth -- which such an object needs before anything is built, factorised or solved (MADQP_ERR_STATE
-// until then) -- allocates the band: npad (ld + 1) + 128 doubles instead of the ldk x dpad of the dense storage.
+// until then) -- allocates the band: npad (ld + 1) + 128 doubles instead of the ldk x ldk of the dense storage.
 extern "C" int32_t madqp_kkt_create_sparse_packed(madqp_ctx* ctx, int32_t mode, int64_t nx, int64_t m, int64_t ns,
                                                   const int64_t* ind_ineq_host, const int64_t* a_ptr, const int64_t* a_col,
                                                   const double* a_val, const int64_t* at_ptr, const int64_t* at_col,
                                                   const double* at_val, madqp_kkt** out) {
     if (!ctx) return MADQP_ERR_ARG;
     ARG_TRY(ctx, (mode == 0 || mode == 1) && a_ptr && at_ptr);
-    return kkt_create_sparse_common(ctx, mode, nx, m, ns, ind_ineq_host, nullptr, 0, a_ptr, a_col, a_val, at_ptr, at_col,
-                                    at_val, out, /*packed=*/true);
+    return kkt_create_common(ctx, mode, nx, m, ns, ind_ineq_host, nullptr, 0, nullptr, 0, nullptr, 0, {a_ptr, a_col, a_val},
+                             {at_ptr, at_col, at_val}, /*packed=*/true, out);
 }
 // a packed object has no storage before its bandwidth is set
 static int32_t kkt_storage_ready(madqp_kkt* k, const char* what) {
@@ -591,13 +535,10 @@ static int32_t kkt_storage_ready(madqp_kkt* k, const char* what) {
 extern "C" int32_t madqp_kkt_set_hdiag(madqp_kkt* k, const double* hdiag) {
     if (!k) return MADQP_ERR_ARG;
     madqp_ctx* ctx = k->ctx;
-    ARG_TRY(ctx, hdiag && !k->H && !k->h_ptr);
+    ARG_TRY(ctx, hdiag && !k->H && !k->h.ptr);
     ARG_TRY(ctx, k->bw < 0);  // the bandwidth was checked against the Hessian the object held
-    if (!k->sg) {
-        const size_t nb = (size_t)std::max<int64_t>(k->nx + k->ns, 1) * sizeof(double);
-        hipError_t e = hipMalloc(&k->sg, nb);
-        if (e != hipSuccess) return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_kkt_set_hdiag: %s", hipGetErrorString(e));
-    }
+    if (!k->sg)
+        if (int32_t r = k->mem.alloc(&k->sg, k->nx + k->ns, "madqp_kkt_set_hdiag")) return r;
     k->hdiag = hdiag;
     return MADQP_OK;
 }
@@ -610,21 +551,61 @@ extern "C" int32_t madqp_kkt_set_hcsr(madqp_kkt* k, const int64_t* h_ptr, const 
     if (!k) return MADQP_ERR_ARG;
     madqp_ctx* ctx = k->ctx;
     ARG_TRY(ctx, h_ptr && !k->H && !k->hdiag);
-    ARG_TRY(ctx, k->a_ptr && k->mode != KKT_NORMAL && !k->scaled);
+    ARG_TRY(ctx, k->a.ptr && k->mode != KKT_NORMAL && !k->scaled);
     ARG_TRY(ctx, k->bw < 0);  // the bandwidth was checked against the Hessian the object held
     int64_t nnz = 0;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(&nnz, h_ptr + k->nx, sizeof(int64_t), hipMemcpyDeviceToHost));
     ARG_TRY(ctx, nnz >= 0 && (nnz == 0 || (h_col && h_val)));
-    k->h_ptr = h_ptr;
-    k->h_col = h_col;
-    k->h_val = h_val;
+    k->h = {h_ptr, h_col, h_val};
     return MADQP_OK;
 }
 
+// The two positive definite forms are one weighted Gram matrix  K = base + diag(dvec) + V diag(w) V'  of order `order`
+// with inner dimension `inner`, roles swapped:
+//   condensed  V = A' (rows = variables),   w = Theta over the constraints,   dvec = Sigma_x (+ hdiag),  base = H
+//   normal     V = A  (rows = constraints), w = 1/Sigma over the variables,   dvec = Sigma_s^-1 on the inequality rows
+// v / vt: the rows of V and of V' of the sparse front end; dense: the operand of the dense one, row k of V' contiguous.
+struct KktGram {
+    int64_t order = 0, inner = 0;
+    Csr v, vt;
+    const double* dense = nullptr;
+    int64_t ld = 0;
+    const double *w = nullptr, *dvec = nullptr;
+    const double* base = nullptr;  // dense base, or
+    int64_t ldbase = 0;
+    Csr hbase;  // symmetric CSR base, or none
+};
+// st == nullptr: the pattern alone (madqp_kkt_set_bandwidth)
+static KktGram kkt_gram(const madqp_kkt* k, const madqp_state* st) {
+    KktGram g;
+    if (k->mode == KKT_NORMAL) {
+        g.order = k->m;
+        g.inner = k->nx;
+        g.v = k->a;
+        g.vt = k->at;
+        g.dense = k->At;
+        g.ld = k->ldat;
+        g.w = k->dn;
+        g.dvec = k->theta;
+    } else {
+        g.order = k->nx;
+        g.inner = k->m;
+        g.v = k->at;
+        g.vt = k->a;
+        g.dense = k->A;
+        g.ld = k->lda;
+        g.w = k->theta;
+        g.dvec = k->hdiag ? k->sg : st ? st->pr_diag : nullptr;  // diagonal of H + Sigma_x
+        g.base = k->H;
+        g.ldbase = k->ldh;
+        g.hbase = k->h;
+    }
+    return g;
+}
+
 // Band-limited assembly and factorisation (see include/madqp.h).  The pattern's bandwidth is read off the structures the
-// object holds, once, on the host: K = base + V diag(w) V' has an entry (i, j) only where a row k of V' holds both i and j,
-// so its half-bandwidth is max_k (last - first column of row k of V'), and max |col - row| over the CSR of H.
+// object holds, once, on the host (kkt_form.inc): the rows of V' of the Gram description, and the CSR of H.
 static int32_t csr_download(madqp_ctx* ctx, int64_t rows, const int64_t* d_ptr, const int64_t* d_col,
                             std::vector<int64_t>& ptr, std::vector<int64_t>& col) {
     ptr.assign((size_t)rows + 1, 0);
@@ -637,64 +618,46 @@ static int32_t csr_download(madqp_ctx* ctx, int64_t rows, const int64_t* d_ptr, 
 extern "C" int32_t madqp_kkt_set_bandwidth(madqp_kkt* k, int64_t bw) {
     if (!k) return MADQP_ERR_ARG;
     madqp_ctx* ctx = k->ctx;
-    ARG_TRY(ctx, k->a_ptr && !k->H && (k->mode == KKT_CONDENSED || k->mode == KKT_NORMAL) && !k->scaled);
-    const int64_t order = (k->mode == KKT_NORMAL) ? k->m : k->nx;
-    ARG_TRY(ctx, bw >= 0 && bw < order);
+    ARG_TRY(ctx, k->a.ptr && !k->H && (k->mode == KKT_CONDENSED || k->mode == KKT_NORMAL) && !k->scaled);
+    ARG_TRY(ctx, bw >= 0 && bw < kkt_orders(k->mode, k->nx, k->m).rule_order);
     if (k->packed && k->K)
         return madqp_fail(ctx, MADQP_ERR_STATE, "madqp_kkt_set_bandwidth: the packed storage of this object is laid out already");
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const KktGram g = kkt_gram(k, nullptr);
     std::vector<int64_t> ptr, col;
-    int64_t pattern = 0;
-    {  // rows of V': the CSR of A' (nx rows) for the normal equations (V = A), the CSR of A (m rows) for the condensed form
-        const bool normal = k->mode == KKT_NORMAL;
-        const int64_t rows = normal ? k->nx : k->m;
-        const int32_t r = csr_download(ctx, rows, normal ? k->at_ptr : k->a_ptr, normal ? k->at_col : k->a_col, ptr, col);
-        if (r) return r;
-        for (int64_t i = 0; i < rows; ++i)
-            if (ptr[i + 1] > ptr[i]) pattern = std::max(pattern, col[ptr[i + 1] - 1] - col[ptr[i]]);
-    }
-    if (k->h_ptr) {
-        const int32_t r = csr_download(ctx, k->nx, k->h_ptr, k->h_col, ptr, col);
-        if (r) return r;
-        for (int64_t i = 0; i < k->nx; ++i)
-            for (int64_t p = ptr[i]; p < ptr[i + 1]; ++p) pattern = std::max<int64_t>(pattern, std::llabs(col[p] - i));
+    int32_t r = csr_download(ctx, g.inner, g.vt.ptr, g.vt.col, ptr, col);
+    if (r) return r;
+    int64_t pattern = kkt_pattern_halfbandwidth(g.inner, ptr.data(), col.data());
+    if (g.hbase.ptr) {
+        if ((r = csr_download(ctx, g.order, g.hbase.ptr, g.hbase.col, ptr, col))) return r;
+        pattern = std::max(pattern, kkt_csr_halfbandwidth(g.order, ptr.data(), col.data()));
     }
     if (bw < pattern)
         return madqp_fail(ctx, MADQP_ERR_ARG, "madqp_kkt_set_bandwidth(%lld): the pattern's half-bandwidth is %lld",
                           (long long)bw, (long long)pattern);
-    const int32_t r = madqp_chol_set_bandwidth(k->chol, bw);
-    if (r) return r;
+    if ((r = madqp_chol_set_bandwidth(k->chol, bw))) return r;
     int64_t extent = 0;
-    const int32_t re = madqp_chol_band_extent(k->chol, &extent);
-    if (re) return re;
+    if ((r = madqp_chol_band_extent(k->chol, &extent))) return r;
     if (k->packed) {  // the band alone, zeroed once: every build rewrites the rows j .. j + extent of every column
         int64_t lay[2] = {0, 0};
-        int32_t rp = madqp_chol_packed_layout(k->chol, 0, lay);
-        if (!rp) rp = madqp_chol_set_packed(k->chol, 1);
-        if (rp) {
+        double* band = nullptr;
+        const size_t before = k->mem.owned.size();
+        r = madqp_chol_packed_layout(k->chol, 0, lay);
+        if (!r) r = madqp_chol_set_packed(k->chol, 1);
+        if (!r) r = k->mem.alloc(&band, lay[1], "madqp_kkt_set_bandwidth: packed storage", /*zero=*/true);
+        if (r) {  // nothing is committed: the object has no storage and takes another madqp_kkt_set_bandwidth
+            k->mem.release(before);
             (void)madqp_chol_set_bandwidth(k->chol, -1);
-            return rp;
+            return r;
         }
-        hipError_t e = hipMalloc(&k->K, (size_t)lay[1] * sizeof(double));
-        if (e == hipSuccess) e = hipMemset(k->K, 0, (size_t)lay[1] * sizeof(double));
-        if (e != hipSuccess) {
-            if (k->K) (void)hipFree(k->K);
-            k->K = nullptr;
-            (void)hipGetLastError();
-            (void)madqp_chol_set_bandwidth(k->chol, -1);
-            return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_kkt_set_bandwidth: %lld doubles of packed storage: %s",
-                              (long long)lay[1], hipGetErrorString(e));
-        }
+        k->K = band;
         k->ldk = lay[0];
         k->k_doubles = lay[1];
-        k->bw = bw;
-        k->band_extent = extent;
-        return MADQP_OK;
+    } else {
+        // K once: from now on nothing writes beyond the extent.  No reader of these zeros is left -- the sweeps of a solve stay
+        // inside the extent too (chol.hip, band form; MADQP_SWEEP_BAND=0 alone still streams the whole lower triangle)
+        HIP_TRY(ctx, hipMemsetAsync(k->K, 0, (size_t)k->k_doubles * sizeof(double), ctx->stream));
     }
-    // K once: from now on nothing writes beyond the extent.  No reader of these zeros is left -- the sweeps of a solve stay
-    // inside the extent too (chol.hip, band form; MADQP_SWEEP_BAND=0 alone still streams the whole lower triangle)
-    const int64_t dpad = std::max<int64_t>(128, (order + 127) / 128 * 128);
-    HIP_TRY(ctx, hipMemsetAsync(k->K, 0, ((size_t)k->ldk * dpad + 128) * sizeof(double), ctx->stream));
     k->bw = bw;
     k->band_extent = extent;
     return MADQP_OK;
@@ -708,7 +671,7 @@ extern "C" int32_t madqp_kkt_create_augmented(madqp_ctx* ctx, int64_t nx, int64_
     if (!ctx) return MADQP_ERR_ARG;
     ARG_TRY(ctx, !H || ldh >= nx);
     ARG_TRY(ctx, m == 0 || nx == 0 || (A && lda >= nx));
-    return kkt_create_common(ctx, KKT_AUGMENTED, nx, m, ns, ind_ineq_host, H, ldh, A, lda, nullptr, 0, out);
+    return kkt_create_common(ctx, KKT_AUGMENTED, nx, m, ns, ind_ineq_host, H, ldh, A, lda, nullptr, 0, {}, {}, false, out);
 }
 
 // K2.5: the augmented system symmetrically scaled (MadNLP's ScaledSparseKKTSystem; see the header comment).
@@ -719,16 +682,15 @@ extern "C" int32_t madqp_kkt_create_scaled_augmented(madqp_ctx* ctx, int64_t nx,
     if (r) return r;
     madqp_kkt* k = *out;
     const int64_t n = nx + ns;
-    const size_t nb = (size_t)std::max<int64_t>(n, 1) * sizeof(double);
-    hipError_t e = hipMalloc(&k->sfac, nb);
-    if (e == hipSuccess) e = hipMalloc(&k->sb, nb);
-    if (e != hipSuccess) {
+    r = k->mem.alloc(&k->sfac, n, "madqp_kkt_create_scaled_augmented");
+    if (!r) r = k->mem.alloc(&k->sb, n, "madqp_kkt_create_scaled_augmented");
+    if (r) {
         madqp_kkt_destroy(k);
         *out = nullptr;
-        return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_kkt_create_scaled_augmented: %s", hipGetErrorString(e));
+        return r;
     }
     k->scaled = 1;
-    if (n) KLAUNCH(k25_ones_kernel, n, n, k->sfac);
+    if (n) LAUNCH(k25_ones_kernel, n, n, k->sfac);
     return MADQP_OK;
 }
 
@@ -737,7 +699,7 @@ extern "C" int32_t madqp_kkt_create_normal(madqp_ctx* ctx, int64_t nx, int64_t m
                                            int64_t ldat, madqp_kkt** out) {
     if (!ctx) return MADQP_ERR_ARG;
     ARG_TRY(ctx, m == 0 || nx == 0 || (At && ldat >= m));
-    return kkt_create_common(ctx, KKT_NORMAL, nx, m, ns, ind_ineq_host, nullptr, 0, nullptr, 0, At, ldat, out);
+    return kkt_create_common(ctx, KKT_NORMAL, nx, m, ns, ind_ineq_host, nullptr, 0, nullptr, 0, At, ldat, {}, {}, false, out);
 }
 
 static int32_t check_kkt_state(madqp_kkt* k, const madqp_state* st) {
@@ -748,75 +710,55 @@ static int32_t check_kkt_state(madqp_kkt* k, const madqp_state* st) {
     return MADQP_OK;
 }
 
-int32_t madqp_syrk_assemble_ranges(madqp_ctx* ctx, int64_t n, int64_t kdim, const double* B, int64_t ldb,
-                                   const double* w, const double* base, int64_t ldbase,
-                                   const double* dvec, double* C, int64_t ldc, int64_t nranges,
-                                   const int64_t* ranges);  // gemm_f64.hip; ranges == nullptr: everything
+// [H + Sigma_x, A'; A, -D], lower triangle, identity over the padding rows nx .. np
+static int32_t kkt_build_augmented(madqp_kkt* k, const madqp_state* st) {
+    madqp_ctx* ctx = k->ctx;
+    const int64_t N = k->np + k->m;
+    if (N == 0) return MADQP_OK;
+    ProfScope ps(ctx, MADQP_PROF_SYRK);
+    const double* sf = k->scaled ? k->sfac : nullptr;
+    if (k->m) LAUNCH(aug_diag_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, st->du_diag, sf, k->theta);
+    const unsigned tiles = (unsigned)((N + 63) / 64);
+    hipLaunchKernelGGL(aug_fill_kernel, dim3(tiles, tiles), dim3(256), 0, ctx->stream, k->nx, k->np, k->m, k->H,
+                       k->ldh, k->hdiag, st->pr_diag, k->A, k->lda, k->theta, sf, k->K, k->ldk);
+    LAUNCH_CHECK(ctx);
+    if (k->a.ptr && k->m) {
+        hipLaunchKernelGGL(aug_scatter_kernel, dim3((unsigned)((k->m * 16 + 255) / 256)), dim3(256), 0, ctx->stream,
+                           k->m, k->np, k->a.ptr, k->a.col, k->a.val, sf, k->K, k->ldk);
+        LAUNCH_CHECK(ctx);
+    }
+    if (k->h.ptr && k->nx) {
+        hipLaunchKernelGGL(aug_scatter_h_kernel, dim3((unsigned)((k->nx * 16 + 255) / 256)), dim3(256), 0, ctx->stream,
+                           k->nx, k->h.ptr, k->h.col, k->h.val, st->pr_diag, k->K, k->ldk);
+        LAUNCH_CHECK(ctx);
+    }
+    return MADQP_OK;
+}
 
-static int32_t kkt_build_impl(madqp_kkt* k, const madqp_state* st, int64_t nranges, const int64_t* ranges) {
+extern "C" int32_t madqp_kkt_build(madqp_kkt* k, const madqp_state* st) {
     int32_t r = check_kkt_state(k, st);
     if (r) return r;
     if ((r = kkt_storage_ready(k, "madqp_kkt_build"))) return r;
     madqp_ctx* ctx = k->ctx;
-    if (k->mode == KKT_NORMAL) {
-        // S = A diag(D_x) A' + diag(D_s on inequality rows),  D = 1/Sigma; du_diag is NOT added
-        // (src/KKT/normalkkt.jl:166-180, src/utils.jl:266-298)
-        {
-            ProfScope ps(ctx, MADQP_PROF_VEC);
-            if (k->hdiag && st->n) KLAUNCH(sigma_h_kernel, st->n, st->n, k->nx, st->pr_diag, k->hdiag, k->sg);
-            if (st->n) KLAUNCH(recip_kernel, st->n, st->n, k->hdiag ? k->sg : st->pr_diag, k->dn);
-            if (k->m) KLAUNCH(slack_diag_kernel, k->m, k->m, k->nx, k->d_slot, k->dn, k->theta);
-        }
-        if (k->a_ptr) {  // V = A (rows = constraints), weights 1/Sigma over the variables
-            ARG_TRY(ctx, ranges == nullptr);
-            if (k->bw >= 0)
-                return madqp_sparse_gram_band(ctx, k->m, k->a_ptr, k->a_col, k->a_val, k->at_ptr, k->at_col, k->at_val, k->dn,
-                                              k->theta, nullptr, nullptr, nullptr, k->K, k->ldk, k->bw, k->band_extent);
-            return madqp_sparse_gram(ctx, k->m, k->a_ptr, k->a_col, k->a_val, k->at_ptr, k->at_col, k->at_val, k->dn,
-                                     nullptr, 0, k->theta, nullptr, nullptr, nullptr, k->K, k->ldk);
-        }
-        return madqp_syrk_assemble_ranges(ctx, k->m, k->nx, k->At, k->ldat, k->dn, nullptr, 0, k->theta,
-                                          k->K, k->ldk, nranges, ranges);
-    }
-    if (k->mode == KKT_AUGMENTED) {
-        ARG_TRY(ctx, ranges == nullptr);
-        const int64_t N = k->np + k->m;
-        if (N == 0) return MADQP_OK;
-        ProfScope ps(ctx, MADQP_PROF_SYRK);
-        const double* sf = k->scaled ? k->sfac : nullptr;
-        if (k->m) KLAUNCH(aug_diag_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, st->du_diag, sf, k->theta);
-        const unsigned tiles = (unsigned)((N + 63) / 64);
-        hipLaunchKernelGGL(aug_fill_kernel, dim3(tiles, tiles), dim3(256), 0, ctx->stream, k->nx, k->np, k->m, k->H,
-                           k->ldh, k->hdiag, st->pr_diag, k->A, k->lda, k->theta, sf, k->K, k->ldk);
-        LAUNCH_CHECK(ctx);
-        if (k->a_ptr && k->m) {
-            hipLaunchKernelGGL(aug_scatter_kernel, dim3((unsigned)((k->m * 16 + 255) / 256)), dim3(256), 0, ctx->stream,
-                               k->m, k->np, k->a_ptr, k->a_col, k->a_val, sf, k->K, k->ldk);
-            LAUNCH_CHECK(ctx);
-        }
-        if (k->h_ptr && k->nx) {
-            hipLaunchKernelGGL(aug_scatter_h_kernel, dim3((unsigned)((k->nx * 16 + 255) / 256)), dim3(256), 0, ctx->stream,
-                               k->nx, k->h_ptr, k->h_col, k->h_val, st->pr_diag, k->K, k->ldk);
-            LAUNCH_CHECK(ctx);
-        }
-        return MADQP_OK;
-    }
-    {
+    if (k->mode == KKT_AUGMENTED) return kkt_build_augmented(k, st);
+    {  // the vectors of the Gram description (kkt_gram)
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        if (k->m) KLAUNCH(theta_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, st->du_diag, k->theta);
-        if (k->hdiag && st->n) KLAUNCH(sigma_h_kernel, st->n, st->n, k->nx, st->pr_diag, k->hdiag, k->sg);
+        if (k->mode == KKT_NORMAL) {
+            // S = A diag(D_x) A' + diag(D_s on inequality rows),  D = 1/Sigma; du_diag is NOT added
+            // (src/KKT/normalkkt.jl:166-180, src/utils.jl:266-298)
+            if (k->hdiag && st->n) LAUNCH(sigma_h_kernel, st->n, st->n, k->nx, st->pr_diag, k->hdiag, k->sg);
+            if (st->n) LAUNCH(recip_kernel, st->n, st->n, k->hdiag ? k->sg : st->pr_diag, k->dn);
+            if (k->m) LAUNCH(slack_diag_kernel, k->m, k->m, k->nx, k->d_slot, k->dn, k->theta);
+        } else {
+            if (k->m) LAUNCH(theta_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, st->du_diag, k->theta);
+            if (k->hdiag && st->n) LAUNCH(sigma_h_kernel, st->n, st->n, k->nx, st->pr_diag, k->hdiag, k->sg);
+        }
     }
-    const double* dvec = k->hdiag ? k->sg : st->pr_diag;  // diagonal of H + Sigma_x
-    if (k->a_ptr) {  // V = A' (rows = variables), weights Theta over the constraints
-        ARG_TRY(ctx, ranges == nullptr);
-        if (k->bw >= 0)
-            return madqp_sparse_gram_band(ctx, k->nx, k->at_ptr, k->at_col, k->at_val, k->a_ptr, k->a_col, k->a_val, k->theta,
-                                          dvec, k->h_ptr, k->h_col, k->h_val, k->K, k->ldk, k->bw, k->band_extent);
-        return madqp_sparse_gram(ctx, k->nx, k->at_ptr, k->at_col, k->at_val, k->a_ptr, k->a_col, k->a_val, k->theta,
-                                 k->H, k->ldh, dvec, k->h_ptr, k->h_col, k->h_val, k->K, k->ldk);
-    }
-    return madqp_syrk_assemble_ranges(ctx, k->nx, k->m, k->A, k->lda, k->theta, k->H, k->ldh, dvec,
-                                      k->K, k->ldk, nranges, ranges);
+    const KktGram g = kkt_gram(k, st);
+    if (k->a.ptr && k->bw >= 0)
+        return madqp_sparse_gram_band(ctx, g.order, g.v, g.vt, g.w, g.dvec, g.hbase, k->K, k->ldk, k->bw, k->band_extent);
+    if (k->a.ptr) return madqp_sparse_gram(ctx, g.order, g.v, g.vt, g.w, g.base, g.ldbase, g.dvec, g.hbase, k->K, k->ldk);
+    return madqp_syrk_assemble_impl(ctx, g.order, g.inner, g.dense, g.ld, g.w, g.base, g.ldbase, g.dvec, k->K, k->ldk);
 }
 
 // set_aug_diagonal_reg!(kkt, solver), dispatched on the KKT type as the reference does (src/kernels.jl:128 for every
@@ -828,9 +770,9 @@ extern "C" int32_t madqp_kkt_set_aug_diagonal_reg(madqp_kkt* k, const madqp_stat
     if (!k->scaled) return madqp_set_aug_diagonal_reg(ctx, st, del_w, del_c);
     ARG_TRY(ctx, st->x && st->xl && st->xu && st->zl && st->zu);
     ProfScope ps(ctx, MADQP_PROF_VEC);
-    if (std::max(st->n, st->m) > 0) KLAUNCH(k25_fill_kernel, std::max(st->n, st->m), *st, del_w, del_c, k->sfac, k->sb);
-    if (std::max(st->nlb, st->nub) > 0) KLAUNCH(k25_bounds_kernel, std::max(st->nlb, st->nub), *st, k->sfac, k->sb);
-    if (st->n) KLAUNCH(k25_final_kernel, st->n, *st, del_w, k->sfac, k->sb);
+    if (std::max(st->n, st->m) > 0) LAUNCH(k25_fill_kernel, std::max(st->n, st->m), *st, del_w, del_c, k->sfac, k->sb);
+    if (std::max(st->nlb, st->nub) > 0) LAUNCH(k25_bounds_kernel, std::max(st->nlb, st->nub), *st, k->sfac, k->sb);
+    if (st->n) LAUNCH(k25_final_kernel, st->n, *st, del_w, k->sfac, k->sb);
     return MADQP_OK;
 }
 
@@ -845,21 +787,15 @@ extern "C" int32_t madqp_kkt_initialize(madqp_kkt* k, const madqp_state* st) {
         (r = madqp_fill(ctx, st->nub, 0.0, st->u_lower)) || (r = madqp_fill(ctx, st->nlb, 1.0, st->l_diag)) ||
         (r = madqp_fill(ctx, st->nub, 1.0, st->u_diag)))
         return r;
-    if (k->scaled && st->n) KLAUNCH(k25_ones_kernel, st->n, st->n, k->sfac);
+    if (k->scaled && st->n) LAUNCH(k25_ones_kernel, st->n, st->n, k->sfac);
     return MADQP_OK;
 }
 
-extern "C" int32_t madqp_kkt_build(madqp_kkt* k, const madqp_state* st) {
-    return kkt_build_impl(k, st, 0, nullptr);
-}
-
-// build_kkt! restricted to the block columns [ranges[2r], ranges[2r+1]) of the lower triangle
-// (multi-GPU path: a rank assembles the panels it owns).  Theta and the vectors the solves read
-// are computed in full, so solve!/mul! work on every rank.
+// the Cholesky handle and the order it was created with (kkt_form.inc: stored_order)
 extern "C" int32_t madqp_kkt_chol(madqp_kkt* k, madqp_chol** chol, int64_t* order) {
     if (!k || !chol) return MADQP_ERR_ARG;
     *chol = k->chol;
-    if (order) *order = (k->mode == KKT_NORMAL) ? k->m : (k->mode == KKT_AUGMENTED) ? k->np + k->m : k->nx;
+    if (order) *order = kkt_orders(k->mode, k->nx, k->m).stored_order;
     return MADQP_OK;
 }
 
@@ -889,28 +825,21 @@ static int32_t kkt_solve_once(madqp_kkt* k, const madqp_state* st, double* w);
 static bool kkt_fusable(const madqp_kkt* k) { return k->fuse && k->mode == KKT_CONDENSED && !k->scaled && k->m > 0; }
 static int32_t ensure_pos(madqp_kkt* k, const madqp_state* st) {
     madqp_ctx* ctx = k->ctx;
-    if (k->pos_lb && k->pos_key_lb == st->ind_lb && k->pos_key_ub == st->ind_ub && k->pos_nlb == st->nlb &&
+    if (k->pos_ok && k->pos_key_lb == st->ind_lb && k->pos_key_ub == st->ind_ub && k->pos_nlb == st->nlb &&
         k->pos_nub == st->nub && k->pos_n == st->n)
         return MADQP_OK;
-    if (k->pos_n != st->n || !k->pos_lb) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (k->pos_lb) (void)hipFree(k->pos_lb);
-        if (k->pos_ub) (void)hipFree(k->pos_ub);
-        if (k->rs) (void)hipFree(k->rs);
-        k->pos_lb = k->pos_ub = nullptr;
-        k->rs = nullptr;
-        const size_t nn = (size_t)std::max<int64_t>(st->n, 1);
-        if (hipMalloc(&k->pos_lb, nn * sizeof(int32_t)) != hipSuccess || hipMalloc(&k->pos_ub, nn * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc(&k->rs, (size_t)std::max<int64_t>(k->ns, 1) * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            return madqp_fail(ctx, MADQP_ERR_ALLOC, "inverse bound lists (%lld variables)", (long long)st->n);
-        }
-    }
+    k->pos_ok = false;
+    const char* who = "inverse bound lists";
+    int32_t r = k->mem.grow(&k->pos_lb, &k->pos_lb_cap, st->n, who);
+    if (!r) r = k->mem.grow(&k->pos_ub, &k->pos_ub_cap, st->n, who);
+    if (!r && !k->rs) r = k->mem.alloc(&k->rs, k->ns, who);
+    if (r) return r;
     ARG_TRY(ctx, st->n < (int64_t)1 << 31 && st->nlb < (int64_t)1 << 31 && st->nub < (int64_t)1 << 31);
     ProfScope ps(ctx, MADQP_PROF_VEC);
-    if (st->n) KLAUNCH(pos_fill_kernel, st->n, st->n, k->pos_lb, k->pos_ub);
-    if (st->nlb) KLAUNCH(pos_scatter_kernel, st->nlb, st->nlb, st->ind_lb, k->pos_lb);
-    if (st->nub) KLAUNCH(pos_scatter_kernel, st->nub, st->nub, st->ind_ub, k->pos_ub);
+    if (st->n) LAUNCH(pos_fill_kernel, st->n, st->n, k->pos_lb, k->pos_ub);
+    if (st->nlb) LAUNCH(pos_scatter_kernel, st->nlb, st->nlb, st->ind_lb, k->pos_lb);
+    if (st->nub) LAUNCH(pos_scatter_kernel, st->nub, st->nub, st->ind_ub, k->pos_ub);
+    k->pos_ok = true;
     k->pos_key_lb = st->ind_lb;
     k->pos_key_ub = st->ind_ub;
     k->pos_nlb = st->nlb;
@@ -938,14 +867,14 @@ int32_t madqp_kkt_solve_from(madqp_kkt* k, const madqp_state* st, const double* 
     const int64_t L = std::max(std::max(st->n, st->m), std::max(st->nlb, st->nub));
     {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        KLAUNCH(solve_pre_kernel, L, *st, p, w, k->pos_lb, k->pos_ub, k->nx, k->d_slot, k->theta, k->t, k->u, k->rs);
+        LAUNCH(solve_pre_kernel, L, *st, p, w, k->pos_lb, k->pos_ub, k->nx, k->d_slot, k->theta, k->t, k->u, k->rs);
     }
     if ((r = apply_At(k, 1.0, k->u, 1.0, w))) return r;  // rhs_x = r1_x + A' (theta t)
     if ((r = madqp_chol_solve(k->chol, w))) return r;
     if ((r = apply_A(k, 1.0, w, 0.0, k->u))) return r;
     {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        KLAUNCH(solve_post_kernel, L, *st, w, k->nx, k->d_slot, k->d_ind_ineq, k->theta, k->t, k->u, k->rs, p, pcopy);
+        LAUNCH(solve_post_kernel, L, *st, w, k->nx, k->d_slot, k->d_ind_ineq, k->theta, k->t, k->u, k->rs, p, pcopy);
     }
     k->u_is_A_of = w;  // dx is final since the sweeps: u = A dx (madqp_kkt_mul_solved)
     return MADQP_OK;
@@ -955,16 +884,16 @@ int32_t madqp_kkt_solve_from(madqp_kkt* k, const madqp_state* st, const double* 
 // MadIPM's solve_system! (src/linear_solver.jl:19-45) calls solve!(kkt, d) once and only LOOKS at the residual; the device
 // factorisation multiplies with explicit inverses of 16 x 16 sub-blocks where LAPACK substitutes scalar by scalar, which on
 // small ill-conditioned problems shows in the per-iteration traces and which one step removes.  The
-// Julia glue asks for the AUTO rule (steps = -1: one step while the factorised matrix has order <= 1024, none above -- the
-// rule madqp_jl_amd/options.py applies in the drivers of this repository, which refine in their own solve_system with the
-// residual they form anyway and leave this at 0).  Arithmetic: operation for operation the drivers' (bitwise equal results).
+// Julia glue asks for the AUTO rule (steps = -1: one step while the system has order <= 1024, none above -- rule_order of
+// kkt_form.inc, nx + m for the augmented form whatever its padding: the rule madqp_jl_amd/options.py applies in the drivers
+// of this repository, which refine in their own solve_system with the residual they form anyway and leave this at 0).
+// Arithmetic: operation for operation the drivers' (bitwise equal results).
 extern "C" int32_t madqp_kkt_set_refine(madqp_kkt* k, int32_t steps) {
     if (!k) return MADQP_ERR_ARG;
     ARG_TRY(k->ctx, steps >= -1 && steps <= 8);
     if (steps < 0) {
-        const int64_t order = k->mode == KKT_NORMAL ? k->m : k->mode == KKT_AUGMENTED ? k->nx + k->m : k->nx;
         static const int64_t auto_max = getenv("MADQP_REFINE_AUTO_MAX") ? atoll(getenv("MADQP_REFINE_AUTO_MAX")) : 1024;
-        steps = order <= auto_max ? 1 : 0;
+        steps = kkt_orders(k->mode, k->nx, k->m).rule_order <= auto_max ? 1 : 0;
     }
     k->refine = steps;
     return MADQP_OK;
@@ -978,99 +907,101 @@ extern "C" int32_t madqp_kkt_solve(madqp_kkt* k, const madqp_state* st, double* 
     if (k->refine <= 0) return kkt_solve_once(k, st, w);
     madqp_ctx* ctx = k->ctx;
     const int64_t len = st->n + st->m + st->nlb + st->nub;
-    if (len > k->rf_len) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (k->rf_p) (void)hipFree(k->rf_p);
-        if (k->rf_r) (void)hipFree(k->rf_r);
-        k->rf_p = k->rf_r = nullptr;
-        k->rf_len = 0;
-        if (hipMalloc(&k->rf_p, len * sizeof(double)) != hipSuccess || hipMalloc(&k->rf_r, len * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_kkt_solve: work vectors of the refinement steps (%lld doubles)", (long long)len);
-        }
-        k->rf_len = len;
-    }
-    if ((r = madqp_copy(ctx, len, w, k->rf_p))) return r;  // p
-    if ((r = kkt_solve_once(k, st, w))) return r;           // w = K^-1 p
+    const int64_t stride = (len + 31) / 32 * 32;  // both vectors 256-byte aligned, as two allocations were
+    if ((r = k->mem.grow(&k->rf, &k->rf_cap, 2 * stride, "madqp_kkt_solve: work vectors of the refinement steps"))) return r;
+    double *rf_p = k->rf, *rf_r = k->rf + stride;
+    if ((r = madqp_copy(ctx, len, w, rf_p))) return r;  // p
+    if ((r = kkt_solve_once(k, st, w))) return r;       // w = K^-1 p
     for (int32_t it = 0; it < k->refine; ++it) {
-        if ((r = madqp_copy(ctx, len, k->rf_p, k->rf_r))) return r;
-        if ((r = madqp_kkt_mul(k, st, k->rf_r, w, -1.0, 1.0))) return r;  // r = p - K w
-        if ((r = kkt_solve_once(k, st, k->rf_r))) return r;
-        if ((r = madqp_axpy(ctx, len, 1.0, k->rf_r, w))) return r;         // w += K^-1 r
+        if ((r = madqp_copy(ctx, len, rf_p, rf_r))) return r;
+        if ((r = madqp_kkt_mul(k, st, rf_r, w, -1.0, 1.0))) return r;  // r = p - K w
+        if ((r = kkt_solve_once(k, st, rf_r))) return r;
+        if ((r = madqp_axpy(ctx, len, 1.0, rf_r, w))) return r;  // w += K^-1 r
     }
     k->u_is_A_of = nullptr;  // (u belongs to the last correction, not to w)
     return MADQP_OK;
 }
 
-static int32_t kkt_solve_once(madqp_kkt* k, const madqp_state* st, double* w) {
+// The middle of a solve, one function per form: on entry w holds the reduced right-hand side [r1; r2; ..], on return dx
+// (with ds) in wx and dy in wy.
+static int32_t kkt_solve_normal(madqp_kkt* k, const madqp_state* st, double* wx, double* wy) {  // src/KKT/normalkkt.jl:185-201
     int32_t r = 0;
     madqp_ctx* ctx = k->ctx;
-    k->u_is_A_of = nullptr;
-    double* wx = w;
-    double* wy = w + st->n;
-    if (k->scaled) {  // r1 = p_x + p_zl / l_diag + p_zu / u_diag (signs of src/kernels.jl:157-158)
+    const double* sig = k->hdiag ? k->sg : st->pr_diag;  // H + Sigma
+    {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        if (st->nlb) KLAUNCH(k25_reduce_kernel, st->nlb, *st, w);
-        if (st->nub) KLAUNCH(k25_reduce_ub_kernel, st->nub, *st, w);
-    } else if ((r = madqp_reduce_rhs(ctx, st, w))) {
-        return r;
+        if (st->n) LAUNCH(div_kernel, st->n, st->n, wx, sig, k->tn);  // r1 = (H + Sigma)^-1 wx
     }
-    if (k->mode == KKT_NORMAL) {  // src/KKT/normalkkt.jl:185-201
-        {
-            ProfScope ps(ctx, MADQP_PROF_VEC);
-            if (st->n) KLAUNCH(div_kernel, st->n, st->n, wx, k->hdiag ? k->sg : st->pr_diag, k->tn);  // r1 = (H + Sigma)^-1 wx
-        }
-        if ((r = apply_A(k, 1.0, k->tn, 0.0, k->u))) return r;
-        if (k->m) {
-            ProfScope ps(ctx, MADQP_PROF_VEC);
-            KLAUNCH(normal_rhs_kernel, k->m, k->m, k->d_slot, k->u, k->tn + k->nx, wy, wy);  // A r1 - r2
-        }
-        if ((r = madqp_chol_solve(k->chol, wy))) return r;  // wy = dy
-        if ((r = apply_At(k, 1.0, wy, 0.0, k->tn))) return r;
-        {
-            ProfScope ps(ctx, MADQP_PROF_VEC);
-            if (k->ns) KLAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, wy, k->tn + k->nx, 1.0, 0.0);
-            if (st->n) KLAUNCH(normal_back_kernel, st->n, st->n, k->tn, k->hdiag ? k->sg : st->pr_diag, wx);
-        }
-        return madqp_finish_aug_solve(ctx, st, w);
+    if ((r = apply_A(k, 1.0, k->tn, 0.0, k->u))) return r;
+    if (k->m) {
+        ProfScope ps(ctx, MADQP_PROF_VEC);
+        LAUNCH(normal_rhs_kernel, k->m, k->m, k->d_slot, k->u, k->tn + k->nx, wy, wy);  // A r1 - r2
     }
-    if (k->mode == KKT_AUGMENTED) {
-        const int64_t N = k->np + k->m;
-        const double* sf = k->scaled ? k->sfac : nullptr;
-        if (N) {
-            ProfScope ps(ctx, MADQP_PROF_VEC);
-            KLAUNCH(aug_rhs_kernel, N, k->nx, k->np, k->m, k->d_slot, st->pr_diag, sf, wx, wy, k->b);
-        }
-        if ((r = madqp_chol_solve(k->chol, k->b))) return r;
-        if (k->nx + k->m) {
-            ProfScope ps(ctx, MADQP_PROF_VEC);
-            KLAUNCH(aug_back_kernel, k->nx + k->m, k->nx, k->np, k->m, k->d_slot, st->pr_diag, sf, k->b, wx, wy);
-        }
-        if (k->scaled) {
-            ProfScope ps(ctx, MADQP_PROF_VEC);
-            if (std::max(st->nlb, st->nub) > 0) KLAUNCH(k25_finish_kernel, std::max(st->nlb, st->nub), *st, w);
-            return MADQP_OK;
-        }
-        return madqp_finish_aug_solve(ctx, st, w);
+    if ((r = madqp_chol_solve(k->chol, wy))) return r;  // wy = dy
+    if ((r = apply_At(k, 1.0, wy, 0.0, k->tn))) return r;
+    ProfScope ps(ctx, MADQP_PROF_VEC);
+    if (k->ns) LAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, wy, k->tn + k->nx, 1.0, 0.0);
+    if (st->n) LAUNCH(normal_back_kernel, st->n, st->n, k->tn, sig, wx);
+    return MADQP_OK;
+}
+static int32_t kkt_solve_augmented(madqp_kkt* k, const madqp_state* st, double* wx, double* wy) {
+    int32_t r = 0;
+    madqp_ctx* ctx = k->ctx;
+    const int64_t N = k->np + k->m;
+    const double* sf = k->scaled ? k->sfac : nullptr;
+    if (N) {
+        ProfScope ps(ctx, MADQP_PROF_VEC);
+        LAUNCH(aug_rhs_kernel, N, k->nx, k->np, k->m, k->d_slot, st->pr_diag, sf, wx, wy, k->b);
     }
+    if ((r = madqp_chol_solve(k->chol, k->b))) return r;
+    if (k->nx + k->m) {
+        ProfScope ps(ctx, MADQP_PROF_VEC);
+        LAUNCH(aug_back_kernel, k->nx + k->m, k->nx, k->np, k->m, k->d_slot, st->pr_diag, sf, k->b, wx, wy);
+    }
+    return MADQP_OK;
+}
+static int32_t kkt_solve_condensed(madqp_kkt* k, const madqp_state* st, double* wx, double* wy) {
+    int32_t r = 0;
+    madqp_ctx* ctx = k->ctx;
     if (k->m) {
         {
             ProfScope ps(ctx, MADQP_PROF_VEC);
-            KLAUNCH(condense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, wx, wy,
-                    k->t, k->u);
+            LAUNCH(condense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, wx, wy, k->t, k->u);
         }
-        // rhs_x = r1_x + A' (theta t)
-        if ((r = apply_At(k, 1.0, k->u, 1.0, wx))) return r;
+        if ((r = apply_At(k, 1.0, k->u, 1.0, wx))) return r;  // rhs_x = r1_x + A' (theta t)
     }
     if ((r = madqp_chol_solve(k->chol, wx))) return r;
     if (k->m) {
         if ((r = apply_A(k, 1.0, wx, 0.0, k->u))) return r;
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        KLAUNCH(decondense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, k->t, k->u,
-                wx, wy);
+        LAUNCH(decondense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, k->t, k->u, wx, wy);
+    }
+    return MADQP_OK;
+}
+
+// reduce_rhs!, the form's own middle, finish_aug_solve! -- the K2.5 object with its sign-flipped first and last step
+static int32_t kkt_solve_once(madqp_kkt* k, const madqp_state* st, double* w) {
+    int32_t r = 0;
+    madqp_ctx* ctx = k->ctx;
+    k->u_is_A_of = nullptr;
+    if (k->scaled) {  // r1 = p_x + p_zl / l_diag + p_zu / u_diag (signs of src/kernels.jl:157-158)
+        ProfScope ps(ctx, MADQP_PROF_VEC);
+        if (st->nlb) LAUNCH(k25_reduce_kernel, st->nlb, *st, w);
+        if (st->nub) LAUNCH(k25_reduce_ub_kernel, st->nub, *st, w);
+    } else if ((r = madqp_reduce_rhs(ctx, st, w))) {
+        return r;
+    }
+    r = k->mode == KKT_NORMAL      ? kkt_solve_normal(k, st, w, w + st->n)
+        : k->mode == KKT_AUGMENTED ? kkt_solve_augmented(k, st, w, w + st->n)
+                                   : kkt_solve_condensed(k, st, w, w + st->n);
+    if (r) return r;
+    if (k->scaled) {
+        ProfScope ps(ctx, MADQP_PROF_VEC);
+        if (std::max(st->nlb, st->nub) > 0) LAUNCH(k25_finish_kernel, std::max(st->nlb, st->nub), *st, w);
+        return MADQP_OK;
     }
     if ((r = madqp_finish_aug_solve(ctx, st, w))) return r;
-    if (k->m) k->u_is_A_of = w;  // dx is final since the sweeps: u = A dx (madqp_kkt_mul_solved)
+    if (k->mode == KKT_CONDENSED && k->m) k->u_is_A_of = w;  // dx is final since the sweeps: u = A dx (madqp_kkt_mul_solved)
     return MADQP_OK;
 }
 
@@ -1082,7 +1013,7 @@ extern "C" int32_t madqp_kkt_jtprod(madqp_kkt* k, double* out, const double* y) 
     if ((r = apply_At(k, 1.0, y, 0.0, out))) return r;
     if (k->ns) {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        KLAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, y, out + k->nx, 1.0, 0.0);
+        LAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, y, out + k->nx, 1.0, 0.0);
     }
     return MADQP_OK;
 }
@@ -1108,38 +1039,30 @@ static int32_t kkt_mul_impl(madqp_kkt* k, const madqp_state* st, double* w, cons
     k->u_is_A_of = nullptr;
     // wx = alpha A_full' vy + beta wx  (+ alpha H vx)
     if ((r = apply_At(k, alpha, v + n, beta, w))) return r;
-    if (k->H && nx)  // H is symmetric: its lower triangle is enough (gemv.hip: madqp_symv_lower)
-        if ((r = madqp_symv_lower(ctx, nx, alpha, k->H, k->ldh, v, 1.0, w, MADQP_PROF_GEMV)))
-            return r;
-    if (k->hdiag && nx) {
-        ProfScope ps(ctx, MADQP_PROF_VEC);
-        KLAUNCH(hdiag_axpy_kernel, nx, nx, alpha, k->hdiag, v, w);
-    }
-    if (k->h_ptr && nx)  // both triangles are stored: one row-wise mat-vec, fixed order
-        if ((r = madqp_spmv_csr(ctx, nx, k->h_ptr, k->h_col, k->h_val, alpha, v, 1.0, w, MADQP_PROF_GEMV))) return r;
+    if ((r = apply_H(k, alpha, v, 1.0, w))) return r;
     if (kkt_fusable(k)) {  // the five per-variable passes that follow, in one (resid_tail_kernel)
         if (!have_Av && (r = apply_A(k, 1.0, v, 0.0, k->u))) return r;
         if ((r = ensure_pos(k, st))) return r;
         const int64_t L = std::max(std::max(st->n, st->m), std::max(st->nlb, st->nub));
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        KLAUNCH(resid_tail_kernel, L, *st, w, v, alpha, beta, nx, k->d_slot, k->d_ind_ineq, k->u, k->pos_lb, k->pos_ub);
+        LAUNCH(resid_tail_kernel, L, *st, w, v, alpha, beta, nx, k->d_slot, k->d_ind_ineq, k->u, k->pos_lb, k->pos_ub);
         return MADQP_OK;
     }
     if (k->ns) {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        KLAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, v + n, w + nx, alpha, beta);
+        LAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, v + n, w + nx, alpha, beta);
     }
     // wy = alpha A_full vx + beta wy
     if (k->m) {
         if (!have_Av && (r = apply_A(k, 1.0, v, 0.0, k->u))) return r;
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        KLAUNCH(mul_rows_kernel, k->m, k->m, k->d_slot, k->u, v + nx, w + n, alpha, beta);
+        LAUNCH(mul_rows_kernel, k->m, k->m, k->d_slot, k->u, v + nx, w + n, alpha, beta);
     }
     if (k->scaled) {  // mul!(w, ::ScaledSparseKKTSystem, v): zl dx + l_diag dzl, zu dx - u_diag dzu
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        if (std::max(st->n, st->m) > 0) KLAUNCH(k25_kktmul_diag_kernel, std::max(st->n, st->m), *st, w, v, alpha);
-        if (st->nlb) KLAUNCH(k25_kktmul_lb_kernel, st->nlb, *st, w, v, alpha, beta);
-        if (st->nub) KLAUNCH(k25_kktmul_ub_kernel, st->nub, *st, w, v, alpha, beta);
+        if (std::max(st->n, st->m) > 0) LAUNCH(k25_kktmul_diag_kernel, std::max(st->n, st->m), *st, w, v, alpha);
+        if (st->nlb) LAUNCH(k25_kktmul_lb_kernel, st->nlb, *st, w, v, alpha, beta);
+        if (st->nub) LAUNCH(k25_kktmul_ub_kernel, st->nub, *st, w, v, alpha, beta);
         return MADQP_OK;
     }
     return madqp_kktmul(ctx, st, w, v, alpha, beta);
@@ -1152,21 +1075,13 @@ int32_t madqp_q_kkt_eval(madqp_kkt* k, const madqp_state* st, const double* q, c
     madqp_ctx* ctx = k->ctx;
     ARG_TRY(ctx, (k->nx == 0 || q) && (k->m == 0 || rhs));
     const int64_t nx = k->nx, n = st->n;
-    if (k->H && nx)
-        if ((r = madqp_symv_lower(ctx, nx, 1.0, k->H, k->ldh, st->x, 0.0, st->f, MADQP_PROF_GEMV)))
-            return r;
-    if (k->hdiag && nx) {
-        ProfScope ps(ctx, MADQP_PROF_VEC);
-        KLAUNCH(hdiag_mul_kernel, nx, nx, k->hdiag, st->x, st->f);
-    }
-    if (k->h_ptr && nx)
-        if ((r = madqp_spmv_csr(ctx, nx, k->h_ptr, k->h_col, k->h_val, 1.0, st->x, 0.0, st->f, MADQP_PROF_GEMV))) return r;
+    if ((r = apply_H(k, 1.0, st->x, 0.0, st->f))) return r;
     if (n) {
         const int nb = grid_for(n);
         {
             ProfScope ps(ctx, MADQP_PROF_VEC);
-            hipLaunchKernelGGL(eval_grad_kernel, dim3(nb), dim3(TPB), 0, ctx->stream, n, nx,
-                               ((k->H || k->hdiag || k->h_ptr) && nx) ? 1 : 0, q, st->x, st->f, ctx->d_part);
+            hipLaunchKernelGGL(eval_grad_kernel, dim3(nb), dim3(TPB), 0, ctx->stream, n, nx, kkt_has_H(k) ? 1 : 0, q, st->x,
+                               st->f, ctx->d_part);
             LAUNCH_CHECK(ctx);
             hipLaunchKernelGGL(sum2_final_kernel, dim3(1), dim3(TPB), 0, ctx->stream, ctx->d_part, nb,
                                ctx->d_res + slot0);
@@ -1178,7 +1093,7 @@ int32_t madqp_q_kkt_eval(madqp_kkt* k, const madqp_state* st, const double* q, c
     if (k->m) {
         if ((r = apply_A(k, 1.0, st->x, 0.0, st->c))) return r;
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        KLAUNCH(eval_cons_kernel, k->m, k->m, k->d_slot, st->x + nx, rhs, st->c);
+        LAUNCH(eval_cons_kernel, k->m, k->m, k->d_slot, st->x + nx, rhs, st->c);
     }
     return MADQP_OK;
 }

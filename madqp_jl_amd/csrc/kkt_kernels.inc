@@ -180,15 +180,16 @@ MQ_KERNEL sigma_h_kernel(int64_t n, int64_t nx, const double* __restrict__ pr_di
                          const double* __restrict__ hd, double* __restrict__ sg) {
     GRID_STRIDE(i, n) sg[i] = (i < nx) ? pr_diag[i] + hd[i] : pr_diag[i];
 }
-// w += alpha * hd .* v   (the H v term of mul!)
-MQ_KERNEL hdiag_axpy_kernel(int64_t nx, double alpha, const double* __restrict__ hd,
-                            const double* __restrict__ v, double* __restrict__ w) {
-    GRID_STRIDE(i, nx) w[i] += alpha * hd[i] * v[i];
-}
-// f = hd .* x   (H x of the callbacks)
-MQ_KERNEL hdiag_mul_kernel(int64_t nx, const double* __restrict__ hd, const double* __restrict__ x,
-                           double* __restrict__ f) {
-    GRID_STRIDE(i, nx) f[i] = hd[i] * x[i];
+// y = alpha * hd .* x + beta * y for beta = 0 (y is not read: H x of the callbacks, where alpha = 1 leaves hd .* x exactly)
+// or beta = 1 (the H v term of mul!)
+MQ_KERNEL hdiag_mul_kernel(int64_t nx, double alpha, const double* __restrict__ hd, const double* __restrict__ x,
+                           double beta, double* __restrict__ y) {
+    GRID_STRIDE(i, nx) {
+        if (beta == 0.0)
+            y[i] = alpha * hd[i] * x[i];
+        else
+            y[i] += alpha * hd[i] * x[i];
+    }
 }
 
 // ---- augmented (K2) mode, kkt.hip ----

@@ -134,41 +134,37 @@ __global__ __launch_bounds__(256) void sparse_gram_band_kernel(int64_t n, const 
 }
 }  // namespace
 
-int32_t madqp_sparse_gram_band(madqp_ctx* ctx, int64_t n, const int64_t* rowptr, const int64_t* col, const double* val,
-                               const int64_t* t_ptr, const int64_t* t_col, const double* t_val, const double* w,
-                               const double* dvec, const int64_t* b_ptr, const int64_t* b_col, const double* b_val,
-                               double* C, int64_t ldc, int64_t bw, int64_t extent) {
+// The host wrappers unpack the CSR views: the kernels keep their parameter lists.
+int32_t madqp_sparse_gram_band(madqp_ctx* ctx, int64_t n, const Csr& v, const Csr& vt, const double* w, const double* dvec,
+                               const Csr& b, double* C, int64_t ldc, int64_t bw, int64_t extent) {
     if (n == 0) return MADQP_OK;
     // (ldc >= n: dense storage; packed band storage has ldc >= extent alone -- the kernel writes the rows j .. j + extent of column j)
-    ARG_TRY(ctx, rowptr && t_ptr && w && C && ldc >= std::max<int64_t>(extent, 1) && bw >= 0 && bw <= extent && extent < n);
+    ARG_TRY(ctx, v.ptr && vt.ptr && w && C && ldc >= std::max<int64_t>(extent, 1) && bw >= 0 && bw <= extent && extent < n);
     ProfScope ps(ctx, MADQP_PROF_SYRK);
-    hipLaunchKernelGGL(sparse_gram_band_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, n, rowptr, col, val, t_ptr,
-                       t_col, t_val, w, dvec, b_ptr, b_col, b_val, C, ldc, bw, extent);
+    hipLaunchKernelGGL(sparse_gram_band_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, n, v.ptr, v.col, v.val, vt.ptr,
+                       vt.col, vt.val, w, dvec, b.ptr, b.col, b.val, C, ldc, bw, extent);
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }
 
-int32_t madqp_spmv_csr(madqp_ctx* ctx, int64_t rows, const int64_t* rowptr, const int64_t* col, const double* val,
-                       double alpha, const double* x, double beta, double* y, int prof_cls) {
+int32_t madqp_spmv_csr(madqp_ctx* ctx, int64_t rows, const Csr& a, double alpha, const double* x, double beta, double* y,
+                       int prof_cls) {
     if (rows == 0) return MADQP_OK;
-    ARG_TRY(ctx, rowptr && x && y);
+    ARG_TRY(ctx, a.ptr && x && y);
     ProfScope ps(ctx, prof_cls);
     const unsigned grid = (unsigned)((rows * 16 + 255) / 256);
-    hipLaunchKernelGGL(spmv_csr_kernel, dim3(grid), dim3(256), 0, ctx->stream, rows, rowptr, col, val, alpha, x,
-                       beta, y);
+    hipLaunchKernelGGL(spmv_csr_kernel, dim3(grid), dim3(256), 0, ctx->stream, rows, a.ptr, a.col, a.val, alpha, x, beta, y);
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }
 
-int32_t madqp_sparse_gram(madqp_ctx* ctx, int64_t n, const int64_t* rowptr, const int64_t* col, const double* val,
-                          const int64_t* t_ptr, const int64_t* t_col, const double* t_val, const double* w,
-                          const double* base, int64_t ldbase, const double* dvec, const int64_t* b_ptr,
-                          const int64_t* b_col, const double* b_val, double* C, int64_t ldc) {
+int32_t madqp_sparse_gram(madqp_ctx* ctx, int64_t n, const Csr& v, const Csr& vt, const double* w, const double* base,
+                          int64_t ldbase, const double* dvec, const Csr& b, double* C, int64_t ldc) {
     if (n == 0) return MADQP_OK;
-    ARG_TRY(ctx, rowptr && t_ptr && w && C && ldc >= n && (!base || ldbase >= n) && !(base && b_ptr));
+    ARG_TRY(ctx, v.ptr && vt.ptr && w && C && ldc >= n && (!base || ldbase >= n) && !(base && b.ptr));
     ProfScope ps(ctx, MADQP_PROF_SYRK);
-    hipLaunchKernelGGL(sparse_gram_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, n, rowptr, col, val, t_ptr,
-                       t_col, t_val, w, base, ldbase, dvec, b_ptr, b_col, b_val, C, ldc);
+    hipLaunchKernelGGL(sparse_gram_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, n, v.ptr, v.col, v.val, vt.ptr,
+                       vt.col, vt.val, w, base, ldbase, dvec, b.ptr, b.col, b.val, C, ldc);
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }

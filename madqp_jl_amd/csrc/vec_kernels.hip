@@ -7,23 +7,10 @@
 // Arithmetic is written in the reference's evaluation order and the library is compiled with
 // -ffp-contract=off, so elementwise results are bit-identical to the numpy oracle; max / min /
 // arg-min reductions are order independent, sums are compared to a tolerance.
-#include <algorithm>
-
-#include "common.h"
-
-#define MADQP_MAX_BLOCKS 1024
-#define TPB 256
+#include "grid_kernels.h"
 
 namespace {
-#define MQ_KERNEL __global__ __launch_bounds__(TPB) void
-#define MQ_BLOCK blockIdx.x
-#define GRID_STRIDE(i, len) \
-    for (int64_t i = (int64_t)blockIdx.x * TPB + threadIdx.x; i < (len); i += (int64_t)gridDim.x * TPB)
 #include "vec_kernels.inc"
-
-inline int grid_for(int64_t len) {
-    return (int)std::max<int64_t>(1, std::min<int64_t>((len + TPB - 1) / TPB, MADQP_MAX_BLOCKS));
-}
 
 int32_t finalize(madqp_ctx* ctx, int nblocks, int nv, const int* ops, int slot0 = 0) {
     FinalOps f;
@@ -50,11 +37,6 @@ int32_t check_state(madqp_ctx* ctx, const madqp_state* st) {
         if (!ctx) return MADQP_ERR_ARG;       \
         int32_t r_ = check_state(ctx, st);    \
         if (r_) return r_;                    \
-    } while (0)
-#define LAUNCH(kern, len, ...)                                                                  \
-    do {                                                                                        \
-        hipLaunchKernelGGL(kern, dim3(grid_for(len)), dim3(TPB), 0, ctx->stream, __VA_ARGS__);  \
-        LAUNCH_CHECK(ctx);                                                                      \
     } while (0)
 
 static inline int64_t max4(int64_t a, int64_t b, int64_t c, int64_t d) {
