@@ -321,6 +321,34 @@ int32_t madqp_chol_sweep_info(madqp_chol* s, int64_t* out_host);
  * the stored factor like that call does.  madqp_chol_solve needs nothing: it uses the matrix and lda of the last factor. */
 int32_t madqp_chol_packed_layout(madqp_chol* s, int64_t ld_in, int64_t* out_host);
 int32_t madqp_chol_set_packed(madqp_chol* s, int32_t on);
+/* LAPACK's dpotrs with its nrhs: B (device, column-major n x nrhs, leading dimension ldb >= max(n, 1)) <- (L L')^-1 B in
+ * place, column by column what madqp_chol_solve computes -- under a signature npos < n (L diag(I, -I) L')^-1 B.  Rows
+ * n .. ldb - 1 of each column are neither read nor written.  nrhs == 0 or n == 0: nothing to do.  MADQP_ERR_ARG for
+ * nrhs < 0, ldb < max(n, 1) or a NULL B with work to do; MADQP_ERR_STATE where madqp_chol_solve returns it (before a
+ * factorisation, after madqp_chol_set_bandwidth / madqp_chol_set_packed forgot the factor).  Asynchronous on the context's
+ * stream, with one exception: the handle owns the workspace of the blocked path (O(n nrhs + 128 n) doubles, never of
+ * order n^2; madqp_chol_destroy frees it) and grows it at the first call that needs more -- that call synchronises the
+ * stream, as does the first product of a new shape (its tile table is uploaded once per context).
+ * Two paths.  nrhs < min_nrhs: the columns one after another through the sweeps of madqp_chol_solve, bitwise the looped
+ * result (nrhs == 1 IS madqp_chol_solve(s, B)).  From min_nrhs on: a two-sweep block substitution over the factor's
+ * 128-column blocks on the transposed block of right-hand sides -- per block and sweep one diagonal step (substitution over
+ * 16 x 16 sub-blocks, no product with a stored 128 x 128 inverse) and one update on the fp64 MFMA product kernels, all
+ * stream-ordered launches: no workgroup waits for another, the path has no spin limit and no fault word, no atomics in
+ * its sums (the same call on the same input gives the same bits).  Every block of L is read once per sweep for all
+ * columns.  A handle that keeps U = L' (the mid-size schedule) multiplies with it in the backward sweep; the others
+ * transpose one block row of L per step into the workspace.  Under a bandwidth the contract of the band sweeps holds: no
+ * entry with i - j > min(n - 1, 128 kb + 127), kb = (bw + 127) / 128, is read, so packed storage is served, with bitwise
+ * the results of dense storage.
+ * madqp_chol_set_solve_many_min: min_nrhs >= 2 (MADQP_ERR_ARG below); the default is the measured cut-over
+ * (profiles/solve_many.json).
+ * madqp_chol_solve_many_info: what a call with nrhs columns would run as, four values: out_host[0] the path (0 column by
+ * column, 1 blocked), out_host[1] the launches (stream operations) of one call, out_host[2] the doubles of workspace the
+ * handle holds now, out_host[3] the bytes of the factor one call moves, counted by the plan (csrc/solve_plan.inc): every
+ * block once per sweep, and for a handle without U the backward block rows three times (read, written to the strip, read
+ * by the product). */
+int32_t madqp_chol_solve_many(madqp_chol* s, double* B, int64_t ldb, int64_t nrhs);
+int32_t madqp_chol_set_solve_many_min(madqp_chol* s, int64_t min_nrhs);
+int32_t madqp_chol_solve_many_info(madqp_chol* s, int64_t nrhs, int64_t* out_host);
 
 /* y = alpha*op(A) x + beta*y ; A has `rows` rows of length `cols`, row r at A + r*lda.
  * trans=0: y(rows) = A x(cols);  trans=1: y(cols) = A' x(rows).
@@ -474,6 +502,16 @@ int32_t madqp_kkt_solve(madqp_kkt* kkt, const madqp_state* st, double* w);
  * refine_steps, same rule) and leave this at 0.  Why: DESIGN.md section 4.2 (16 x 16 inverse products against LAPACK's scalar
  * substitution on small ill-conditioned problems). */
 int32_t madqp_kkt_set_refine(madqp_kkt* kkt, int32_t steps);
+/* MadNLP.solve!(kkt, w) for nrhs vectors with one factor: vector c is the UnreducedKKTVector.values at W + c ldw
+ * (ldw >= n + m + nlb + nub), each solved in place as madqp_kkt_solve solves one; nrhs == 1 IS madqp_kkt_solve(kkt, st, W),
+ * nrhs == 0 does nothing; MADQP_ERR_ARG for nrhs < 0, a short ldw or a NULL W with work to do.  Every KKT form: the passes
+ * before the factor solve run per column (the kernels of the one-vector solve on offset pointers), then ONE
+ * madqp_chol_solve_many of all columns, then the passes after it per column.  The products with A / A' stay mat-vecs per
+ * column: with a dense A they are the larger part of a many-column solve (their GEMM form is not in this library yet).
+ * madqp_kkt_set_refine is honoured (residuals per column, corrections through one solve of the residual block).  The work
+ * vectors of the columns belong to the object and grow at the first call that needs more (that call synchronises).
+ * Afterwards madqp_kkt_mul_solved has nothing to reuse: it is madqp_kkt_mul. */
+int32_t madqp_kkt_solve_many(madqp_kkt* kkt, const madqp_state* st, double* W, int64_t ldw, int64_t nrhs);
 /* MadNLP.mul!(w, kkt, v, alpha, beta) (src/KKT/normalkkt.jl:207-219), with H for a QP */
 int32_t madqp_kkt_mul(madqp_kkt* kkt, const madqp_state* st, double* w, const double* v,
                       double alpha, double beta);

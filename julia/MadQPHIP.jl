@@ -128,6 +128,14 @@ function MadNLP.solve!(s::HIPCholeskySolver, rhs::AbstractVector)
     return rhs
 end
 
+# LAPACK's dpotrs with its nrhs: every column of the device matrix X (column-major, stride size(X, 1) >= the order), in
+# place, with one factor (madqp_chol_solve_many: block substitution from its cut-over on, the loop over columns below it)
+function MadNLP.solve!(s::HIPCholeskySolver, X::AbstractMatrix)
+    check(s.aug_com.ctx, ccall((:madqp_chol_solve_many, libmadqp), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64),
+                               s.chol, dptr(X), size(X, 1), size(X, 2)))
+    return X
+end
+
 # --------------------------------------------------------------------------- KKT system
 # F = :condensed  K = H + Sigma_x + A' Theta A            (madqp_kkt_create)
 #     :augmented  [H + Sigma_x, A'; A, -D], L diag(I,-I) L' (madqp_kkt_create_augmented; MadNLP's default K2 form)
@@ -294,6 +302,14 @@ function MadNLP.solve!(kkt::HIPKKTSystem, w::MadNLP.AbstractKKTVector)   # :182-
     check(kkt.ctx, ccall((:madqp_kkt_solve, libmadqp), Int32, (Ptr{Cvoid}, Ref{CState}, Ptr{Float64}),
                          kkt.handle, kkt.cstate, dptr(MadNLP.full(w))))
     return w
+end
+
+# solve! for a block of right-hand sides: column c of the device matrix W (stride size(W, 1) >= length(full(w))) is the
+# `full` of an UnreducedKKTVector, each solved in place with one factor (madqp_kkt_solve_many; madqp_kkt_set_refine holds)
+function MadNLP.solve!(kkt::HIPKKTSystem, W::AbstractMatrix)
+    check(kkt.ctx, ccall((:madqp_kkt_solve_many, libmadqp), Int32, (Ptr{Cvoid}, Ref{CState}, Ptr{Float64}, Int64, Int64),
+                         kkt.handle, kkt.cstate, dptr(W), size(W, 1), size(W, 2)))
+    return W
 end
 
 function mul!(w::MadNLP.AbstractKKTVector{T}, kkt::HIPKKTSystem, v::MadNLP.AbstractKKTVector,

@@ -214,6 +214,14 @@ function MadNLP.solve!(kkt::HIPSparseKKTSystem, w::MadNLP.AbstractKKTVector)   #
     return w
 end
 
+# a block of right-hand sides, as MadQPHIP's method for its KKT type (the linear solver's matrix method is inherited:
+# this type uses MadQPHIP.HIPCholeskySolver): column c of W is the `full` of an UnreducedKKTVector
+function MadNLP.solve!(kkt::HIPSparseKKTSystem, W::AbstractMatrix)
+    check(kkt.ctx, ccall((:madqp_kkt_solve_many, libmadqp), Int32, (Ptr{Cvoid}, Ref{CState}, Ptr{Float64}, Int64, Int64),
+                         kkt.handle, kkt.cstate, dptr(W), size(W, 1), size(W, 2)))
+    return W
+end
+
 function mul!(w::MadNLP.AbstractKKTVector{T}, kkt::HIPSparseKKTSystem, v::MadNLP.AbstractKKTVector,
               alpha = one(T), beta = zero(T)) where {T}           # :207-219
     check(kkt.ctx, ccall((:madqp_kkt_mul, libmadqp), Int32,

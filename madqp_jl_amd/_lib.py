@@ -142,6 +142,9 @@ _SIGNATURES = {
     "madqp_chol_set_packed": [vp, i32],
     "madqp_chol_factor": [vp, vp, i64, pi32],
     "madqp_chol_solve": [vp, vp],
+    "madqp_chol_solve_many": [vp, vp, i64, i64],
+    "madqp_chol_set_solve_many_min": [vp, i64],
+    "madqp_chol_solve_many_info": [vp, i64, pi64],
     "madqp_gemv": [vp, i32, i64, i64, f64, vp, i64, vp, f64, vp],
     "madqp_set_aug_diagonal_reg": [vp, pstate, f64, f64],
     "madqp_set_initial_primal_rhs": [vp, pstate],
@@ -180,6 +183,7 @@ _SIGNATURES = {
     "madqp_kkt_build": [vp, pstate],
     "madqp_kkt_factorize": [vp, pi32],
     "madqp_kkt_solve": [vp, pstate, vp],
+    "madqp_kkt_solve_many": [vp, pstate, vp, i64, i64],
     "madqp_kkt_set_refine": [vp, C.c_int32],
     "madqp_kkt_mul": [vp, pstate, vp, vp, f64, f64],
     "madqp_kkt_mul_solved": [vp, pstate, vp, vp, f64, f64],

@@ -194,6 +194,25 @@ class HipBackend:
     def chol_solve(self, h, rhs):
         self._ck(self.lib.madqp_chol_solve(h, ptr(rhs)))
 
+    def chol_solve_many(self, h, B, ldb=None):
+        """``B`` (``(nrhs, ldb)``, row c = right-hand side c: LAPACK's column-major n x nrhs operand of leading dimension
+        ``ldb``) <- K^-1 B in place with one factor; ``ldb`` defaults to the row stride of ``B``."""
+        nrhs = B.shape[0]
+        if ldb is None:
+            ldb = B.stride(0) if nrhs > 1 else max(B.shape[1], 1)
+        self._ck(self.lib.madqp_chol_solve_many(h, ptr(B), int(ldb), nrhs))
+
+    def chol_set_solve_many_min(self, h, min_nrhs):
+        """``chol_solve_many`` takes its blocked path from ``min_nrhs`` (>= 2) right-hand sides on."""
+        self._ck(self.lib.madqp_chol_set_solve_many_min(h, int(min_nrhs)))
+
+    def chol_solve_many_info(self, h, nrhs):
+        """``(path, launches, workspace_doubles, factor_bytes)`` of a ``chol_solve_many`` with ``nrhs`` right-hand sides:
+        path 0 column by column, 1 blocked."""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.madqp_chol_solve_many_info(h, int(nrhs), out))
+        return tuple(out)
+
     def gemv(self, trans, rows, cols, alpha, A, lda, x, beta, y):
         self._ck(self.lib.madqp_gemv(self.ctx, trans, rows, cols, alpha, ptr(A), lda, ptr(x), beta, ptr(y)))
 
@@ -415,6 +434,11 @@ class HipBackend:
 
     def kkt_solve(self, h, st, w):
         self._ck(self.lib.madqp_kkt_solve(h, C.byref(st.cstruct), ptr(w)))
+
+    def kkt_solve_many(self, h, st, W):
+        """Row c of ``W`` (``(nrhs, ldw)``) is an UnreducedKKTVector.values, each solved in place with one factor."""
+        nrhs = W.shape[0]
+        self._ck(self.lib.madqp_kkt_solve_many(h, C.byref(st.cstruct), ptr(W), W.stride(0) if nrhs > 1 else W.shape[1], nrhs))
 
     def kkt_set_refine(self, h, steps):
         self._ck(self.lib.madqp_kkt_set_refine(h, int(steps)))

@@ -33,12 +33,20 @@
 #include "common.h"
 #include "band_plan.inc"
 #include "mid_plan.inc"
+#include "solve_plan.inc"
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
 namespace {
 constexpr int NB = 128;    // diagonal block
 constexpr int NBO = 1024;  // outer panel
+static_assert(SOLVE_NB == NB, "solve_plan.inc plans in this file's blocks");
+// madqp_chol_solve_many takes the blocked path from this many right-hand sides on (madqp_chol_set_solve_many_min changes it
+// per handle).  Measured (tools/bench_solve_many.py -> profiles/solve_many.json, "min_nrhs"): the smallest of 2, 4, .., 128 from
+// which on the blocked median beats the looped one by more than the spread at n = 5 000, 12 800, 50 000 and on the packed band
+// of order 90 000 alike.  The blocked path costs the same up to 128 columns -- its launches, not its bytes, are its time -- and
+// a one-vector solve a sixteenth to a twentieth of that, so the two cross between 16 and 32 in every case.
+constexpr int64_t SOLVE_MANY_MIN_DEFAULT = 32;
 #ifndef P2_LDS_LD
 #define P2_LDS_LD (NB + 1)
 #endif
@@ -1371,6 +1379,7 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
     s->ctx = ctx;
     s->n = n;
     s->npos = n;
+    s->many_min = SOLVE_MANY_MIN_DEFAULT;
     (void)s->band.clear(n);  // (nothing to free yet)
     const int64_t nblk = std::max<int64_t>(1, (n + NB - 1) / NB);
     hipError_t e = hipMalloc(&s->winv, nblk * WBLK * sizeof(double));
@@ -1427,6 +1436,7 @@ extern "C" int32_t madqp_chol_destroy(madqp_chol* s) {
     if (s->d_mid_plan) (void)hipFree(s->d_mid_plan);
     if (s->upper) (void)hipFree(s->upper);
     if (s->utmp) (void)hipFree(s->utmp);
+    if (s->many_ws) (void)hipFree(s->many_ws);
     delete[] s->mid_units;
     delete s;
     return MADQP_OK;
@@ -2009,5 +2019,242 @@ extern "C" int32_t madqp_chol_solve(madqp_chol* s, double* rhs) {
         launch_sweep(true, grid, ctx->stream, A, lda, s->winv, s->tmp, rhs, n, s->d_info, ctx->d_res + MADQP_FAULT_SLOT, vec, pb, kb);
         LAUNCH_CHECK(ctx);
     }
+    return MADQP_OK;
+}
+
+// ---- many right-hand sides: block substitution on the transposed block T = B' (solve_plan.inc) -------------------------------
+// Stream-ordered launches only: a diagonal step per block and sweep (solve_many_diag_kernel), a product on the fp64 MFMA
+// kernels per update (madqp_gemm_tn), the transposes of the caller's block and, for a handle without U = L', of one block row
+// of L per backward update.  No workgroup waits for another: no tickets, no sentinel, no spin limit, no fault word.
+namespace {
+// T (ldt x npad, ldt a multiple of 64) <- B' (B: n x nrhs, leading dimension ldb), zeros in the padding: 64 x 64 pieces through LDS
+__global__ __launch_bounds__(256) void many_in_kernel(const double* __restrict__ B, int64_t ldb, int64_t n, int64_t nrhs,
+                                                      double* __restrict__ T, int64_t ldt) {
+    __shared__ double tile[64][65];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * 64, r0 = (int64_t)blockIdx.y * 64;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int rr = ty + 4 * q;
+        tile[rr][tx] = (i0 + tx < n && r0 + rr < nrhs) ? B[i0 + tx + (r0 + rr) * ldb] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int ii = ty + 4 * q;
+        T[r0 + tx + (i0 + ii) * ldt] = tile[tx][ii];
+    }
+}
+// B <- T' (the entries i < n, r < nrhs only: rows n .. ldb-1 of the caller's columns are never touched)
+__global__ __launch_bounds__(256) void many_out_kernel(const double* __restrict__ T, int64_t ldt, int64_t n, int64_t nrhs,
+                                                       double* __restrict__ B, int64_t ldb) {
+    __shared__ double tile[64][65];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * 64, r0 = (int64_t)blockIdx.y * 64;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int ii = ty + 4 * q;
+        tile[ii][tx] = T[r0 + tx + (i0 + ii) * ldt];  // (the padded block exists up to ldt x npad)
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int rr = ty + 4 * q;
+        if (i0 + tx < n && r0 + rr < nrhs) B[i0 + tx + (r0 + rr) * ldb] = tile[tx][rr];
+    }
+}
+// S[c + k lds] <- L[k0 + k, row0 + c] for the `cols` (a multiple of 128) columns from row0 on and k < 128: the block row of L
+// that a backward update multiplies with, contraction index slow; rows at or beyond n give zeros.  grid (cols / 64, 2).
+__global__ __launch_bounds__(256) void many_strip_kernel(const double* __restrict__ A, int64_t lda, int64_t n, int64_t k0,
+                                                         int64_t row0, double* __restrict__ S, int64_t lds) {
+    __shared__ double tile[64][65];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int64_t c0 = (int64_t)blockIdx.x * 64, kk0 = (int64_t)blockIdx.y * 64;
+    const int64_t r = k0 + kk0 + tx;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int c = ty + 4 * q;
+        tile[c][tx] = r < n ? A[r + (row0 + c0 + c) * lda] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int kk = ty + 4 * q;
+        S[c0 + tx + (kk0 + kk) * lds] = tile[tx][kk];
+    }
+}
+// The diagonal step of a sweep for 16 right-hand sides per wave, X (rows x w, leading dimension ld) in place:
+//   forward   X <- X L_jj^-T :  Z = X',  Z_J = W_JJ  (C'_J - sum_{I<J} L_JI  Z_I),  J = 0 .. 7   (panel_sub16_kernel's step)
+//   backward  X <- X L_jj^-1 :           Z_J = W_JJ' (C'_J - sum_{I>J} L_IJ' Z_I),  J = 7 .. 0
+// by block substitution over the 16 x 16 sub-blocks, multiplying only with the inverses W_JJ of the DIAGONAL sub-blocks that
+// the diagonal kernel left in the image Wcm -- never with a stored 128 x 128 inverse.  On the MFMA unit in
+// registers as in panel_sub16_kernel: m = index inside the sub-block written, n = one of 16 right-hand sides, k = index
+// inside the sub-block read; a finished Z_J (accumulator layout) is the B-operand of the updates as it stands.  A short last
+// block (w < 128): entries of L at or beyond w are not loaded (they need not exist) and count as zero, the image is zero
+// there, columns at or beyond w are not stored.  A wave reads only what it writes, all up front.
+template <bool BWD>
+__global__ __launch_bounds__(256) void solve_many_diag_kernel(double* __restrict__ C, int64_t ld, const double* __restrict__ Lkk,
+                                                              int64_t ldl, const double* __restrict__ Wcm, int64_t rows, int w) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lo = lane & 15, hi = lane >> 4;
+    const int64_t i0 = (int64_t)blockIdx.x * 64 + wave * 16;
+    if (i0 >= rows) return;  // (no barrier in this kernel)
+    const int64_t gi = i0 + lo;  // (< ld: the block of right-hand sides is padded to whole 128s)
+    double* Cp = C + gi + (int64_t)hi * ld;
+    double4_t z[8];  // u_J = -(C'_J - ..) until step J, Z_J afterwards: element (16 J + hi + 4 v, right-hand side gi)
+#pragma unroll
+    for (int J = 0; J < 8; ++J)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) z[J][v] = -Cp[(int64_t)(16 * J + 4 * v) * ld];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int J = BWD ? 7 - q : q;
+        double4_t t = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {  // A[m = lo][k = 4 s + hi] = -W_JJ (forward) / -W_JJ' (backward)
+            const double aw = BWD ? -Wcm[(16 * J + 4 * s + hi) + (16 * J + lo) * NB] : -Wcm[(16 * J + lo) + (16 * J + 4 * s + hi) * NB];
+            t = __builtin_amdgcn_mfma_f64_16x16x4f64(aw, z[J][s], t, 0, 0, 0);
+        }
+        z[J] = t;  // Z_J
+#pragma unroll
+        for (int d = 0; d < 7 - q; ++d) {
+            const int J2 = BWD ? J - 1 - d : J + 1 + d;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {  // u_J2 += L_{J2,J} Z_J (forward) / L_{J,J2}' Z_J (backward)
+                const int r = BWD ? 16 * J + 4 * s + hi : 16 * J2 + lo;
+                const int c = BWD ? 16 * J2 + lo : 16 * J + 4 * s + hi;
+                const double a = r < w ? Lkk[r + (int64_t)c * ldl] : 0.0;
+                z[J2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, t[s], z[J2], 0, 0, 0);
+            }
+        }
+    }
+    if (gi < rows) {
+#pragma unroll
+        for (int J = 0; J < 8; ++J)
+#pragma unroll
+            for (int v = 0; v < 4; ++v)
+                if (16 * J + 4 * v + hi < w) Cp[(int64_t)(16 * J + 4 * v) * ld] = z[J][v];
+    }
+}
+}  // namespace
+
+extern "C" int32_t madqp_chol_set_solve_many_min(madqp_chol* s, int64_t min_nrhs) {
+    if (!s) return MADQP_ERR_ARG;
+    ARG_TRY(s->ctx, min_nrhs >= 2);
+    s->many_min = min_nrhs;
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_chol_solve_many_info(madqp_chol* s, int64_t nrhs, int64_t* out_host) {
+    if (!s) return MADQP_ERR_ARG;
+    ARG_TRY(s->ctx, out_host != nullptr && nrhs >= 0);
+    const bool blocked = nrhs >= s->many_min;
+    const bool up = s->upper_ok;  // the last factorisation left U = L'
+    SolveCount c;
+    if (blocked) {
+        std::vector<SolveOp> ops;
+        solve_plan(s->n, s->npos, s->band.sweep_kb, nrhs, ops);
+        c = solve_plan_count(ops, up);
+    } else {
+        c = solve_looped_count(s->n, s->npos, s->band.sweep_kb, nrhs, up);
+    }
+    out_host[0] = blocked ? 1 : 0;
+    out_host[1] = c.launches;
+    out_host[2] = s->many_ws_len;
+    out_host[3] = c.bytes;
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_chol_solve_many(madqp_chol* s, double* B, int64_t ldb, int64_t nrhs) {
+    if (!s) return MADQP_ERR_ARG;
+    madqp_ctx* ctx = s->ctx;
+    const int64_t n = s->n;
+    ARG_TRY(ctx, nrhs >= 0 && ldb >= std::max<int64_t>(n, 1) && (B != nullptr || n == 0 || nrhs == 0));
+    if (!s->A) return madqp_fail(ctx, MADQP_ERR_STATE, "madqp_chol_solve_many before madqp_chol_factor");
+    if (n == 0 || nrhs == 0) return MADQP_OK;
+    if (nrhs < s->many_min) {  // column by column through the one-vector sweeps (nrhs == 1: madqp_chol_solve itself)
+        for (int64_t c = 0; c < nrhs; ++c)
+            if (const int32_t r = madqp_chol_solve(s, B + c * ldb)) return r;
+        return MADQP_OK;
+    }
+    ProfScope ps(ctx, MADQP_PROF_TRSV);
+    struct ProfMute {  // (one timer scope for the call: the scopes of the products inside are switched off meanwhile)
+        madqp_ctx* c;
+        decltype(c->prof) saved;
+        explicit ProfMute(madqp_ctx* ctx_) : c(ctx_), saved(ctx_->prof) { c->prof = 0; }
+        ~ProfMute() { c->prof = saved; }
+    } mute(ctx);
+    const bool up = s->upper_ok;  // the last factorisation left U = L'
+    const int64_t lda = s->lda, npad = (n + NB - 1) / NB * NB, ldt = solve_plan_ldt(nrhs);
+    const int64_t need = solve_plan_workspace(n, nrhs, up);
+    if (need > s->many_ws_len) {  // grown here: the stream is drained before the old buffer goes
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (s->many_ws) (void)hipFree(s->many_ws);
+        s->many_ws = nullptr;
+        s->many_ws_len = 0;
+        if (hipMalloc(&s->many_ws, (size_t)need * sizeof(double)) != hipSuccess) {
+            (void)hipGetLastError();
+            s->many_ws = nullptr;
+            return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_chol_solve_many: no memory for %lld doubles of workspace", (long long)need);
+        }
+        s->many_ws_len = need;
+    }
+    double* T = s->many_ws;
+    double* strip = T + ldt * npad;  // (npad x 128, leading dimension npad; only without U)
+    const double* A = s->A;
+    const bool padded = s->band.packed || lda >= npad;  // rows up to the padded order may be read (CholTarget::padded)
+    std::vector<SolveOp> ops;
+    solve_plan(n, s->npos, s->band.sweep_kb, nrhs, ops);
+    const dim3 tgrid((unsigned)(npad / 64), (unsigned)(ldt / 64));
+    hipLaunchKernelGGL(many_in_kernel, tgrid, dim3(256), 0, ctx->stream, (const double*)B, ldb, n, nrhs, T, ldt);
+    LAUNCH_CHECK(ctx);
+    for (const SolveOp& o : ops) {
+        if (o.kind == SOLVE_DIAG) {
+            const auto kern = o.sweep ? solve_many_diag_kernel<true> : solve_many_diag_kernel<false>;
+            hipLaunchKernelGGL(kern, dim3((unsigned)((nrhs + 63) / 64)), dim3(256), 0, ctx->stream, T + o.k0 * ldt, ldt,
+                               A + o.k0 + o.k0 * lda, lda, (const double*)(s->winv + o.blk * WBLK), nrhs, (int)(o.k1 - o.k0));
+            LAUNCH_CHECK(ctx);
+        } else if (o.kind == SOLVE_NEGATE) {
+            const int64_t len = o.rows * ldt;
+            hipLaunchKernelGGL(negate_kernel, dim3((unsigned)std::min<int64_t>((len + 255) / 256, 1024)), dim3(256), 0, ctx->stream,
+                               T + o.row0 * ldt, len);
+            LAUNCH_CHECK(ctx);
+        } else {
+            GemmArgs g{};
+            g.X = T + o.k0 * ldt;
+            g.ldx = ldt;
+            g.C = T + o.row0 * ldt;
+            g.ldc = ldt;
+            g.Cin = g.C;
+            g.ldcin = ldt;
+            g.alpha = -1.0;
+            g.beta = 1.0;
+            g.M = nrhs;
+            g.Mread = ldt;
+            g.N = o.rows;
+            if (o.sweep == 0) {  // Y[i + k ldy] = L[row0 + i, k0 + k]
+                g.Y = A + o.row0 + o.k0 * lda;
+                g.ldy = lda;
+                g.K = o.k1 - o.k0;  // (a block with rows below it is a whole one)
+                if (padded) g.Nread = (o.rows + NB - 1) / NB * NB;
+            } else {  // Y[c + k ldy] = L[k0 + k, row0 + c]: U, or the strip; K = 128 with zeros from n on (T is zero there too)
+                if (up) {
+                    g.Y = s->upper + o.row0 + o.k0 * s->upper_ld;
+                    g.ldy = s->upper_ld;
+                } else {
+                    hipLaunchKernelGGL(many_strip_kernel, dim3((unsigned)(o.rows / 64), 2), dim3(256), 0, ctx->stream, A, lda, n, o.k0,
+                                       o.row0, strip, npad);
+                    LAUNCH_CHECK(ctx);
+                    g.Y = strip;
+                    g.ldy = npad;
+                }
+                g.K = NB;
+                g.Nread = o.rows;
+            }
+            if (const int32_t r = madqp_gemm_tn(ctx, g, MADQP_PROF_TRSV)) return r;
+        }
+    }
+    hipLaunchKernelGGL(many_out_kernel, tgrid, dim3(256), 0, ctx->stream, (const double*)T, ldt, n, nrhs, B, ldb);
+    LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }

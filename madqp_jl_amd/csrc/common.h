@@ -335,4 +335,10 @@ struct madqp_chol {
     double* utmp = nullptr;
     int64_t utmp_len = 0;
     bool upper_ok = false;  // the last factorisation left U and substitution images
+    // madqp_chol_solve_many: the transposed block of right-hand sides and, without U, the strip of one block row of L'
+    // (solve_plan.inc: solve_plan_workspace), grown at the first call that needs more; from many_min right-hand sides on
+    // the call takes the blocked path
+    double* many_ws = nullptr;
+    int64_t many_ws_len = 0;
+    int64_t many_min = 0;  // (madqp_chol_create: the measured default)
 };

@@ -64,6 +64,9 @@ struct madqp_kkt {
     int32_t refine = 0;
     double* rf = nullptr;
     int64_t rf_cap = 0;
+    // madqp_kkt_solve_many: the work vectors t, u, tn, b of its columns, one grow-only buffer (kkt_many_work)
+    double* many = nullptr;
+    int64_t many_cap = 0;
     // fused per-variable passes of the condensed mode (solve_pre_kernel / solve_post_kernel / resid_tail_kernel below):
     // where each variable sits in the two bound lists (-1: not there), built when the lists are first seen (grow-only
     // buffers, allocated with rs at the first fused pass), and the reduced right-hand side of the slacks kept between the
@@ -922,68 +925,91 @@ extern "C" int32_t madqp_kkt_solve(madqp_kkt* k, const madqp_state* st, double* 
     return MADQP_OK;
 }
 
-// The middle of a solve, one function per form: on entry w holds the reduced right-hand side [r1; r2; ..], on return dx
-// (with ds) in wx and dy in wy.
-static int32_t kkt_solve_normal(madqp_kkt* k, const madqp_state* st, double* wx, double* wy) {  // src/KKT/normalkkt.jl:185-201
+// The work vectors of one right-hand side: the object's own (madqp_kkt_solve), or one column of each of the blocks that
+// madqp_kkt_solve_many grows (kkt_many_work)
+struct KktWork {
+    double *t, *u;  // m
+    double* tn;     // normal mode: n
+    double* b;      // augmented mode: the stored order
+};
+static KktWork kkt_own_work(const madqp_kkt* k) { return KktWork{k->t, k->u, k->tn, k->b}; }
+// what the factor solves for the right-hand side w: dy in place (normal), the vector b (augmented), dx in place (condensed)
+static double* kkt_factor_rhs(const madqp_kkt* k, const madqp_state* st, double* w, const KktWork& wk) {
+    return k->mode == KKT_NORMAL ? w + st->n : k->mode == KKT_AUGMENTED ? wk.b : w;
+}
+
+// The middle of a solve, two functions per form around the factor solve: on entry of `before` w holds the reduced
+// right-hand side [r1; r2; ..], on return of `after` dx (with ds) in wx and dy in wy.
+static int32_t kkt_normal_before(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk) {  // src/KKT/normalkkt.jl:185-201
     int32_t r = 0;
     madqp_ctx* ctx = k->ctx;
     const double* sig = k->hdiag ? k->sg : st->pr_diag;  // H + Sigma
     {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        if (st->n) LAUNCH(div_kernel, st->n, st->n, wx, sig, k->tn);  // r1 = (H + Sigma)^-1 wx
+        if (st->n) LAUNCH(div_kernel, st->n, st->n, wx, sig, wk.tn);  // r1 = (H + Sigma)^-1 wx
     }
-    if ((r = apply_A(k, 1.0, k->tn, 0.0, k->u))) return r;
+    if ((r = apply_A(k, 1.0, wk.tn, 0.0, wk.u))) return r;
     if (k->m) {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        LAUNCH(normal_rhs_kernel, k->m, k->m, k->d_slot, k->u, k->tn + k->nx, wy, wy);  // A r1 - r2
+        LAUNCH(normal_rhs_kernel, k->m, k->m, k->d_slot, wk.u, wk.tn + k->nx, wy, wy);  // A r1 - r2
     }
-    if ((r = madqp_chol_solve(k->chol, wy))) return r;  // wy = dy
-    if ((r = apply_At(k, 1.0, wy, 0.0, k->tn))) return r;
+    return MADQP_OK;  // the factor: wy = dy
+}
+static int32_t kkt_normal_after(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk) {
+    int32_t r = 0;
+    madqp_ctx* ctx = k->ctx;
+    const double* sig = k->hdiag ? k->sg : st->pr_diag;
+    if ((r = apply_At(k, 1.0, wy, 0.0, wk.tn))) return r;
     ProfScope ps(ctx, MADQP_PROF_VEC);
-    if (k->ns) LAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, wy, k->tn + k->nx, 1.0, 0.0);
-    if (st->n) LAUNCH(normal_back_kernel, st->n, st->n, k->tn, sig, wx);
+    if (k->ns) LAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, wy, wk.tn + k->nx, 1.0, 0.0);
+    if (st->n) LAUNCH(normal_back_kernel, st->n, st->n, wk.tn, sig, wx);
     return MADQP_OK;
 }
-static int32_t kkt_solve_augmented(madqp_kkt* k, const madqp_state* st, double* wx, double* wy) {
-    int32_t r = 0;
+static int32_t kkt_augmented_before(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk) {
     madqp_ctx* ctx = k->ctx;
     const int64_t N = k->np + k->m;
     const double* sf = k->scaled ? k->sfac : nullptr;
     if (N) {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        LAUNCH(aug_rhs_kernel, N, k->nx, k->np, k->m, k->d_slot, st->pr_diag, sf, wx, wy, k->b);
+        LAUNCH(aug_rhs_kernel, N, k->nx, k->np, k->m, k->d_slot, st->pr_diag, sf, wx, wy, wk.b);
     }
-    if ((r = madqp_chol_solve(k->chol, k->b))) return r;
+    return MADQP_OK;  // the factor: b
+}
+static int32_t kkt_augmented_after(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk) {
+    madqp_ctx* ctx = k->ctx;
+    const double* sf = k->scaled ? k->sfac : nullptr;
     if (k->nx + k->m) {
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        LAUNCH(aug_back_kernel, k->nx + k->m, k->nx, k->np, k->m, k->d_slot, st->pr_diag, sf, k->b, wx, wy);
+        LAUNCH(aug_back_kernel, k->nx + k->m, k->nx, k->np, k->m, k->d_slot, st->pr_diag, sf, wk.b, wx, wy);
     }
     return MADQP_OK;
 }
-static int32_t kkt_solve_condensed(madqp_kkt* k, const madqp_state* st, double* wx, double* wy) {
-    int32_t r = 0;
+static int32_t kkt_condensed_before(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk) {
     madqp_ctx* ctx = k->ctx;
     if (k->m) {
         {
             ProfScope ps(ctx, MADQP_PROF_VEC);
-            LAUNCH(condense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, wx, wy, k->t, k->u);
+            LAUNCH(condense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, wx, wy, wk.t, wk.u);
         }
-        if ((r = apply_At(k, 1.0, k->u, 1.0, wx))) return r;  // rhs_x = r1_x + A' (theta t)
+        if (int32_t r = apply_At(k, 1.0, wk.u, 1.0, wx)) return r;  // rhs_x = r1_x + A' (theta t)
     }
-    if ((r = madqp_chol_solve(k->chol, wx))) return r;
+    return MADQP_OK;  // the factor: wx = dx
+}
+static int32_t kkt_condensed_after(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk) {
+    madqp_ctx* ctx = k->ctx;
     if (k->m) {
-        if ((r = apply_A(k, 1.0, wx, 0.0, k->u))) return r;
+        if (int32_t r = apply_A(k, 1.0, wx, 0.0, wk.u)) return r;
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        LAUNCH(decondense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, k->t, k->u, wx, wy);
+        LAUNCH(decondense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, wk.t, wk.u, wx, wy);
     }
     return MADQP_OK;
 }
 
-// reduce_rhs!, the form's own middle, finish_aug_solve! -- the K2.5 object with its sign-flipped first and last step
-static int32_t kkt_solve_once(madqp_kkt* k, const madqp_state* st, double* w) {
+// The three stages of a solve.  Before the factor solve: reduce_rhs! and the first half of the form's middle -- the K2.5
+// object with its sign-flipped first and last step.
+static int32_t kkt_solve_before(madqp_kkt* k, const madqp_state* st, double* w, const KktWork& wk) {
     int32_t r = 0;
     madqp_ctx* ctx = k->ctx;
-    k->u_is_A_of = nullptr;
     if (k->scaled) {  // r1 = p_x + p_zl / l_diag + p_zu / u_diag (signs of src/kernels.jl:157-158)
         ProfScope ps(ctx, MADQP_PROF_VEC);
         if (st->nlb) LAUNCH(k25_reduce_kernel, st->nlb, *st, w);
@@ -991,17 +1017,94 @@ static int32_t kkt_solve_once(madqp_kkt* k, const madqp_state* st, double* w) {
     } else if ((r = madqp_reduce_rhs(ctx, st, w))) {
         return r;
     }
-    r = k->mode == KKT_NORMAL      ? kkt_solve_normal(k, st, w, w + st->n)
-        : k->mode == KKT_AUGMENTED ? kkt_solve_augmented(k, st, w, w + st->n)
-                                   : kkt_solve_condensed(k, st, w, w + st->n);
+    return k->mode == KKT_NORMAL      ? kkt_normal_before(k, st, w, w + st->n, wk)
+           : k->mode == KKT_AUGMENTED ? kkt_augmented_before(k, st, w, w + st->n, wk)
+                                      : kkt_condensed_before(k, st, w, w + st->n, wk);
+}
+// after it: the second half of the middle and finish_aug_solve!
+static int32_t kkt_solve_after(madqp_kkt* k, const madqp_state* st, double* w, const KktWork& wk) {
+    madqp_ctx* ctx = k->ctx;
+    const int32_t r = k->mode == KKT_NORMAL      ? kkt_normal_after(k, st, w, w + st->n, wk)
+                      : k->mode == KKT_AUGMENTED ? kkt_augmented_after(k, st, w, w + st->n, wk)
+                                                 : kkt_condensed_after(k, st, w, w + st->n, wk);
     if (r) return r;
     if (k->scaled) {
         ProfScope ps(ctx, MADQP_PROF_VEC);
         if (std::max(st->nlb, st->nub) > 0) LAUNCH(k25_finish_kernel, std::max(st->nlb, st->nub), *st, w);
         return MADQP_OK;
     }
-    if ((r = madqp_finish_aug_solve(ctx, st, w))) return r;
-    if (k->mode == KKT_CONDENSED && k->m) k->u_is_A_of = w;  // dx is final since the sweeps: u = A dx (madqp_kkt_mul_solved)
+    return madqp_finish_aug_solve(ctx, st, w);
+}
+
+static int32_t kkt_solve_once(madqp_kkt* k, const madqp_state* st, double* w) {
+    int32_t r = 0;
+    k->u_is_A_of = nullptr;
+    const KktWork wk = kkt_own_work(k);
+    if ((r = kkt_solve_before(k, st, w, wk))) return r;
+    if ((r = madqp_chol_solve(k->chol, kkt_factor_rhs(k, st, w, wk)))) return r;
+    if ((r = kkt_solve_after(k, st, w, wk))) return r;
+    if (!k->scaled && k->mode == KKT_CONDENSED && k->m) k->u_is_A_of = w;  // dx is final since the sweeps: u = A dx (madqp_kkt_mul_solved)
+    return MADQP_OK;
+}
+
+// ---- many right-hand sides (madqp_kkt_solve_many) ------------------------------------------------------------------------
+// The same three stages with the middle one shared: stage 1 for every column, ONE madqp_chol_solve_many on the column-major
+// matrix that the columns' factor right-hand sides form where they stand (dy / dx inside W with leading dimension ldw; the
+// augmented form's b vectors in a block of their own), stage 3 for every column.  The per-column passes are the kernels of
+// the one-vector solve launched on offset pointers, the products with A / A' stay mat-vecs per column.
+// column c of the work blocks: [t | u | tn | b], each a block of nrhs columns at a stride of whole 256 bytes
+static int64_t kkt_pad32(int64_t v) { return (v + 31) / 32 * 32; }
+static KktWork kkt_many_work(const madqp_kkt* k, const madqp_state* st, int64_t nrhs, int64_t c) {
+    const int64_t sm = kkt_pad32(k->m), sn = k->mode == KKT_NORMAL ? kkt_pad32(st->n) : 0;
+    const int64_t sb = k->mode == KKT_AUGMENTED ? kkt_pad32(k->chol->n) : 0;
+    double* t = k->many;
+    double* u = t + nrhs * sm;
+    double* tn = u + nrhs * sm;
+    double* b = tn + nrhs * sn;
+    return KktWork{t + c * sm, u + c * sm, tn + c * sn, b + c * sb};
+}
+static int32_t kkt_solve_many_once(madqp_kkt* k, const madqp_state* st, double* W, int64_t ldw, int64_t nrhs) {
+    int32_t r = 0;
+    const int64_t per = 2 * kkt_pad32(k->m) + (k->mode == KKT_NORMAL ? kkt_pad32(st->n) : 0) +
+                        (k->mode == KKT_AUGMENTED ? kkt_pad32(k->chol->n) : 0);
+    if ((r = k->mem.grow(&k->many, &k->many_cap, nrhs * per, "madqp_kkt_solve_many: work vectors of the columns"))) return r;
+    k->u_is_A_of = nullptr;
+    for (int64_t c = 0; c < nrhs; ++c)
+        if ((r = kkt_solve_before(k, st, W + c * ldw, kkt_many_work(k, st, nrhs, c)))) return r;
+    const int64_t ldb = k->mode == KKT_AUGMENTED ? kkt_pad32(k->chol->n) : ldw;
+    if ((r = madqp_chol_solve_many(k->chol, kkt_factor_rhs(k, st, W, kkt_many_work(k, st, nrhs, 0)), ldb, nrhs))) return r;
+    for (int64_t c = 0; c < nrhs; ++c)
+        if ((r = kkt_solve_after(k, st, W + c * ldw, kkt_many_work(k, st, nrhs, c)))) return r;
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_kkt_solve_many(madqp_kkt* k, const madqp_state* st, double* W, int64_t ldw, int64_t nrhs) {
+    int32_t r = check_kkt_state(k, st);
+    if (r) return r;
+    if ((r = kkt_storage_ready(k, "madqp_kkt_solve_many"))) return r;
+    madqp_ctx* ctx = k->ctx;
+    const int64_t len = st->n + st->m + st->nlb + st->nub;
+    ARG_TRY(ctx, nrhs >= 0 && (W != nullptr || nrhs == 0) && ldw >= len);
+    if (nrhs == 0) return MADQP_OK;
+    if (nrhs == 1) return madqp_kkt_solve(k, st, W);
+    if (k->refine <= 0) return kkt_solve_many_once(k, st, W, ldw, nrhs);
+    // refinement as in madqp_kkt_solve, the residuals per column, the corrections through one solve of the residual block
+    const int64_t stride = kkt_pad32(len);
+    if ((r = k->mem.grow(&k->rf, &k->rf_cap, 2 * nrhs * stride, "madqp_kkt_solve_many: work vectors of the refinement steps"))) return r;
+    double *rf_p = k->rf, *rf_r = k->rf + nrhs * stride;
+    for (int64_t c = 0; c < nrhs; ++c)
+        if ((r = madqp_copy(ctx, len, W + c * ldw, rf_p + c * stride))) return r;  // p
+    if ((r = kkt_solve_many_once(k, st, W, ldw, nrhs))) return r;                  // w = K^-1 p
+    for (int32_t it = 0; it < k->refine; ++it) {
+        for (int64_t c = 0; c < nrhs; ++c) {
+            if ((r = madqp_copy(ctx, len, rf_p + c * stride, rf_r + c * stride))) return r;
+            if ((r = madqp_kkt_mul(k, st, rf_r + c * stride, W + c * ldw, -1.0, 1.0))) return r;  // r = p - K w
+        }
+        if ((r = kkt_solve_many_once(k, st, rf_r, stride, nrhs))) return r;
+        for (int64_t c = 0; c < nrhs; ++c)
+            if ((r = madqp_axpy(ctx, len, 1.0, rf_r + c * stride, W + c * ldw))) return r;  // w += K^-1 r
+    }
+    k->u_is_A_of = nullptr;
     return MADQP_OK;
 }
 

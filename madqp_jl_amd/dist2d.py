@@ -393,6 +393,11 @@ class HIPDistributedCondensedKKTSystem2D:
         self.be._ck(self.be.lib.madqp_dkkt_solve(self._h, C.byref(self.st.cstruct), w.data_ptr()))
         return w
 
+    def solve_many(self, W):
+        from .kkt import GRID_REFUSAL
+
+        raise ValueError(GRID_REFUSAL)
+
     def mul(self, w, v, alpha=1.0, beta=0.0):
         self.be._ck(self.be.lib.madqp_dkkt_mul(self._h, C.byref(self.st.cstruct), w.data_ptr(), v.data_ptr(), alpha, beta))
         return w

@@ -54,6 +54,28 @@ def check_storage(storage, bandwidth, band_form="condensed", H=None):
             raise ValueError("storage='packed' needs a sparse (DeviceSymCSR), diagonal or absent Hessian, not a dense one")
 
 
+GRID_REFUSAL = ("solves with a block of right-hand sides are not available on a grid of GPUs "
+                "(madqp_dist_* / madqp_dkkt_* take one vector): loop over solve()")
+
+
+def check_rhs_block(W, length, device, what="W"):
+    """The refusals of a block of right-hand sides, before any device call: a contiguous 2-D float64 tensor on the
+    backend's device, one right-hand side per row, rows of at least ``length`` entries.  Returns the number of rows."""
+    import torch
+
+    if not isinstance(W, torch.Tensor) or W.dim() != 2:
+        raise ValueError(f"{what}: a 2-D tensor (nrhs, >= {length}), one right-hand side per row")
+    if W.dtype != torch.float64:
+        raise ValueError(f"{what}: float64, not {W.dtype}")
+    if W.device != torch.device(device):
+        raise ValueError(f"{what}: on {torch.device(device)}, not {W.device}")
+    if W.shape[1] < length:
+        raise ValueError(f"{what}: rows of at least {length} entries, not {W.shape[1]}")
+    if not W.is_contiguous():
+        raise ValueError(f"{what}: contiguous (row c = right-hand side c at stride shape[1]), strides {tuple(W.stride())}")
+    return W.shape[0]
+
+
 class HIPCholeskySolver:
     """AbstractLinearSolver contract: ctor keeps the matrix it re-reads at every
     ``factorize`` (src/KKT/normalkkt.jl:99-101); ``solve`` is in place (:196)."""
@@ -82,6 +104,25 @@ class HIPCholeskySolver:
 
     def is_factorized(self) -> bool:  # MadIPM.is_factorized, src/utils.jl:54-62
         return self.info == 0
+
+    def solve(self, rhs):
+        """MadNLP.solve!(linear_solver, rhs), in place.  ``rhs``: a vector of the matrix's order (``madqp_chol_solve``)
+        or a contiguous 2-D float64 tensor ``(nrhs, >= order)``, one right-hand side per row -- LAPACK's column-major
+        n x nrhs operand -- solved with one factor (``madqp_chol_solve_many``)."""
+        if self._kkt is None:
+            raise ValueError(GRID_REFUSAL)
+        ch, order = self.be.kkt_chol(self._kkt)
+        import torch
+
+        if isinstance(rhs, torch.Tensor) and rhs.dim() == 1:
+            if rhs.dtype != torch.float64 or rhs.numel() < order or not rhs.is_contiguous():
+                raise ValueError(f"rhs: a contiguous float64 vector of at least {order} entries")
+            self.be.chol_solve(ch, rhs)
+            return rhs
+        check_rhs_block(rhs, order, self.be.device, "rhs")
+        if rhs.shape[0]:
+            self.be.chol_solve_many(ch, rhs, max(rhs.shape[1], 1))
+        return rhs
 
     def is_inertia(self) -> bool:
         return True
@@ -183,6 +224,16 @@ class HIPCondensedKKTSystem:
     def solve(self, w):  # MadNLP.solve!(kkt, w), :182-205
         self.be.kkt_solve(self._h, self.st, w)
         return w
+
+    def solve_many(self, W):
+        """MadNLP.solve!(kkt, w) for every row of ``W`` with one factor (``madqp_kkt_solve_many``): ``W`` is a contiguous
+        2-D float64 device tensor ``(nrhs, >= n + m + nlb + nub)``, row c an UnreducedKKTVector.values, solved in place.
+        Anything else is refused before a device call.  ``set_refine`` is honoured; ``mul_solved`` afterwards is ``mul``."""
+        st = self.st
+        nrhs = check_rhs_block(W, st.n + st.m + st.nlb + st.nub, self.be.device)
+        if nrhs:
+            self.be.kkt_solve_many(self._h, st, W)
+        return W
 
     def set_refine(self, steps):
         """Refinement steps ``solve`` runs itself (``madqp_kkt_set_refine``; -1 = the AUTO rule by order).  For hosts whose
