@@ -1,94 +1,13 @@
-// Schedule of the band-limited left-looking factorisation (see chol.hip, "band driver") and, at the end, the job lists of
-// the triangular sweeps under a band with band_sweep_range, the one place that says which tiles a sweep job reads: plain
-// C++17, shared by chol.hip (host code and both sweep kernels) and the CPU test build tests/csrc_band (one library, three
-// sanitized check programs).  The matrix is dense, column-major and of order n with half-bandwidth bw (A[i,j] = 0 for i - j > bw); a factor without pivoting stays inside the band, so every product and
-// every panel solve of the dense schedule is cut down to the rows and the k-range the band can reach.
-#include <algorithm>
-#include <cstdint>
-#include <vector>
+// The band-limited Cholesky beyond its schedule (chol_plan.inc): packed band storage and the job lists of the sweeps under a
+// band with band_sweep_range, the one place that says which tiles a sweep job reads.  Plain C++17, shared by chol.hip (host
+// code and both sweep kernels) and the CPU test build tests/csrc_band (one library, three sanitized check programs).
+#include "chol_plan.inc"
 
-constexpr int64_t BAND_NB = 128;    // block width (chol.hip: NB)
-constexpr int64_t BAND_NBO = 1024;  // outer panel of the dense schedule without an update (chol.hip: NBO)
-
-// UPDATE: C[row0:row0+rows, row0:row0+width] -= L[row0:row0+rows, k0:kend] L[row0:row0+width, k0:kend]', lower part only.
-// BLOCK:  factor the diagonal block of width w <= 128 at jb, then solve the `rows` rows below it.
-enum { BAND_UPDATE = 0, BAND_BLOCK = 1 };
-struct BandOp {
-    int32_t kind;
-    int64_t row0, rows, k0, kend, width;  // BLOCK: row0 = jb, width = w, k0 = kend = 0
-};
-
-static int64_t band_up(int64_t v) { return (v + BAND_NB - 1) / BAND_NB * BAND_NB; }
-static int64_t band_down(int64_t v) { return v < 0 ? 0 : v / BAND_NB * BAND_NB; }
-
-// Width (multiple of 128) of the dense schedule's next outer panel over `rows` remaining rows: the wide update runs
-// (rows/128) x (W/128) tiles of equal cost on `slots` resident workgroups, W fills the last round of tiles best.
-static int64_t plan_outer_width(int64_t rows, bool has_update, int64_t slots, int64_t wt_min, int64_t wt_max) {
-    const int64_t mt = (rows + BAND_NB - 1) / BAND_NB;
-    if (!has_update || mt <= 6) return BAND_NBO;
-    int64_t best = BAND_NBO / BAND_NB;
-    double best_eff = -1.0;
-    for (int64_t wt = wt_min; wt <= wt_max && wt <= mt; ++wt) {
-        const int64_t tiles = mt * wt - wt * (wt - 1) / 2;
-        const int64_t rounds = (tiles + slots - 1) / slots;
-        const double eff = (double)tiles / (double)(rounds * slots);
-        if (eff > best_eff + 1e-9 || (eff > best_eff - 0.01 && wt > best && eff > 0.97)) {
-            best_eff = std::max(eff, best_eff);
-            best = wt;
-        }
-    }
-    return best * BAND_NB;
-}
-
-// Outer panel of the band schedule.  Where the band does not limit the remaining rows the dense rule holds (so the plan at
-// bw = n - 1 IS the dense schedule).  Where it does, a round of tiles is never full and the dense rule has nothing to
-// optimise: the panel is as wide as the band in whole blocks, within [wt_min, wt_max] blocks -- a wider panel makes the
-// outer update run tiles with i - j > bw (products of stored zeros), a narrower one adds dependent launches.  force_wt > 0
-// fixes the width in blocks (measurements).
-static int64_t band_outer_width(int64_t rows, int64_t bw, bool has_update, int64_t slots, int64_t wt_min, int64_t wt_max,
-                                int64_t force_wt) {
-    const int64_t mt = (rows + BAND_NB - 1) / BAND_NB, mb = bw / BAND_NB + 1;
-    if (mb >= mt) return plan_outer_width(rows, has_update, slots, wt_min, wt_max);
-    if (force_wt > 0) return force_wt * BAND_NB;
-    return std::max(wt_min, std::min(mb, wt_max)) * BAND_NB;
-}
-
-static void band_plan_block(int64_t n, int64_t bw, int64_t jb, int64_t w, std::vector<BandOp>& ops) {
-    // the rows below the block that the band reaches from its columns: i <= jb + w - 1 + bw
-    ops.push_back({BAND_BLOCK, jb, std::min(band_up(bw), n - jb - w), 0, 0, w});
-}
-// an update of the columns [row0, row0 + width) with the columns [lo, row0) to their left, band-limited; nothing when the
-// band reaches none of them
-static void band_plan_update(int64_t n, int64_t bw, int64_t lo, int64_t row0, int64_t width, std::vector<BandOp>& ops) {
-    const int64_t k0 = std::max(lo, band_down(row0 - bw));
-    if (k0 >= row0) return;
-    ops.push_back({BAND_UPDATE, row0, std::min(band_up(width + bw), n - row0), k0, row0, width});
-}
-// the recursive halving of chol.hip's factor_range
-static void band_plan_range(int64_t n, int64_t bw, int64_t j0, int64_t w, std::vector<BandOp>& ops) {
-    if (w <= BAND_NB) return band_plan_block(n, bw, j0, w, ops);
-    const int64_t h = ((w + BAND_NB - 1) / BAND_NB + 1) / 2 * BAND_NB;
-    band_plan_range(n, bw, j0, h, ops);
-    band_plan_update(n, bw, j0, j0 + h, w - h, ops);
-    band_plan_range(n, bw, j0 + h, w - h, ops);
-}
-
-// The ordered operations of the factorisation of an order-n matrix with half-bandwidth bw (0 <= bw < n) on `slots` resident
-// GEMM workgroups; returns the extent: the largest i - j of any entry an operation reads or writes (n - 1 at bw = n - 1).
-// Rows are counted up to n; a padded leading dimension lets the kernels read (never write) whole tiles beyond n.
-static int64_t band_plan(int64_t n, int64_t bw, int64_t slots, std::vector<BandOp>& ops, int64_t wt_min = 6,
-                         int64_t wt_max = 20, int64_t force_wt = 0) {
-    ops.clear();
-    int64_t W = 0;
-    for (int64_t J0 = 0; J0 < n; J0 += W) {
-        W = std::min<int64_t>(band_outer_width(n - J0, bw, J0 > 0, slots, wt_min, wt_max, force_wt), n - J0);
-        band_plan_update(n, bw, 0, J0, W, ops);
-        band_plan_range(n, bw, J0, W, ops);
-    }
-    int64_t extent = 0;
-    for (const BandOp& o : ops)
-        extent = std::max(extent, o.kind == BAND_UPDATE ? o.row0 + o.rows - 1 - o.k0 : o.width + o.rows - 1);
-    return extent;
+// The plan under a band, in the band's own names: positive definite (a band admits no signature), so every update subtracts.
+using BandOp = CholOp;
+enum { BAND_UPDATE = CHOL_UPDATE, BAND_BLOCK = CHOL_BLOCK };
+static int64_t band_plan(int64_t n, int64_t bw, int64_t slots, std::vector<BandOp>& ops, int64_t wt_min = 6, int64_t wt_max = 20, int64_t force_wt = 0) {
+    return chol_plan(n, bw, n, slots, ops, wt_min, wt_max, force_wt);
 }
 
 // ---- packed band storage (madqp_chol_set_packed, madqp_chol_packed_layout) --------------------------------------------------
@@ -120,7 +39,7 @@ static bool band_packed_layout(int64_t n, int64_t extent, int64_t ld_in, int64_t
 // ---- the triangular sweeps under a band (chol.hip, trsv_*_sweep_kernel) --------------------------------------------------
 // Block row r of the factor has nonzero tiles (r, j) for r - kb <= j < r only, kb = band_up(bw) / 128: a tile further left
 // holds entries with i - j >= (kb + 1) 128 - 127 > bw alone.  The sweeps read those tiles and the diagonal blocks, so the
-// largest i - j they touch is min(n - 1, kb 128 + 127) -- never above the extent of band_plan, whose first BLOCK op alone
+// largest i - j they touch is min(n - 1, kb 128 + 127) -- never above the extent of chol_plan, whose first BLOCK op alone
 // reaches min(band_up(bw) + 127, n - 1) for n >= 128.  The backward sweep is the same in chain coordinates (position rr
 // is block nblk - 1 - rr, its tiles are counted from the last block row).
 static int64_t band_sweep_blocks(int64_t bw) { return band_up(bw) / BAND_NB; }

@@ -21,9 +21,9 @@
 // ticket-ordered workgroups handing the solved blocks on through a sentinel-tagged vector, HBM bound
 // (4 n^2 bytes); block rows longer than 64 tiles are streamed by several workgroups (SweepPlan).  Which tiles a sweep
 // job reads is decided in one place, band_sweep_range of band_plan.inc, which both sweep kernels and the CPU checks call.
-// Host side: ONE left-looking driver (panel_update / factor_block / factor_range) on a CholTarget -- one matrix
-// (madqp_chol_factor), a batch of small matrices at fixed strides (madqp_chol_factor_batched) or a panel of the multi-GPU
-// loop (madqp_chol_factor_panel, ...); ONE panel solve of a 128-column block (madqp_chol_panel_solve), shared with the
+// Host side: ONE left-looking schedule as a list of operations (chol_plan.inc) and ONE executor of it (run_ops: panel_update /
+// factor_block) on a CholTarget -- one matrix (madqp_chol_factor), a batch of small matrices at fixed strides (madqp_chol_factor_batched)
+// or a panel of the multi-GPU loop (madqp_chol_factor_panel, ...); ONE panel solve of a 128-column block (madqp_chol_panel_solve), shared with the
 // mid-size schedule (factor_mid) and dist.hip; the environment is read in one place (CholModes).
 #include <algorithm>
 #include <cstdlib>
@@ -1343,7 +1343,7 @@ struct CholModes {
     int64_t mid_max;          // MADQP_CHOL_MID_MAX (13312): largest order of the mid-size schedule
     int mid_cap;              // MADQP_CHOL_MID_CAP (0 = from the CU count; experiments)
     int64_t wt_min, wt_max;   // MADQP_CHOL_WMIN / WMAX (6, 20): outer panel width in blocks
-    int64_t band_w;           // MADQP_CHOL_BAND_W (0 = the rule of band_plan.inc): outer panel in blocks where a band limits it
+    int64_t band_w;           // MADQP_CHOL_BAND_W (0 = the rule of chol_plan.inc): outer panel in blocks where a band limits it
 };
 static CholModes chol_modes_from_env() {
     auto num = [](const char* name, int64_t dflt) { return getenv(name) ? atoll(getenv(name)) : dflt; };
@@ -1413,6 +1413,11 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
     return MADQP_OK;
 }
 
+// The left-looking plan (chol_plan.inc) of handle s at half-bandwidth bw (-1: none) and its signature; returns the extent.
+static int64_t handle_plan(const madqp_chol* s, int64_t bw, std::vector<CholOp>& ops) {
+    return chol_plan(s->n, bw < 0 ? s->n - 1 : bw, s->npos, s->ctx->gemm_slots, ops, chol_modes().wt_min, chol_modes().wt_max, chol_modes().band_w);
+}
+
 // Quasi-definite mode: the matrix handed to madqp_chol_factor is [P, .; B, Q] (lower triangle, P of order npos
 // and Q positive definite) and stands for [P, B'; B, -Q]; factor computes L with [P, B'; B, -Q] = L diag(I_npos, -I) L',
 // solve applies the inverse of that matrix.  npos a multiple of 128 (or n, which restores plain Cholesky).
@@ -1421,6 +1426,7 @@ extern "C" int32_t madqp_chol_set_signature(madqp_chol* s, int64_t npos) {
     ARG_TRY(s->ctx, npos >= 0 && npos <= s->n && (npos % NB == 0 || npos == s->n));
     ARG_TRY(s->ctx, s->band.bw < 0 || npos == s->n);  // the band schedule factors positive definite matrices only
     s->npos = npos;
+    s->plan.clear();  // (built again at the next left-looking factorisation)
     s->factored = false;
     return MADQP_OK;
 }
@@ -1445,7 +1451,7 @@ extern "C" int32_t madqp_chol_destroy(madqp_chol* s) {
 // ---- band driver -------------------------------------------------------------------------------------------------------
 // A matrix with half-bandwidth bw (A[i,j] = 0 for i - j > bw) has a factor inside the same band, so the left-looking
 // schedule below runs its products, diagonal kernels and panel solves on band-limited ranges only: the plan of
-// band_plan.inc, built here once per bandwidth.  The storage stays dense (or packed, below).  The sweeps of madqp_chol_solve stay inside the
+// chol_plan.inc, built here once per bandwidth.  The storage stays dense (or packed, below).  The sweeps of madqp_chol_solve stay inside the
 // band as well (MADQP_SWEEP_BAND, default 1): block row r streams the band_sweep_blocks(bw) tiles next to its diagonal
 // block, along a job list of its own where the dense sweeps have one.  bw = -1 clears the bandwidth (the dense schedules
 // and sweeps, launch for launch as without this call).
@@ -1461,12 +1467,12 @@ extern "C" int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw) {
     // (the extent changes with the bandwidth and packed storage is laid out for one extent: madqp_chol_set_packed again)
     if (s->band.d_jobs) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (a solve on the stream may still read the list)
     HIP_TRY(ctx, s->band.clear(s->n));
+    s->plan.clear();  // (without a band: built at the next left-looking factorisation)
     if (bw < 0) return MADQP_OK;
     // the new state in a local: the handle takes it once the plan and the job list both stand, and keeps "no band" otherwise
     madqp_chol_band b;
     b.bw = bw;
-    const CholModes& md = chol_modes();
-    b.extent = band_plan(s->n, bw, ctx->gemm_slots, b.ops, md.wt_min, md.wt_max, md.band_w);
+    b.extent = handle_plan(s, bw, s->plan);
     if (s->sweep_band) {
         b.sweep_kb = band_sweep_blocks(bw);
         if (s->d_jobs) {
@@ -1476,6 +1482,7 @@ extern "C" int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw) {
             if (e == hipSuccess) e = hipMemcpy(b.d_jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice);
             if (e != hipSuccess) {
                 (void)b.clear(s->n);
+                s->plan.clear();
                 return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_chol_set_bandwidth: %s", hipGetErrorString(e));
             }
             b.njobs = (int32_t)jobs.size();
@@ -1530,15 +1537,7 @@ extern "C" int32_t madqp_chol_set_packed(madqp_chol* s, int32_t on) {
     return MADQP_OK;
 }
 
-// Width (multiple of 128, 768..2560; up to 2048: +5 ms per iteration at C-main) of the next outer panel: the wide update GEMM runs
-// (rows/128) x (W/128) tiles of equal cost on `slots` resident workgroups, so W is chosen to
-// make the last round of tiles as full as possible (tail quantisation is the main loss of a
-// left-looking factorisation; 8 fixed tile columns leave the last round 5-50 % full).
-static int64_t outer_panel_width(int64_t rows, bool has_update, int64_t slots) {
-    // (the rule itself lives with the band schedule, which falls back on it: band_plan.inc)
-    return plan_outer_width(rows, has_update, slots, chol_modes().wt_min, chol_modes().wt_max);
-}
-static_assert(BAND_NB == NB && BAND_NBO == NBO, "band_plan.inc plans in this file's blocks");
+static_assert(BAND_NB == NB && BAND_NBO == NBO, "chol_plan.inc plans in this file's blocks");
 
 // What a factorisation works on: one matrix, or B equally sized ones at fixed strides (the batch part; every launch
 // then covers all problems, grid.y / grid.x = problem, and leaves those with skip[b] != 0 alone).
@@ -1568,30 +1567,24 @@ static int32_t target_gemm(const CholTarget& t, const GemmArgs& g, int cls, int6
     return madqp_gemm_tn(t.ctx, g, cls, nullptr, 0, &bt);
 }
 
-static int32_t panel_update(const CholTarget& t, int64_t row0, int64_t k0, int64_t width, int64_t kend = -1,
-                            double alpha = -1.0, int64_t rows = -1) {
-    // C[row0:n, row0:row0+width] += alpha L[row0:n, k0:kend] * L[row0:row0+width, k0:kend]'   (kend = row0
-    // unless given: the distributed factorisation applies one received panel at a time; alpha = +1: the
-    // columns of the positive block applied to the negative block of a quasi-definite matrix)
-    // rows >= 0 (band schedule): the rows row0 .. row0+rows-1 only -- whole 128-row tiles, or up to n
-    if (kend < 0) kend = row0;
+static int32_t panel_update(const CholTarget& t, const CholOp& o) {  // an UPDATE of the plan (chol_plan.inc)
     GemmArgs g{};
-    g.X = t.A + row0 + k0 * t.lda;
+    g.X = t.A + o.row0 + o.k0 * t.lda;
     g.ldx = t.lda;
     g.Y = g.X;
     g.ldy = t.lda;
-    g.C = t.A + row0 + row0 * t.lda;
+    g.C = t.A + o.row0 + o.row0 * t.lda;
     g.ldc = t.lda;
     g.Cin = g.C;
     g.ldcin = t.lda;
-    g.alpha = alpha;
+    g.alpha = (double)o.sign;
     g.beta = 1.0;
-    g.M = rows >= 0 ? rows : t.n - row0;
-    g.N = width;
-    g.K = kend - k0;
+    g.M = o.rows;
+    g.N = o.width;
+    g.K = o.kend - o.k0;
     if (t.padded()) {
-        g.Mread = rows >= 0 ? (rows + NB - 1) / NB * NB : t.npad() - row0;
-        g.Nread = std::min<int64_t>(t.npad() - row0, (width + NB - 1) / NB * NB);
+        g.Mread = (o.rows + NB - 1) / NB * NB;
+        g.Nread = std::min<int64_t>(t.npad() - o.row0, (o.width + NB - 1) / NB * NB);
     }
     g.diag_off = 0;
     g.lower_only = 1;
@@ -1637,11 +1630,11 @@ int32_t madqp_chol_panel_solve(madqp_ctx* ctx, double* X, int64_t ldx, int64_t r
     return MADQP_OK;
 }
 
-// One 128-column block whose entries already carry every update from the columns to its left:
-// factor the diagonal block (a batched target: and invert it), then L[below, jb] = C[below, jb] L_jj^-T.
-// rows_below >= 0 (band schedule): the panel solve covers that many rows only -- whole 128-row tiles, or up to n.
-static int32_t factor_block(const CholTarget& t, int64_t jb, int64_t w, int64_t rows_below = -1) {
+// A BLOCK of the plan: one 128-column block whose entries already carry every update from the columns to its left --
+// factor the diagonal block (a batched target: and invert it), then L[below, jb] = C[below, jb] L_jj^-T for o.rows rows.
+static int32_t factor_block(const CholTarget& t, const CholOp& o) {
     madqp_ctx* ctx = t.ctx;
+    const int64_t jb = o.row0, w = o.width, rows = o.rows;
     double* Ajj = t.A + jb + jb * t.lda;
     double* Wcm = t.winv + (jb / NB) * WBLK;
     {
@@ -1652,24 +1645,17 @@ static int32_t factor_block(const CholTarget& t, int64_t jb, int64_t w, int64_t 
                            Wcm + NB * NB, t.info, (int32_t)jb, bt);
         LAUNCH_CHECK(ctx);
     }
-    // the rows below the block
-    const int64_t rows = rows_below >= 0 ? rows_below : t.n - jb - w;
-    const int64_t rows_pad = rows_below >= 0 ? (rows + NB - 1) / NB * NB : t.npad() - jb - w;
-    return madqp_chol_panel_solve(ctx, Ajj + w, t.lda, rows, t.padded() ? rows_pad : rows, Ajj, t.lda, Wcm, w,
+    return madqp_chol_panel_solve(ctx, Ajj + w, t.lda, rows, t.padded() ? (rows + NB - 1) / NB * NB : rows, Ajj, t.lda, Wcm, w,
                                   t.batched ? &t : nullptr);
 }
 
-// Recursive left-looking factorisation of the columns [j0, j0+w), which already carry the updates
-// of all columns < j0: factor the first half, apply it to the second half with ONE wide GEMM
-// (N = K = w/2), recurse.  Compared with a flat loop over 128-column blocks (N = 128, K up to
-// w - 128) this moves the in-panel flops into well-filled launches; only the leaves are narrow.
-static int32_t factor_range(const CholTarget& t, int64_t j0, int64_t w) {
-    if (w <= NB) return factor_block(t, j0, w);
-    const int64_t h = ((w + NB - 1) / NB + 1) / 2 * NB;  // first half, in whole blocks
-    int32_t r = factor_range(t, j0, h);
-    if (r) return r;
-    if ((r = panel_update(t, j0 + h, j0, w - h))) return r;
-    return factor_range(t, j0 + h, w - h);
+// The executor of every left-looking schedule: the operations of a plan (chol_plan.inc) in their order.
+static int32_t run_ops(const CholTarget& t, const std::vector<CholOp>& ops) {
+    for (const CholOp& o : ops) {
+        const int32_t r = o.kind == CHOL_UPDATE ? panel_update(t, o) : factor_block(t, o);
+        if (r) return r;
+    }
+    return MADQP_OK;
 }
 // the one matrix of a handle as a target
 static CholTarget chol_target(madqp_chol* s, double* A, int64_t lda) {
@@ -1782,15 +1768,6 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
     const int64_t n = s->n;
     HIP_TRY(ctx, hipMemsetAsync(s->d_info, 0, sizeof(int32_t), ctx->stream));
     s->upper_ok = false;
-    if (s->band.bw >= 0) {  // band schedule, every n: the operations of band_plan.inc in their order, then the sweep images
-        const CholTarget t = chol_target(s, A, lda);
-        for (const BandOp& o : s->band.ops) {
-            const int32_t r = o.kind == BAND_UPDATE ? panel_update(t, o.row0, o.k0, o.width, o.kend, -1.0, o.rows)
-                                                    : factor_block(t, o.row0, o.width, o.rows);
-            if (r) return r;
-        }
-        return sweep_images(s, A, lda, 0, n);
-    }
     // mid-size matrices: right-looking, two launches per 128-column block (chol_mid_step_kernel)
     // (measured on bench.py, m = 0.4 n, ms per iteration against the left-looking schedule: 3.34 / 3.90 at n = 3 000,
     // 6.37 / 7.51 at 5 000, 13.7 / 15.1 at 8 000, 22.7 / 23.2 at 10 000, 34.4 / 33.0 at 12 000 -- every step rewrites
@@ -1798,32 +1775,15 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
     // (round 5, with the backward sweep on U = L' behind this path -- ms per iteration, this path / left-looking: 19.1 / 21.0 at
     // n = 10 000, 23.7 / 25.4 at 11 000, 29.2 / 30.5 at 12 000, 35.5 / 36.4 at 13 000, 42.8 / 42.6 at 14 000, 60.8 / 58.1 at 16 000)
     // (the plan is built before anything of the schedule is queued; without one -- no memory for it, MADQP_CHOL_MID_MAX beyond
-    // 255 blocks, fewer than 4 GEMM slots -- the left-looking driver below serves every order)
+    // 255 blocks, fewer than 4 GEMM slots -- the left-looking schedule below serves every order, as it does under a bandwidth)
     const CholModes& md = chol_modes();
-    if (n <= md.mid_max && n > NB && s->npos == n && lda >= (n + NB - 1) / NB * NB && lda % 2 == 0 && (((uintptr_t)A) & 15) == 0 &&
+    if (s->band.bw < 0 && n <= md.mid_max && n > NB && s->npos == n && lda >= (n + NB - 1) / NB * NB && lda % 2 == 0 && (((uintptr_t)A) & 15) == 0 &&
         mid_plan_build(s, (int)((n + NB - 1) / NB), md.mid_cap > 0 ? md.mid_cap : ctx->gemm_slots / 2 - 1))
         return factor_mid(s, A, lda);
-    // Quasi-definite mode (npos < n): A = [P, .; B, -Q] with P, Q positive definite and Q's block STORED AS +Q.
-    // A = L diag(I, -I) L' with L = [L11, 0; W, L22], W = B L11^-T, L22 L22' = Q + W W': the same left-looking
-    // sweep, except that an outer panel of the second block receives the columns of the first with a plus sign
-    // (and never straddles the boundary).  No pivoting: stable for quasi-definite matrices.
-    const CholTarget t = chol_target(s, A, lda);
-    const int64_t npos = s->npos;
-    int64_t W = 0;
-    for (int64_t J0 = 0; J0 < n; J0 += W) {
-        W = std::min<int64_t>(outer_panel_width(n - J0, J0 > 0, ctx->gemm_slots), n - J0);
-        if (J0 < npos && J0 + W > npos) W = npos - J0;
-        int32_t r = MADQP_OK;
-        if (J0 > 0 && J0 < npos) {
-            r = panel_update(t, J0, 0, W);
-        } else if (J0 > 0) {
-            if (npos > 0) r = panel_update(t, J0, 0, W, npos, 1.0);
-            if (!r && J0 > npos) r = panel_update(t, J0, npos, W);
-        }
-        if (r) return r;
-        r = factor_range(t, J0, W);
-        if (r) return r;
-    }
+    // left-looking: the handle's plan for its (bandwidth, signature), built here unless it stands (host only)
+    if (s->plan.empty()) handle_plan(s, s->band.bw, s->plan);
+    const int32_t r = run_ops(chol_target(s, A, lda), s->plan);
+    if (r) return r;
     return sweep_images(s, A, lda, 0, n);
 }
 
@@ -1879,7 +1839,7 @@ void madqp_chol_factor_result(madqp_chol* s, int32_t info) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// The same recursive factorisation for a batch of B equally sized matrices at fixed strides (small
+// The halving of the whole matrix (chol_plan_range) for a batch of B equally sized matrices at fixed strides (small
 // QPs, batch.hip): every launch covers all problems (grid.y / grid.x = problem), problems with
 // skip[b] != 0 are left alone.  winv: B x nblk x WBLK, info: B ints.
 // internal (batch.hip): asynchronous; info[b] = 0 or the first failing column of problem b (1-based)
@@ -1891,7 +1851,9 @@ int32_t madqp_chol_factor_batched(madqp_ctx* ctx, double* A, int64_t lda, int64_
     HIP_TRY(ctx, hipMemsetAsync(info, 0, (size_t)B * sizeof(int32_t), ctx->stream));
     // (the diagonal kernel factors and inverts: the images are what the batched sweeps multiply with)
     const CholTarget t{ctx, A, lda, n, winv, info, true, list ? slots : B, sA, sW, list ? nullptr : skip, list, count};
-    return factor_range(t, 0, n);
+    std::vector<CholOp> ops;
+    chol_plan_range(n, 0, n, ops);
+    return run_ops(t, ops);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1927,7 +1889,9 @@ extern "C" int32_t madqp_chol_factor_begin(madqp_chol* s, double* A, int64_t lda
 extern "C" int32_t madqp_chol_factor_panel(madqp_chol* s, int64_t j0, int64_t w) {
     if (!s) return MADQP_ERR_ARG;
     ARG_TRY(s->ctx, panel_ok(s, j0, w) && s->band.bw < 0);
-    const int32_t r = factor_range(chol_target(s, s->A, s->lda), j0, w);
+    std::vector<CholOp> ops;
+    chol_plan_range(s->n, j0, w, ops);
+    const int32_t r = run_ops(chol_target(s, s->A, s->lda), ops);
     return r ? r : sweep_images(s, s->A, s->lda, j0, w);  // (the caller packs / reads the images of this panel next)
 }
 

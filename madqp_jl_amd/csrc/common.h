@@ -295,7 +295,6 @@ int32_t madqp_trsv_tile(madqp_ctx* ctx, int32_t trans, const double* L, int64_t 
 struct madqp_chol_band {
     int64_t bw = -1;      // half-bandwidth (-1: none, the dense schedules and sweeps)
     int64_t extent = 0;   // of the plan: the largest i - j the factorisation touches; n - 1 without a band
-    std::vector<struct BandOp> ops;  // the plan
     bool packed = false;  // packed band storage: the lda of a factorisation is the packed leading dimension (>= extent)
     // the sweeps under the band (MADQP_SWEEP_BAND): blocks a block row reads left of its diagonal block (-1: the dense
     // sweeps), and the band's own job list where the dense sweeps have one
@@ -316,6 +315,8 @@ struct madqp_chol {
     int32_t sweep_chunk = 0, sweep_maxc = 0, sweep_njobs = 0;
     bool sweep_band = false;  // MADQP_SWEEP_BAND of this handle: under a bandwidth the sweeps stay inside the band
     madqp_chol_band band;
+    // the left-looking plan for the current (bandwidth, npos) (chol_plan.inc; chol.hip: handle_plan); empty: not built, or none needed yet
+    std::vector<struct CholOp> plan;
     int32_t* d_info = nullptr;
     double* A = nullptr;  // last factored matrix (borrowed)
     int64_t lda = 0;

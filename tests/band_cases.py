@@ -24,7 +24,7 @@ def band_lib():
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "csrc_band")], stdout=subprocess.DEVNULL)
         _lib = C.CDLL(os.path.join(ROOT, "tests", "_build", "libmadqp_band.so"))
         i64, i32, vp = C.c_int64, C.c_int32, C.c_void_p
-        for name, args in (("band_plan_rows", [i64, i64, i64, i64, vp, i64, vp]), ("band_dense_outer_width", [i64, i64, i64]),
+        for name, args in (("band_plan_rows", [i64, i64, i64, i64, i64, vp, i64, vp]), ("band_dense_outer_width", [i64, i64, i64]),
                            ("band_sweep_blocks_c", [i64]), ("band_sweep_reach_c", [i64, i64]),
                            ("band_sweep_jobs_c", [i64, i64, i64, vp, i64, vp]),
                            ("band_packed_layout_c", [i64, i64, i64, i64, vp]), ("band_packed_default_pad_c", [])):
@@ -32,18 +32,32 @@ def band_lib():
             getattr(_lib, name).argtypes = args
         _lib.band_sweep_range_c.restype = None
         _lib.band_sweep_range_c.argtypes = [i32, i32, i32, i32, vp]
+        _lib.chol_range_rows.restype = None
+        _lib.chol_range_rows.argtypes = [i64, i64, i64, vp, i64, vp]
     return _lib
 
 
-def plan(n, bw, slots=SLOTS, force_wt=0):
-    """(operations as rows (kind, row0, rows, k0, kend, width), extent)"""
-    lib = band_lib()
+def _plan_rows(n, fill):
     cap = 4 * (n // NB + 2) + 16
-    rows = np.zeros((cap, 6), dtype=np.int64)
+    rows = np.zeros((cap, 7), dtype=np.int64)
     cnt = C.c_int64(0)
-    extent = lib.band_plan_rows(n, bw, slots, force_wt, rows.ctypes.data, cap, C.byref(cnt))
+    out = fill(rows.ctypes.data, cap, C.byref(cnt))
     assert 0 < cnt.value <= cap
-    return rows[: cnt.value], int(extent)
+    return rows[: cnt.value], out
+
+
+def plan(n, bw, slots=SLOTS, force_wt=0, npos=None):
+    """(operations as rows (kind, row0, rows, k0, kend, width, sign), extent); npos: the signature, None for positive
+    definite"""
+    lib = band_lib()
+    rows, extent = _plan_rows(n, lambda *out: lib.band_plan_rows(n, bw, n if npos is None else npos, slots, force_wt, *out))
+    return rows, int(extent)
+
+
+def range_plan(n, j0, w):
+    """the operations of the bare halving of the columns [j0, j0 + w) of an order-n matrix, rows as above"""
+    lib = band_lib()
+    return _plan_rows(n, lambda *out: lib.chol_range_rows(n, j0, w, *out))[0]
 
 
 def band_factor(n, bw, seed=None):

@@ -112,7 +112,7 @@ def lower_only(K, lda):
 # Positive definite table: order -> planted columns (0-based; the report is c + 1).
 # The 2500 row: the left-looking driver's first outer panel is 1024 columns wide and its second one, by the library's own
 # rule (second_panel_end; tests/test_chol_cases.py asserts it), takes all the 1476 columns that remain -- so "the last column
-# of the second outer panel" is 2499 and no column comes after it.  factor_range halves that panel at 1024 + 768: 1791 and
+# of the second outer panel" is 2499 and no column comes after it.  The plan halves that panel at 1024 + 768: 1791 and
 # 1792 stand for the edge inside it.
 FIRST_PANEL = 1024
 PD_TABLE = {
@@ -121,7 +121,7 @@ PD_TABLE = {
     128: (0, 127),
     129: (127, 128),  # a last block of one column
     300: (0, 16, 127, 128, 255, 256, 299),
-    1100: (0, 511, 512, 1023, 1024, 1099),  # first halving of factor_range, the first outer panel, the ragged last block
+    1100: (0, 511, 512, 1023, 1024, 1099),  # first halving of the first outer panel, its end, the ragged last block
     2500: (1023, 1024, 1791, 1792, 2499),
 }
 TWO_FAILURES = {300: (16, 256), 1100: (512, 1099), 2500: (1024, 2499)}  # the report is the first of the two
@@ -135,7 +135,7 @@ NAN_ORDERS = {17: (3, 13), 300: (40, 126), 1100: (600, 1022)}  # order -> c: one
 
 
 def second_panel_end(n=2500):
-    """first column past the second outer panel of chol_factor_enqueue's left-looking loop at order n"""
+    """first column past the second outer panel of the left-looking plan (chol_plan.inc) at order n"""
     from band_cases import SLOTS, band_lib
 
     lib = band_lib()
@@ -144,7 +144,7 @@ def second_panel_end(n=2500):
 
 
 def first_half(w):
-    """columns of the first half of a w-column range in factor_range (chol.hip): whole blocks, the larger half first"""
+    """columns of the first half of a w-column range in the plan's halving (chol_plan.inc): whole blocks, the larger half first"""
     return ((w + NB - 1) // NB + 1) // 2 * NB
 
 

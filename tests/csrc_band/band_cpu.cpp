@@ -1,23 +1,33 @@
-// Test infrastructure: madqp_jl_amd/csrc/band_plan.inc behind C entry points -- the schedule of the band-limited
-// factorisation, the job lists of the sweeps under a band with the decode of a job that the kernels compile, and the
-// layout of packed band storage -- so that the tests (tests/band_cases.py) can check and execute them in numpy without a GPU.
+// Test infrastructure: madqp_jl_amd/csrc/band_plan.inc behind C entry points -- the schedule of the left-looking
+// factorisations (chol_plan.inc, which it includes), the job lists of the sweeps under a band with the decode of a job
+// that the kernels compile, and the layout of packed band storage -- so that the tests (tests/band_cases.py) can check and
+// execute them in numpy without a GPU.
 #include "../../madqp_jl_amd/csrc/band_plan.inc"
 
-// Plans (n, bw) on `slots` workgroups (force_wt > 0: the outer panel width in blocks wherever the band limits it) and
-// writes up to max_rows rows (kind, row0, rows, k0, kend, width) to out; *nrows = operations in all; returns the extent.
-extern "C" int64_t band_plan_rows(int64_t n, int64_t bw, int64_t slots, int64_t force_wt, int64_t* out, int64_t max_rows,
-                                  int64_t* nrows) {
-    std::vector<BandOp> ops;
-    const int64_t extent = band_plan(n, bw, slots, ops, 6, 20, force_wt);
+static void plan_rows(const std::vector<CholOp>& ops, int64_t* out, int64_t max_rows, int64_t* nrows) {
     *nrows = (int64_t)ops.size();
     for (int64_t i = 0; i < *nrows && i < max_rows; ++i) {
-        const BandOp& o = ops[i];
-        int64_t* row = out + 6 * i;
-        row[0] = o.kind, row[1] = o.row0, row[2] = o.rows, row[3] = o.k0, row[4] = o.kend, row[5] = o.width;
+        const CholOp& o = ops[i];
+        int64_t* row = out + 7 * i;
+        row[0] = o.kind, row[1] = o.row0, row[2] = o.rows, row[3] = o.k0, row[4] = o.kend, row[5] = o.width, row[6] = o.sign;
     }
+}
+// Plans (n, bw, npos) on `slots` workgroups (force_wt > 0: the outer panel width in blocks wherever the band limits it) and
+// writes up to max_rows rows (kind, row0, rows, k0, kend, width, sign) to out; *nrows = operations in all; returns the extent.
+extern "C" int64_t band_plan_rows(int64_t n, int64_t bw, int64_t npos, int64_t slots, int64_t force_wt, int64_t* out,
+                                  int64_t max_rows, int64_t* nrows) {
+    std::vector<CholOp> ops;
+    const int64_t extent = chol_plan(n, bw, npos, slots, ops, 6, 20, force_wt);
+    plan_rows(ops, out, max_rows, nrows);
     return extent;
 }
-// the dense schedule's outer panel (chol.hip: outer_panel_width with the default MADQP_CHOL_WMIN / WMAX)
+// the bare halving of the columns [j0, j0 + w) of an order-n matrix (chol_plan_range), rows as above
+extern "C" void chol_range_rows(int64_t n, int64_t j0, int64_t w, int64_t* out, int64_t max_rows, int64_t* nrows) {
+    std::vector<CholOp> ops;
+    chol_plan_range(n, j0, w, ops);
+    plan_rows(ops, out, max_rows, nrows);
+}
+// the outer panel where no band limits it (plan_outer_width with the default MADQP_CHOL_WMIN / WMAX)
 extern "C" int64_t band_dense_outer_width(int64_t rows, int64_t has_update, int64_t slots) {
     return plan_outer_width(rows, has_update != 0, slots, 6, 20);
 }

@@ -41,7 +41,7 @@ def reference(n, bw):
 def execute(ops, W):
     """The operations of the plan in place on W, the packed buffer seen as a column-major matrix: what
     tests/test_band_plan.py does on a dense copy, with the same masks on every store."""
-    for kind, row0, rows, k0, kend, width in ops:
+    for kind, row0, rows, k0, kend, width, _ in ops:  # (a band's updates all subtract)
         if kind == UPDATE:
             X = W[row0: row0 + rows, k0: kend]
             Y = W[row0: row0 + width, k0: kend]

@@ -1,7 +1,9 @@
-"""CPU: the schedule of the band-limited Cholesky (madqp_jl_amd/csrc/band_plan.inc, compiled for the CPU by
-tests/csrc_band).  The plan is executed in numpy float64 on band matrices and held to scipy; its ranges are checked against
-the band, the extent it reports and the dense schedule; ``kkt.pattern_bandwidth`` is held to dense numpy; the refusals of
-``kkt_bandwidth`` happen before any device call.  The kernels that run the plan are held in tests/test_gpu_band.py."""
+"""CPU: the schedule of the left-looking Cholesky (madqp_jl_amd/csrc/chol_plan.inc, compiled for the CPU by
+tests/csrc_band) -- band-limited, dense, quasi-definite, and the bare halving of a column range.  The plan is executed in
+numpy float64 on band and quasi-definite matrices and held to LAPACK; its ranges are checked against the band and the extent
+it reports; the dense, quasi-definite and range plans are held to restatements of their rules in Python;
+``kkt.pattern_bandwidth`` is held to dense numpy; the refusals of ``kkt_bandwidth`` happen before any device call.  The
+kernels that run the plan are held in tests/test_gpu_band.py."""
 import math
 import os
 import subprocess
@@ -16,12 +18,19 @@ import torch
 import madqp_jl_amd as M
 from madqp_jl_amd import preprocess as P
 from madqp_jl_amd.kkt import pattern_bandwidth
-from band_cases import (BLOCK, NB, ROOT, SLOTS, UPDATE, band_spd, banded_qp, band_lib, dense_pattern_bandwidth, plan)
+import chol_cases as cc
+from band_cases import (BLOCK, NB, ROOT, SLOTS, UPDATE, band_spd, banded_qp, band_lib, dense_pattern_bandwidth, plan, range_plan)
 
 CPU = torch.device("cpu")
 NS = (1, 128, 129, 500, 1537, 2100)
 SHAPES = [(n, bw) for n in NS for bw in sorted({0, 1, 127, 128, 129, 300, 640, n - 1}) if bw < n]
 RANGE_ONLY = [(90000, 600), (22500, 300)]
+# (npos, nneg): an empty positive block; panels cut at npos (768 / 800, 1280 / 2900); a first panel that ends at npos; a
+# short cut panel (1152); a negative block of two outer panels, whose second receives the + and the - update (2561 is the
+# smallest nneg with one at 512 slots)
+SIGNATURES = [(0, 300), (128, 50), (256, 300), (768, 800), (1024, 129), (1152, 1300), (128, 2561), (1280, 2900), (2304, 1500)]
+SIGNATURES_EXECUTED = [(128, 50), (256, 300), (768, 800), (128, 2561)]
+RANGES = [(1, 0, 1), (128, 0, 128), (129, 0, 129), (640, 0, 640), (1000, 0, 1000), (900, 256, 644), (2100, 1024, 1076)]  # (n, j0, w)
 
 
 def execute(ops, K, extent):
@@ -29,13 +38,13 @@ def execute(ops, K, extent):
     n = K.shape[0]
     i, j = np.indices((n, n))
     W = np.where((i >= j) & (i - j <= extent), K, np.nan)
-    for kind, row0, rows, k0, kend, width in ops:
+    for kind, row0, rows, k0, kend, width, sign in ops:
         if kind == UPDATE:
             X = W[row0: row0 + rows, k0: kend]
             Y = W[row0: row0 + width, k0: kend]
             low = i[row0: row0 + rows, row0: row0 + width] >= j[row0: row0 + rows, row0: row0 + width]
             C = W[row0: row0 + rows, row0: row0 + width]
-            C[low] -= (X @ Y.T)[low]
+            C[low] += sign * (X @ Y.T)[low]
         else:
             jb, w = row0, width
             D = np.tril(W[jb: jb + w, jb: jb + w])
@@ -51,17 +60,39 @@ def execute(ops, K, extent):
 def test_executed_plan_factors_the_band_matrix(n, bw):
     K = band_spd(n, bw)
     ops, extent = plan(n, bw)
-    W = execute(ops, K, extent)
+    L = executed_factor(ops, K, extent, K, np.ones(n), sla.cholesky(K, lower=True))
+    i, j = np.indices((n, n))
+    assert np.all(L[i - j > bw] == 0.0), "the factor stays inside the band: stored zeros stay zeros"
+
+
+def executed_factor(ops, stored, extent, M, signs, Lref):
+    """L of the plan executed on `stored`, held to M = L diag(signs) L' and to Lref"""
+    n = M.shape[0]
+    W = execute(ops, stored, extent)
     i, j = np.indices((n, n))
     outside = (i < j) | (i - j > extent)
     assert np.all(np.isnan(W[outside])), "nothing beyond the extent (or above the diagonal) is written"
     assert not np.any(np.isnan(W[~outside])), "nothing beyond the extent is read"
     L = np.where(outside, 0.0, W)
-    Lref = sla.cholesky(K, lower=True)
-    rel = np.linalg.norm(L @ L.T - K) / np.linalg.norm(K)
+    rel = np.linalg.norm((L * signs) @ L.T - M) / np.linalg.norm(M)
     assert rel < 1e-14 * max(1, math.sqrt(n)), rel
     assert np.max(np.abs(L - Lref)) / np.max(np.abs(Lref)) < 1e-11
-    assert np.all(L[i - j > bw] == 0.0), "the factor stays inside the band: stored zeros stay zeros"
+    return L
+
+
+@pytest.mark.parametrize("npos,nneg", SIGNATURES_EXECUTED)
+def test_executed_signature_plan_factors_the_quasidefinite_matrix(npos, nneg):
+    """[P, B'; B, -Q] = L diag(I, -I) L'; the reference by blocks with LAPACK: L11 = chol(P), W = B L11^-T,
+    L22 = chol(Q + W W')."""
+    n = npos + nneg
+    stored, M = cc.quasidefinite(npos, nneg, n)
+    L11 = sla.cholesky(stored[:npos, :npos], lower=True)
+    Wm = sla.solve_triangular(L11, stored[npos:, :npos].T, lower=True).T
+    L22 = sla.cholesky(stored[npos:, npos:] + Wm @ Wm.T, lower=True)
+    Lref = np.block([[L11, np.zeros((npos, nneg))], [Wm, L22]])
+    ops, extent = plan(n, n - 1, npos=npos)
+    assert extent == n - 1
+    executed_factor(ops, stored, extent, M, np.where(np.arange(n) < npos, 1.0, -1.0), Lref)
 
 
 def check_ranges(n, bw, ops, extent):
@@ -71,8 +102,8 @@ def check_ranges(n, bw, ops, extent):
     applied = {}  # tile (I, J) -> k-ranges in the order applied
     done = 0
     seen_extent = 0
-    for kind, row0, rows, k0, kend, width in ops:
-        assert row0 % NB == 0 and 0 <= rows and row0 + rows <= n and width >= 1
+    for kind, row0, rows, k0, kend, width, sign in ops:
+        assert row0 % NB == 0 and 0 <= rows and row0 + rows <= n and width >= 1 and sign == -1
         assert rows % NB == 0 or row0 + (width if kind == BLOCK else 0) + rows == n, "whole tiles, or clamped at n"
         if kind == UPDATE:
             assert k0 < kend == row0 <= done and k0 % NB == 0 and k0 >= max(0, (row0 - bw) // NB * NB)
@@ -117,26 +148,29 @@ def test_ranges_cover_the_band_once(n, bw):
         check_ranges(n, bw, ops, extent)
 
 
+def halving(n, j0, w, ops):
+    """The recursive halving of the columns [j0, j0 + w) of a dense matrix of order n: the first half in whole blocks, the
+    larger half first, one update of the second half with it."""
+    if w <= NB:
+        ops.append((BLOCK, j0, n - j0 - w, 0, 0, w, -1))
+        return
+    h = ((w + NB - 1) // NB + 1) // 2 * NB
+    halving(n, j0, h, ops)
+    ops.append((UPDATE, j0 + h, n - j0 - h, j0, j0 + h, w - h, -1))
+    halving(n, j0 + h, w - h, ops)
+
+
 def dense_schedule(n, slots=SLOTS):
-    """chol_factor_enqueue's left-looking schedule and factor_range's halving, as operations."""
+    """What the dense left-looking schedule has to be, written down independently of chol_plan.inc: outer panels of the
+    library's width rule, each updated with all columns to its left and then halved."""
     lib = band_lib()
     ops = []
-
-    def rng(j0, w):
-        if w <= NB:
-            ops.append((BLOCK, j0, n - j0 - w, 0, 0, w))
-            return
-        h = ((w + NB - 1) // NB + 1) // 2 * NB
-        rng(j0, h)
-        ops.append((UPDATE, j0 + h, n - j0 - h, j0, j0 + h, w - h))
-        rng(j0 + h, w - h)
-
     J0 = 0
     while J0 < n:
         W = min(lib.band_dense_outer_width(n - J0, 1 if J0 > 0 else 0, slots), n - J0)
         if J0 > 0:
-            ops.append((UPDATE, J0, n - J0, 0, J0, W))
-        rng(J0, W)
+            ops.append((UPDATE, J0, n - J0, 0, J0, W, -1))
+        halving(n, J0, W, ops)
         J0 += W
     return np.array(ops, dtype=np.int64)
 
@@ -148,13 +182,56 @@ def test_full_bandwidth_is_the_dense_schedule(n):
     assert np.array_equal(ops, dense_schedule(n))
 
 
+def quasidefinite_schedule(npos, nneg, slots=SLOTS):
+    """What the schedule under a signature has to be: an outer panel never straddles npos; one that starts in [1, npos)
+    receives the columns [0, J0); one at or beyond npos receives +[0, npos) (npos > 0) and then -[npos, J0) (J0 > npos)."""
+    lib = band_lib()
+    n = npos + nneg
+    ops = []
+    J0 = 0
+    while J0 < n:
+        W = min(lib.band_dense_outer_width(n - J0, 1 if J0 > 0 else 0, slots), n - J0)
+        if J0 < npos < J0 + W:
+            W = npos - J0
+        if 0 < J0 < npos:
+            ops.append((UPDATE, J0, n - J0, 0, J0, W, -1))
+        elif J0 > 0:
+            if npos > 0:
+                ops.append((UPDATE, J0, n - J0, 0, npos, W, +1))
+            if J0 > npos:
+                ops.append((UPDATE, J0, n - J0, npos, J0, W, -1))
+        halving(n, J0, W, ops)
+        J0 += W
+    return np.array(ops, dtype=np.int64)
+
+
+@pytest.mark.parametrize("npos,nneg", SIGNATURES)
+def test_signature_plan_is_the_quasidefinite_schedule(npos, nneg):
+    n = npos + nneg
+    ops, extent = plan(n, n - 1, npos=npos)
+    assert extent == n - 1
+    expected = quasidefinite_schedule(npos, nneg)
+    assert np.array_equal(ops, expected)
+    if (npos, nneg) in ((128, 2561), (1280, 2900)):  # the shapes chosen for it: a panel with both updates
+        plus = expected[(expected[:, 0] == UPDATE) & (expected[:, 6] == 1)]
+        assert any(np.any((expected[:, 0] == UPDATE) & (expected[:, 6] == -1) & (expected[:, 1] == r) & (expected[:, 4] == r)
+                          & (expected[:, 3] == npos)) for r in plus[:, 1])
+
+
+@pytest.mark.parametrize("n,j0,w", RANGES)
+def test_range_plan_is_the_halving(n, j0, w):
+    expected = []
+    halving(n, j0, w, expected)
+    assert np.array_equal(range_plan(n, j0, w), np.array(expected, dtype=np.int64))
+
+
 def test_narrow_band_panels():
     """(2100, 200): three outer panels, the third starts its k range at 1280 -- below it a wrong k0 would not show."""
     ops, _ = plan(2100, 200)
     outer = [tuple(o) for o in ops if o[0] == UPDATE and o[1] in (768, 1536) and o[5] > 384]
-    assert outer == [(UPDATE, 768, 1024, 512, 768, 768), (UPDATE, 1536, 564, 1280, 1536, 564)]
+    assert outer == [(UPDATE, 768, 1024, 512, 768, 768, -1), (UPDATE, 1536, 564, 1280, 1536, 564, -1)]
     ops, extent = plan(1600, 80)  # boundary_control_qp(40), normal equations
-    assert [tuple(o[1:]) for o in ops if o[0] == UPDATE and o[5] > 384] == [(768, 832, 640, 768, 768)]
+    assert [tuple(o[1:]) for o in ops if o[0] == UPDATE and o[5] > 384] == [(768, 832, 640, 768, 768, -1)]
     assert sum(1 for o in ops if o[0] == BLOCK) == 13
 
 
@@ -240,8 +317,9 @@ def test_default_is_no_bandwidth():
 
 # ---- the plan under the sanitizers ----------------------------------------------------------------------------------------
 def test_plan_under_address_and_undefined_sanitizers():
-    """tests/csrc_band/band_plan_main.cpp: a stand-alone program (never loaded into Python) that plans the shapes above."""
+    """tests/csrc_band/band_plan_main.cpp: a stand-alone program (never loaded into Python) that plans the shapes above --
+    band, signature and range."""
     band_lib()  # (runs make)
     out = subprocess.run([os.path.join(ROOT, "tests", "_build", "band_plan_check")], capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "BAD" not in out.stdout and out.stdout.count(" ok") >= len(SHAPES) + len(RANGE_ONLY)
+    assert "BAD" not in out.stdout and out.stdout.count(" ok") >= len(SHAPES) + len(RANGE_ONLY) + len(SIGNATURES) + len(RANGES)

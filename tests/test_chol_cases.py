@@ -75,7 +75,7 @@ def test_the_table_sits_on_the_panel_edges():
     # ... and the second one takes all that remains of 2500: its last column is the matrix's, none comes after it
     assert cc.second_panel_end(2500) == 2500 and 2499 in cc.PD_TABLE[2500]
     assert cc.second_panel_end(1100) == 1100
-    # factor_range's halvings: 1024 -> 512 -> 256 -> 128 in the first panel, 1476 -> 768 + 708 in the second panel of 2500
+    # the plan's halvings: 1024 -> 512 -> 256 -> 128 in the first panel, 1476 -> 768 + 708 in the second panel of 2500
     assert [cc.first_half(w) for w in (1024, 512, 256, 2500 - 1024, 300)] == [512, 256, 128, 768, 256]
     assert {511, 512} <= set(cc.PD_TABLE[1100]) and {1024 + 768 - 1, 1024 + 768} <= set(cc.PD_TABLE[2500])
     for n, cols in cc.PD_TABLE.items():

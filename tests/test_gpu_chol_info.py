@@ -4,12 +4,12 @@ every driver and the inertia a KKT object reports; nothing crashes when it is wr
 the proof that every case is far from the border are in tests/chol_cases.py and tests/test_chol_cases.py (no GPU).
 
 How chol_factor_enqueue (chol.hip) is reached, in the order it decides:
-  band       a bandwidth is set (madqp_chol_set_bandwidth): the plan of band_plan.inc, dense or packed storage, every n;
-  mid-size   128 < n <= MADQP_CHOL_MID_MAX (13 312), no signature, lda >= ceil128(n) and even, A 16-byte aligned:
-             chol_mid_step_kernel, one step per 128-column block -- the `padded` layout;
-  left       everything else: outer panels (1024 columns first) and the halvings of factor_range -- the `unpadded`
-             layout (lda < ceil128(n): no order of the table above 128 is a multiple of 128), a signature (quasi-definite
-             mode), MADQP_CHOL_MID_MAX=0 in a process of its own, and the panel pieces (madqp_chol_factor_panel);
+  mid-size   no bandwidth, 128 < n <= MADQP_CHOL_MID_MAX (13 312), no signature, lda >= ceil128(n) and even, A 16-byte
+             aligned: chol_mid_step_kernel, one step per 128-column block -- the `padded` layout;
+  left       everything else, the handle's plan (chol_plan.inc): outer panels (1024 columns first) and their halvings -- the
+             `unpadded` layout (lda < ceil128(n): no order of the table above 128 is a multiple of 128), a signature
+             (quasi-definite mode), MADQP_CHOL_MID_MAX=0 in a process of its own, the panel pieces (madqp_chol_factor_panel),
+             and, cut down to the band, a bandwidth (madqp_chol_set_bandwidth): dense or packed storage, every n;
   one block  n <= 128 is a single launch of the diagonal kernel in either layout."""
 import functools
 import json

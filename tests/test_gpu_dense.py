@@ -433,7 +433,7 @@ def test_mid_size_schedules_factor_the_same_matrix():
 
 
 def test_left_looking_driver_at_small_orders():
-    """The left-looking driver (chol.hip: factor_range / factor_block with the block-substitution panel solve), here forced
+    """The left-looking driver (chol.hip: run_ops on the plan of chol_plan.inc, the block-substitution panel solve), here forced
     at small orders with MADQP_CHOL_MID_MAX=0.  Orders with a single trailing block, one recursion level, a ragged last
     block and more than one outer panel, at ld = ceil(n/128) 128 and -- 257 and 1000 -- at ld = n: it must give LAPACK's
     factor and solution up to rounding."""

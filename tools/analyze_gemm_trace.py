@@ -36,7 +36,7 @@ def panel_update(n, row0, k0, width, kind="upd"):
     sched.append((kind, n - row0, width, row0 - k0, tiles_lower(n - row0, width)))
 
 
-def factor_range(n, j0, w):
+def halve_range(n, j0, w):
     if w <= NB:
         if j0 + w < n:
             below = n - j0 - w
@@ -44,9 +44,9 @@ def factor_range(n, j0, w):
             sched.append(("trsm64", below, w, w, (below + 63) // 64))
         return
     h = ((w + NB - 1) // NB + 1) // 2 * NB
-    factor_range(n, j0, h)
+    halve_range(n, j0, h)
     panel_update(n, j0 + h, j0, w - h)
-    factor_range(n, j0 + h, w - h)
+    halve_range(n, j0 + h, w - h)
 
 
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 50000
@@ -55,7 +55,7 @@ while J0 < n:
     W = min(outer_w(n - J0, J0 > 0), n - J0)
     if J0 > 0:
         panel_update(n, J0, 0, W, "outer")
-    factor_range(n, J0, W)
+    halve_range(n, J0, W)
     J0 += W
 f = glob.glob(sys.argv[1])[0]
 rows = [r for r in csv.DictReader(open(f)) if "gemm_tn" in r["Kernel_Name"] or "panel_sub16" in r["Kernel_Name"]]
