@@ -25,6 +25,11 @@
 // factor_block) on a CholTarget -- one matrix (madqp_chol_factor), a batch of small matrices at fixed strides (madqp_chol_factor_batched)
 // or a panel of the multi-GPU loop (madqp_chol_factor_panel, ...); ONE panel solve of a 128-column block (madqp_chol_panel_solve), shared with the
 // mid-size schedule (factor_mid) and dist.hip; the environment is read in one place (CholModes).
+// The handle (struct madqp_chol, common.h): ONE owner of its device buffers (DevOwner: destroy is a synchronise and a delete,
+// the paths that must leave the handle usable release what they allocated), ONE way to take a matrix (adopt_matrix) and to
+// forget its factor (forget_factor: the solves refuse while there is no matrix -- the handle keeps no record of whether a
+// factorisation succeeded), ONE description of a solve's sweeps (Sweeps) and ONE launcher of their three kernel forms
+// (launch_sweep) on ONE scratch buffer, for both paths of madqp_chol_solve and for madqp_trsv_tile.
 #include <algorithm>
 #include <cstdlib>
 
@@ -1364,11 +1369,27 @@ static const CholModes& chol_modes() {  // filled once, at the first use
     return m;
 }
 
-hipError_t madqp_chol_band::clear(int64_t n) {
-    const hipError_t e = d_jobs ? hipFree(d_jobs) : hipSuccess;
-    *this = madqp_chol_band{};
-    extent = n - 1;
+// ---- the handle (struct madqp_chol: common.h) ----------------------------------------------------------------------------
+// back to "no band"; frees the band's job list, which nothing on the stream may still read
+static hipError_t band_clear(madqp_chol* s) {
+    const hipError_t e = s->mem.free_one(&s->band.d_jobs);
+    s->band = madqp_chol_band{};
+    s->band.extent = s->n - 1;
     return e;
+}
+// What every factor entry point does with its matrix: lda has to cover the storage form (the order, or the extent of packed
+// band storage), and what an earlier factorisation left beside the matrix (U) is void
+static int32_t adopt_matrix(madqp_chol* s, double* A, int64_t lda) {
+    ARG_TRY(s->ctx, A && lda >= (s->band.packed ? std::max<int64_t>(s->band.extent, 1) : s->n));
+    s->A = A;
+    s->lda = lda;
+    s->upper_ok = false;
+    return MADQP_OK;
+}
+// what is stored is no factor for the handle's new settings: the solves refuse until the next factorisation
+static void forget_factor(madqp_chol* s) {
+    s->A = nullptr;
+    s->upper_ok = false;
 }
 
 extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out) {
@@ -1376,17 +1397,12 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
     *out = nullptr;
     madqp_chol* s = new (std::nothrow) madqp_chol();
     if (!s) return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
-    s->ctx = ctx;
-    s->n = n;
-    s->npos = n;
+    s->ctx = s->mem.ctx = ctx;
+    s->n = s->npos = n;
+    s->band.extent = n - 1;
     s->many_min = SOLVE_MANY_MIN_DEFAULT;
-    (void)s->band.clear(n);  // (nothing to free yet)
     const int64_t nblk = std::max<int64_t>(1, (n + NB - 1) / NB);
-    hipError_t e = hipMalloc(&s->winv, nblk * WBLK * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(s->winv, 0, nblk * WBLK * sizeof(double));  // the kernel writes lower parts only
-    // sweeps: block rows longer than `chunk` tiles are streamed by several workgroups (SweepPlan).  tmp holds the
-    // intermediate vector (padded to whole blocks) followed by the partial-sum slots of both sweeps, so that one fill
-    // per solve resets all of them.
+    // sweeps: block rows longer than `chunk` tiles are streamed by several workgroups (SweepPlan)
     const CholModes md = chol_modes_from_env();  // (read per handle: the tests build job lists with several chunks)
     s->sweep_chunk = md.sweep_chunk;
     s->sweep_band = md.sweep_band;
@@ -1396,18 +1412,27 @@ extern "C" int32_t madqp_chol_create(madqp_ctx* ctx, int64_t n, madqp_chol** out
         s->sweep_njobs = (int32_t)jobs.size();
     }
     s->tmp_len = nblk * NB + 2 * nblk * (int64_t)s->sweep_maxc * NB;
-    if (e == hipSuccess) e = hipMalloc(&s->tmp, s->tmp_len * sizeof(double));
-    if (e == hipSuccess && !jobs.empty()) {
-        e = hipMalloc(&s->d_jobs, jobs.size() * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemcpy(s->d_jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    s->utmp_len = nblk * NB + s->tmp_len;
+    const bool with_x = nblk > 1 && nblk <= 160;  // (the orders a mid-size factorisation may leave U for)
+    const char* who = "madqp_chol_create";
+    auto hip_ok = [&](hipError_t e) {
+        return e == hipSuccess ? MADQP_OK : madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_chol_create(%lld): %s", (long long)n, hipGetErrorString(e));
+    };
+    int32_t r = s->mem.alloc(&s->winv, nblk * WBLK, who);
+    // the kernel writes lower parts only.  A blocking fill: it is complete when this call returns, whatever stream uses winv next
+    if (!r) r = hip_ok(hipMemset(s->winv, 0, nblk * WBLK * sizeof(double)));
+    double* scratch = nullptr;
+    if (!r) r = s->mem.alloc(&scratch, with_x ? s->utmp_len : s->tmp_len, who);
+    s->sweep_x = with_x ? scratch : nullptr;
+    s->sweep_y = with_x && scratch ? scratch + nblk * NB : scratch;
+    if (!r && !jobs.empty()) {
+        r = s->mem.alloc(&s->d_jobs, (int64_t)jobs.size(), who);
+        if (!r) r = hip_ok(hipMemcpy(s->d_jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    s->utmp_len = 2 * nblk * NB + 2 * nblk * (int64_t)s->sweep_maxc * NB;
-    if (e == hipSuccess && nblk > 1 && nblk <= 160) e = hipMalloc(&s->utmp, s->utmp_len * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&s->d_info, 8 * sizeof(int32_t));  // [0] info, [1..2] sweep tickets
-    if (e != hipSuccess) {
+    if (!r) r = s->mem.alloc(&s->d_info, 8, who);
+    if (r) {
         madqp_chol_destroy(s);
-        return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_chol_create(%lld): %s", (long long)n,
-                          hipGetErrorString(e));
+        return r;
     }
     *out = s;
     return MADQP_OK;
@@ -1427,24 +1452,13 @@ extern "C" int32_t madqp_chol_set_signature(madqp_chol* s, int64_t npos) {
     ARG_TRY(s->ctx, s->band.bw < 0 || npos == s->n);  // the band schedule factors positive definite matrices only
     s->npos = npos;
     s->plan.clear();  // (built again at the next left-looking factorisation)
-    s->factored = false;
     return MADQP_OK;
 }
 
 extern "C" int32_t madqp_chol_destroy(madqp_chol* s) {
     if (!s) return MADQP_OK;
     (void)hipStreamSynchronize(s->ctx->stream);
-    if (s->winv) (void)hipFree(s->winv);
-    if (s->tmp) (void)hipFree(s->tmp);
-    if (s->d_jobs) (void)hipFree(s->d_jobs);
-    (void)s->band.clear(s->n);
-    if (s->d_info) (void)hipFree(s->d_info);
-    if (s->d_mid_plan) (void)hipFree(s->d_mid_plan);
-    if (s->upper) (void)hipFree(s->upper);
-    if (s->utmp) (void)hipFree(s->utmp);
-    if (s->many_ws) (void)hipFree(s->many_ws);
-    delete[] s->mid_units;
-    delete s;
+    delete s;  // (its owner frees the device buffers)
     return MADQP_OK;
 }
 
@@ -1460,13 +1474,11 @@ extern "C" int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw) {
     madqp_ctx* ctx = s->ctx;
     ARG_TRY(ctx, bw == -1 || (bw >= 0 && bw < s->n && s->npos == s->n));
     // the form of the sweeps changes with this call and what is stored may be the factor of another schedule: a solve
-    // needs a new factorisation first (madqp_chol_solve refuses with MADQP_ERR_STATE until then)
-    s->factored = false;
-    s->A = nullptr;
-    s->upper_ok = false;
+    // needs a new factorisation first (without a matrix madqp_chol_solve refuses with MADQP_ERR_STATE)
+    forget_factor(s);
     // (the extent changes with the bandwidth and packed storage is laid out for one extent: madqp_chol_set_packed again)
     if (s->band.d_jobs) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (a solve on the stream may still read the list)
-    HIP_TRY(ctx, s->band.clear(s->n));
+    HIP_TRY(ctx, band_clear(s));
     s->plan.clear();  // (without a band: built at the next left-looking factorisation)
     if (bw < 0) return MADQP_OK;
     // the new state in a local: the handle takes it once the plan and the job list both stand, and keeps "no band" otherwise
@@ -1478,17 +1490,19 @@ extern "C" int32_t madqp_chol_set_bandwidth(madqp_chol* s, int64_t bw) {
         if (s->d_jobs) {
             std::vector<int32_t> jobs;
             band_sweep_jobs((s->n + NB - 1) / NB, b.sweep_kb, s->sweep_chunk, jobs);
-            hipError_t e = hipMalloc(&b.d_jobs, jobs.size() * sizeof(int32_t));
-            if (e == hipSuccess) e = hipMemcpy(b.d_jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                (void)b.clear(s->n);
+            const size_t before = s->mem.owned.size();
+            int32_t r = s->mem.alloc(&b.d_jobs, (int64_t)jobs.size(), "madqp_chol_set_bandwidth");
+            const hipError_t e = r ? hipSuccess : hipMemcpy(b.d_jobs, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+            if (e != hipSuccess) r = madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_chol_set_bandwidth: %s", hipGetErrorString(e));
+            if (r) {
+                s->mem.release(before);
                 s->plan.clear();
-                return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_chol_set_bandwidth: %s", hipGetErrorString(e));
+                return r;
             }
             b.njobs = (int32_t)jobs.size();
         }
     }
-    s->band = std::move(b);
+    s->band = b;
     return MADQP_OK;
 }
 
@@ -1529,10 +1543,7 @@ extern "C" int32_t madqp_chol_packed_layout(madqp_chol* s, int64_t ld_in, int64_
 extern "C" int32_t madqp_chol_set_packed(madqp_chol* s, int32_t on) {
     if (!s) return MADQP_ERR_ARG;
     ARG_TRY(s->ctx, !on || (s->band.bw >= 0 && s->band.sweep_kb >= 0 && s->npos == s->n));
-    if (s->band.packed != (on != 0)) {  // what is stored was factored in the other layout
-        s->factored = false;
-        s->A = nullptr;
-    }
+    if (s->band.packed != (on != 0)) forget_factor(s);  // what is stored was factored in the other layout
     s->band.packed = on != 0;
     return MADQP_OK;
 }
@@ -1601,15 +1612,10 @@ static int32_t sweep_images(madqp_chol* s, double* A, int64_t lda, int64_t j0, i
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }
-// kb: the band of the sweep in blocks (band_plan.inc), -1 for the whole block rows
-static void launch_sweep(bool bwd, unsigned grid, hipStream_t st, const double* L, int64_t ld, const double* winv, const double* in,
-                         double* out, int64_t n, int32_t* ctl, double* fault, int vec, const SweepPlan& plan, int kb = -1) {
-    if (bwd)
-        hipLaunchKernelGGL(trsv_bwd_sweep_kernel, dim3(grid), dim3(1024), 0, st, L, ld, winv, in, out, n, ctl, fault, vec, plan, kb);
-    else
-        hipLaunchKernelGGL(trsv_fwd_sweep_kernel<false>, dim3(grid), dim3(1024), 0, st, L, ld, winv, in, out, n, ctl, fault, vec, plan,
-                           (double*)nullptr, kb);
-}
+
+// the forward sweep's kernel, named ahead of factor_block: the compiler emits the instances of kernel templates in the order of
+// their first use, and the code object keeps the order it has always had (launch_sweep below is the one user)
+static const auto sweep_fwd_kernel = trsv_fwd_sweep_kernel<false>;
 
 // The panel solve of ONE 128-column block: X (rows x 128, leading dimension ldx; rows_read >= rows of them exist in memory)
 // <- X L^-T for the factored diagonal block L (ldl), by block substitution with the 16 x 16 diagonal inverses that the
@@ -1678,8 +1684,9 @@ static CholTarget chol_target(madqp_chol* s, double* A, int64_t lda) {
 // n = 5 000 instead of 8 of them at ~90 us), 2-4 up to 10 240, 5-6 up to 13 312.  The plan depends on (number of blocks, cap) only.
 // builds and uploads the plan of s (once; nothing is queued); false: no plan (the caller takes the left-looking driver)
 static bool mid_plan_build(madqp_chol* s, int nblk, int cap) {
-    if (s->mid_plan_state) return s->mid_plan_state > 0;
-    s->mid_plan_state = -1;
+    MidPlan& mp = s->mid;
+    if (mp.state) return mp.state > 0;
+    mp.state = -1;
     if (nblk > 255 || cap < 1) return false;
     std::vector<std::vector<MidVisit>> steps;
     std::vector<int32_t> units;
@@ -1687,32 +1694,29 @@ static bool mid_plan_build(madqp_chol* s, int nblk, int cap) {
     for (int rounds = 1; rounds <= 64 && !ok; ++rounds) ok = mid_plan_steps(nblk, rounds * cap, steps, units, cap);
     if (!ok) return false;
     std::vector<uint32_t> w;
-    s->mid_units = new (std::nothrow) int32_t[2 * nblk];
-    if (!s->mid_units) return false;
-    // every failure exit leaves the handle without a plan AND without its pieces (the left-looking driver runs next: no
-    // sticky HIP error may reach its first launch check)
-    auto give_up = [&]() {
-        (void)hipGetLastError();
-        if (s->d_mid_plan) (void)hipFree(s->d_mid_plan);
-        s->d_mid_plan = nullptr;
-        delete[] s->mid_units;
-        s->mid_units = nullptr;
-        return false;
-    };
+    std::vector<int32_t> count((size_t)nblk), first((size_t)nblk);
     for (int k = 0; k < nblk; ++k) {
-        s->mid_units[nblk + k] = (int32_t)w.size();
+        first[k] = (int32_t)w.size();
         mid_plan_units(nblk, k, steps[k], w);
-        s->mid_units[k] = (int32_t)w.size() - s->mid_units[nblk + k];
-        if (s->mid_units[k] != units[k]) return give_up();
+        count[k] = (int32_t)w.size() - first[k];
+        if (count[k] != units[k]) return false;
     }
     if (w.empty()) w.push_back(0);
-    if (hipMalloc(&s->d_mid_plan, w.size() * sizeof(uint32_t)) != hipSuccess) {
-        s->d_mid_plan = nullptr;
-        return give_up();
-    }
+    // a failure leaves the handle without a plan AND without its pieces (the left-looking driver runs next: no sticky HIP
+    // error may reach its first launch check)
+    const size_t before = s->mem.owned.size();
+    uint32_t* d_units = nullptr;
     // (synchronous, pageable source: the copy has left `w` when the call returns; once per handle)
-    if (hipMemcpy(s->d_mid_plan, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return give_up();
-    s->mid_plan_state = 1;
+    if (s->mem.alloc(&d_units, (int64_t)w.size(), "madqp_chol_factor: mid-size plan") ||
+        hipMemcpy(d_units, w.data(), w.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        s->mem.release(before);
+        return false;
+    }
+    mp.count.swap(count);
+    mp.first.swap(first);
+    mp.d_units = d_units;
+    mp.state = 1;
     return true;
 }
 
@@ -1726,15 +1730,10 @@ static int32_t factor_mid(madqp_chol* s, double* A, int64_t lda) {
     // one timer scope for the whole factorisation (80 short launches: a scope each costs 0.7 ms per factorisation
     // at n = 5 000); the scopes of the launches inside are switched off meanwhile
     ProfScope ps_all(ctx, MADQP_PROF_POTRF_GEMM);
-    struct ProfMute {
-        madqp_ctx* c;
-        decltype(c->prof) saved;
-        explicit ProfMute(madqp_ctx* ctx_) : c(ctx_), saved(ctx_->prof) { c->prof = 0; }
-        ~ProfMute() { c->prof = saved; }
-    } mute(ctx);
+    ProfMute mute(ctx);
     for (int32_t k = 0; k < nblk; ++k) {
-        hipLaunchKernelGGL(chol_mid_step_kernel, dim3((unsigned)(1 + s->mid_units[k])), dim3(MID_THREADS), 0, ctx->stream,
-                           MidArgs{A, lda, n, nblk, k, s->d_mid_plan + s->mid_units[nblk + k], s->winv, s->d_info});
+        hipLaunchKernelGGL(chol_mid_step_kernel, dim3((unsigned)(1 + s->mid.count[k])), dim3(MID_THREADS), 0, ctx->stream,
+                           MidArgs{A, lda, n, nblk, k, s->mid.d_units + s->mid.first[k], s->winv, s->d_info});
         LAUNCH_CHECK(ctx);
         // L[below, jb] = C[below, jb] L_kk^-T
         const int64_t jb = (int64_t)k * NB;
@@ -1745,12 +1744,12 @@ static int32_t factor_mid(madqp_chol* s, double* A, int64_t lda) {
     const int32_t ri = sweep_images(s, A, lda, 0, n);  // of all blocks, one launch
     if (ri) return ri;
     // U = L' for the backward sweep (trsv_fwd_sweep_kernel<true>): one pass over the factor, 37 us at n = 5 000
-    if (chol_modes().sweep_upper && s->utmp) {
-        if (!s->upper) {
-            if (hipMalloc(&s->upper, (size_t)npad_m * npad_m * sizeof(double)) != hipSuccess) {
-                (void)hipGetLastError();
-                s->upper = nullptr;
-                return MADQP_OK;  // (no room for the copy: the backward sweep on L serves)
+    if (chol_modes().sweep_upper && s->sweep_x) {
+        if (!s->upper) {  // (allocated at the first mid-size factorisation)
+            const size_t before = s->mem.owned.size();
+            if (s->mem.alloc(&s->upper, npad_m * npad_m, "madqp_chol_factor: U = L'")) {
+                s->mem.release(before);
+                return MADQP_OK;  // (no room for the copy, and no sticky HIP error: the backward sweep on L serves)
             }
             s->upper_ld = npad_m;
         }
@@ -1767,7 +1766,6 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
     madqp_ctx* ctx = s->ctx;
     const int64_t n = s->n;
     HIP_TRY(ctx, hipMemsetAsync(s->d_info, 0, sizeof(int32_t), ctx->stream));
-    s->upper_ok = false;
     // mid-size matrices: right-looking, two launches per 128-column block (chol_mid_step_kernel)
     // (measured on bench.py, m = 0.4 n, ms per iteration against the left-looking schedule: 3.34 / 3.90 at n = 3 000,
     // 6.37 / 7.51 at 5 000, 13.7 / 15.1 at 8 000, 22.7 / 23.2 at 10 000, 34.4 / 33.0 at 12 000 -- every step rewrites
@@ -1790,22 +1788,16 @@ static int32_t chol_factor_enqueue(madqp_chol* s, double* A, int64_t lda) {
 extern "C" int32_t madqp_chol_factor(madqp_chol* s, double* A, int64_t lda, int32_t* info_host) {
     if (!s) return MADQP_ERR_ARG;
     madqp_ctx* ctx = s->ctx;
-    ARG_TRY(ctx, A && info_host && lda >= (s->band.packed ? std::max<int64_t>(s->band.extent, 1) : s->n));
-    s->factored = false;
-    s->A = A;
-    s->lda = lda;
-    *info_host = 0;
-    if (s->n == 0) {
-        s->factored = true;
-        return MADQP_OK;
-    }
-    int32_t r = chol_factor_enqueue(s, A, lda);
+    ARG_TRY(ctx, info_host != nullptr);
+    int32_t r = adopt_matrix(s, A, lda);
     if (r) return r;
+    *info_host = 0;
+    if (s->n == 0) return MADQP_OK;
+    if ((r = chol_factor_enqueue(s, A, lda))) return r;
     int32_t info = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&info, s->d_info, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *info_host = info;
-    s->factored = (info == 0);
     return MADQP_OK;
 }
 
@@ -1815,27 +1807,22 @@ __global__ void info_to_slot_kernel(const int32_t* __restrict__ info, double* __
 }
 }  // namespace
 // Queued form (mpc.hip): no read-back here; info goes to *d_slot (a word of the context's result block) and comes
-// back with the caller's next madqp_read_results, who then reports it through madqp_chol_factor_result.  Until then
-// the object counts as factored: solves enqueued behind a failed factorisation produce values the caller discards.
+// back with the caller's next madqp_read_results.  The handle does not learn it: solves enqueued behind a failed
+// factorisation run, and produce values the caller discards.
 int32_t madqp_chol_factor_q(madqp_chol* s, double* A, int64_t lda, double* d_slot) {
     if (!s) return MADQP_ERR_ARG;
     madqp_ctx* ctx = s->ctx;
-    ARG_TRY(ctx, A && d_slot && lda >= (s->band.packed ? std::max<int64_t>(s->band.extent, 1) : s->n));
-    s->A = A;
-    s->lda = lda;
-    s->factored = true;
+    ARG_TRY(ctx, d_slot != nullptr);
+    int32_t r = adopt_matrix(s, A, lda);
+    if (r) return r;
     if (s->n == 0) {
         HIP_TRY(ctx, hipMemsetAsync(d_slot, 0, sizeof(double), ctx->stream));
         return MADQP_OK;
     }
-    int32_t r = chol_factor_enqueue(s, A, lda);
-    if (r) return r;
+    if ((r = chol_factor_enqueue(s, A, lda))) return r;
     hipLaunchKernelGGL(info_to_slot_kernel, dim3(1), dim3(1), 0, ctx->stream, s->d_info, d_slot);
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
-}
-void madqp_chol_factor_result(madqp_chol* s, int32_t info) {
-    if (s) s->factored = (info == 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1876,12 +1863,9 @@ bool panel_ok(const madqp_chol* s, int64_t j0, int64_t w) {
 extern "C" int32_t madqp_chol_factor_begin(madqp_chol* s, double* A, int64_t lda) {
     if (!s) return MADQP_ERR_ARG;
     madqp_ctx* ctx = s->ctx;
-    ARG_TRY(ctx, A && lda >= s->n);
     ARG_TRY(ctx, s->npos == s->n);  // the panel pieces factor positive definite matrices only
     ARG_TRY(ctx, s->band.bw < 0);        // ... and know no band
-    s->factored = false;
-    s->A = A;
-    s->lda = lda;
+    if (const int32_t r = adopt_matrix(s, A, lda)) return r;
     HIP_TRY(ctx, hipMemsetAsync(s->d_info, 0, sizeof(int32_t), ctx->stream));
     return MADQP_OK;
 }
@@ -1912,18 +1896,52 @@ extern "C" int32_t madqp_chol_panel_pack(madqp_chol* s, int64_t j0, int64_t w, d
     return MADQP_OK;
 }
 
+// ---- the sweeps of one solve, described once: madqp_chol_solve (both of its paths) and madqp_trsv_tile build this and launch
+// through launch_sweep ----
+struct Sweeps {
+    hipStream_t stream;
+    unsigned grid;  // workgroups per sweep: the jobs of the list, one per block row without a list
+    const double* winv;
+    int64_t n;
+    int32_t* ctl;       // the sweeps' ticket counters: ctl[1] forward, ctl[2] backward
+    double* fault;      // the context's fault word
+    int vec;            // the factor may be read in 16-byte pieces
+    int kb;             // the band of the sweeps in blocks (band_plan.inc), -1 for whole block rows
+    SweepPlan fwd, bwd;  // the job list (dense or band) with the partial-sum slots of either direction
+};
+// jobs: the list (of njobs) and the slots of the forward sweep; the backward sweep's follow them
+static Sweeps solve_sweeps(madqp_ctx* ctx, int64_t n, const double* L, int64_t ld, const double* winv, int32_t* ctl, const SweepPlan& jobs,
+                           int32_t njobs, int kb) {
+    const int64_t nblk = (n + NB - 1) / NB;
+    Sweeps w{ctx->stream, jobs.jobs ? (unsigned)njobs : (unsigned)nblk, winv, n, ctl, ctx->d_res + MADQP_FAULT_SLOT,
+             ((((uintptr_t)L) & 15) == 0) && (ld % 2 == 0), kb, jobs, jobs};
+    if (jobs.part) w.bwd.part = jobs.part + nblk * jobs.maxc * NB;
+    return w;
+}
+// The three forms of a sweep on the matrix M (ld): v <- L^-1 v on L, v <- L^-T v on L, and v <- L^-T v as the forward
+// kernel on U = L' from the far end (out2: the plain copy of the solution)
+enum SweepForm { SWEEP_FWD, SWEEP_BWD, SWEEP_REV };
+static void launch_sweep(const Sweeps& w, SweepForm form, const double* M, int64_t ld, const double* in, double* out,
+                         double* out2 = nullptr) {
+    const dim3 grid(w.grid), block(1024);
+    if (form == SWEEP_BWD)
+        hipLaunchKernelGGL(trsv_bwd_sweep_kernel, grid, block, 0, w.stream, M, ld, w.winv, in, out, w.n, w.ctl, w.fault, w.vec, w.bwd, w.kb);
+    else if (form == SWEEP_FWD)
+        hipLaunchKernelGGL(sweep_fwd_kernel, grid, block, 0, w.stream, M, ld, w.winv, in, out, w.n, w.ctl, w.fault, w.vec, w.fwd,
+                           (double*)nullptr, w.kb);
+    else
+        hipLaunchKernelGGL(trsv_fwd_sweep_kernel<true>, grid, block, 0, w.stream, M, ld, w.winv, in, out, w.n, w.ctl, w.fault, w.vec, w.bwd,
+                           out2, w.kb);
+}
+
 // One sweep over a single order-w tile (multi-GPU solves, dist.hip): the same kernels as madqp_chol_solve.
 int32_t madqp_trsv_tile(madqp_ctx* ctx, int32_t trans, const double* L, int64_t ld, const double* winv, double* v,
                         int64_t w, double* tmp, int32_t* ctl) {
     ARG_TRY(ctx, L && winv && v && tmp && ctl && w > 0 && ld >= w);
     ProfScope ps(ctx, MADQP_PROF_TRSV);
-    const unsigned nblk = (unsigned)((w + NB - 1) / NB);
-    const int vec = ((((uintptr_t)L) & 15) == 0) && (ld % 2 == 0);
     HIP_TRY(ctx, hipMemsetAsync(ctl, 0, 4 * sizeof(int32_t), ctx->stream));
     HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)tmp, 0x7FF8A5A5, 2 * (size_t)w, ctx->stream));
-    const SweepPlan none{nullptr, nullptr, 0, 0};
-    double* fault = ctx->d_res + MADQP_FAULT_SLOT;
-    launch_sweep(trans != 0, nblk, ctx->stream, L, ld, winv, v, tmp, w, ctl, fault, vec, none);
+    launch_sweep(solve_sweeps(ctx, w, L, ld, winv, ctl, SweepPlan{nullptr, nullptr, 0, 0}, 0, -1), trans ? SWEEP_BWD : SWEEP_FWD, L, ld, v, tmp);
     LAUNCH_CHECK(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(v, tmp, (size_t)w * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     return MADQP_OK;
@@ -1938,51 +1956,34 @@ extern "C" int32_t madqp_chol_solve(madqp_chol* s, double* rhs) {
     const double* A = s->A;
     if (n == 0) return MADQP_OK;
     ProfScope ps(ctx, MADQP_PROF_TRSV);
-    if (s->upper_ok) {  // mid-size factor: y = L^-1 b, then x = U^-1 y with the same kernel on U = L'; three launches
-        const int64_t nblk = (n + NB - 1) / NB;
-        const unsigned grid = s->d_jobs ? (unsigned)s->sweep_njobs : (unsigned)nblk;
-        double* yv = s->utmp;
-        double* xv = yv + nblk * NB;
-        double* part_f = xv + nblk * NB;
-        double* part_b = part_f + nblk * s->sweep_maxc * NB;
-        const SweepPlan pf{s->d_jobs, part_f, s->sweep_chunk, s->sweep_maxc}, pb{s->d_jobs, part_b, s->sweep_chunk, s->sweep_maxc};
-        double* fault = ctx->d_res + MADQP_FAULT_SLOT;
+    // one launch per sweep (see trsv_*_sweep_kernel).  Under a bandwidth the band form: the tiles within sweep_kb blocks of
+    // the diagonal, along the band's own (shorter) job list
+    const bool band = s->band.sweep_kb >= 0;
+    double* y = s->sweep_y;
+    const SweepPlan jobs{band ? s->band.d_jobs : s->d_jobs, y + (n + NB - 1) / NB * NB, s->sweep_chunk, s->sweep_maxc};
+    const Sweeps sw = solve_sweeps(ctx, n, A, lda, s->winv, s->d_info, jobs, band ? s->band.njobs : s->sweep_njobs, (int)s->band.sweep_kb);
+    if (s->upper_ok) {  // mid-size factor (no band): y = L^-1 b, then x = U^-1 y with the same kernel on U = L'; three launches
         hipLaunchKernelGGL(sweep_prep_kernel, dim3((unsigned)std::min<int64_t>((s->utmp_len + 255) / 256, 256)), dim3(256), 0,
-                           ctx->stream, reinterpret_cast<unsigned long long*>(s->utmp), s->utmp_len, s->d_info);
-        hipLaunchKernelGGL(trsv_fwd_sweep_kernel<false>, dim3(grid), dim3(1024), 0, ctx->stream, A, lda, s->winv,
-                           (const double*)rhs, yv, n, s->d_info, fault, 1, pf, (double*)nullptr, -1);
-        hipLaunchKernelGGL(trsv_fwd_sweep_kernel<true>, dim3(grid), dim3(1024), 0, ctx->stream, (const double*)s->upper,
-                           s->upper_ld, s->winv, (const double*)yv, xv, n, s->d_info, fault, 1, pb, rhs, -1);
+                           ctx->stream, reinterpret_cast<unsigned long long*>(s->sweep_x), s->utmp_len, s->d_info);
+        launch_sweep(sw, SWEEP_FWD, A, lda, rhs, y);
+        launch_sweep(sw, SWEEP_REV, s->upper, s->upper_ld, y, s->sweep_x, rhs);
         LAUNCH_CHECK(ctx);
         return MADQP_OK;
     }
-    {
-        // one launch per sweep (see trsv_*_sweep_kernel): y = L^-1 b into s->tmp, x = L^-T y into rhs
-        const unsigned nblk = (unsigned)((n + NB - 1) / NB);
-        const int vec = ((((uintptr_t)A) & 15) == 0) && (lda % 2 == 0);
-        const int64_t nb64 = nblk;
-        // under a bandwidth the band form: the tiles within sweep_kb blocks of the diagonal, its own (shorter) job list
-        const int kb = (int)s->band.sweep_kb;
-        const int32_t* jobs = kb >= 0 ? s->band.d_jobs : s->d_jobs;
-        const unsigned grid = jobs ? (unsigned)(kb >= 0 ? s->band.njobs : s->sweep_njobs) : nblk;
-        double* part_f = s->tmp + nb64 * NB;
-        double* part_b = part_f + nb64 * s->sweep_maxc * NB;
-        const SweepPlan pf{jobs, part_f, s->sweep_chunk, s->sweep_maxc};
-        const SweepPlan pb{jobs, part_b, s->sweep_chunk, s->sweep_maxc};
-        HIP_TRY(ctx, hipMemsetAsync(s->d_info + 1, 0, 3 * sizeof(int32_t), ctx->stream));
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)s->tmp, 0x7FF8A5A5, 2 * (size_t)s->tmp_len, ctx->stream));
-        launch_sweep(false, grid, ctx->stream, A, lda, s->winv, rhs, s->tmp, n, s->d_info, ctx->d_res + MADQP_FAULT_SLOT, vec, pf, kb);
-        LAUNCH_CHECK(ctx);
-        if (s->npos < n) {  // y <- diag(I, -I) y
-            const int64_t len = n - s->npos;
-            hipLaunchKernelGGL(negate_kernel, dim3((unsigned)std::min<int64_t>((len + 255) / 256, 1024)), dim3(256), 0,
-                               ctx->stream, s->tmp + s->npos, len);
-            LAUNCH_CHECK(ctx);
-        }
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)rhs, 0x7FF8A5A5, 2 * (size_t)n, ctx->stream));
-        launch_sweep(true, grid, ctx->stream, A, lda, s->winv, s->tmp, rhs, n, s->d_info, ctx->d_res + MADQP_FAULT_SLOT, vec, pb, kb);
+    // y = L^-1 b into the scratch, x = L^-T y into rhs
+    HIP_TRY(ctx, hipMemsetAsync(s->d_info + 1, 0, 3 * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)y, 0x7FF8A5A5, 2 * (size_t)s->tmp_len, ctx->stream));
+    launch_sweep(sw, SWEEP_FWD, A, lda, rhs, y);
+    LAUNCH_CHECK(ctx);
+    if (s->npos < n) {  // y <- diag(I, -I) y
+        const int64_t len = n - s->npos;
+        hipLaunchKernelGGL(negate_kernel, dim3((unsigned)std::min<int64_t>((len + 255) / 256, 1024)), dim3(256), 0,
+                           ctx->stream, y + s->npos, len);
         LAUNCH_CHECK(ctx);
     }
+    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)rhs, 0x7FF8A5A5, 2 * (size_t)n, ctx->stream));
+    launch_sweep(sw, SWEEP_BWD, A, lda, y, rhs);
+    LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }
 
@@ -2142,31 +2143,16 @@ extern "C" int32_t madqp_chol_solve_many(madqp_chol* s, double* B, int64_t ldb, 
         return MADQP_OK;
     }
     ProfScope ps(ctx, MADQP_PROF_TRSV);
-    struct ProfMute {  // (one timer scope for the call: the scopes of the products inside are switched off meanwhile)
-        madqp_ctx* c;
-        decltype(c->prof) saved;
-        explicit ProfMute(madqp_ctx* ctx_) : c(ctx_), saved(ctx_->prof) { c->prof = 0; }
-        ~ProfMute() { c->prof = saved; }
-    } mute(ctx);
+    ProfMute mute(ctx);  // (one timer scope for the call)
     const bool up = s->upper_ok;  // the last factorisation left U = L'
     const int64_t lda = s->lda, npad = (n + NB - 1) / NB * NB, ldt = solve_plan_ldt(nrhs);
-    const int64_t need = solve_plan_workspace(n, nrhs, up);
-    if (need > s->many_ws_len) {  // grown here: the stream is drained before the old buffer goes
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->many_ws) (void)hipFree(s->many_ws);
-        s->many_ws = nullptr;
-        s->many_ws_len = 0;
-        if (hipMalloc(&s->many_ws, (size_t)need * sizeof(double)) != hipSuccess) {
-            (void)hipGetLastError();
-            s->many_ws = nullptr;
-            return madqp_fail(ctx, MADQP_ERR_ALLOC, "madqp_chol_solve_many: no memory for %lld doubles of workspace", (long long)need);
-        }
-        s->many_ws_len = need;
-    }
+    // (grown here, at the first call that needs more: the stream is drained before the old buffer goes)
+    if (const int32_t r = s->mem.grow(&s->many_ws, &s->many_ws_len, solve_plan_workspace(n, nrhs, up), "madqp_chol_solve_many: workspace"))
+        return r;
     double* T = s->many_ws;
     double* strip = T + ldt * npad;  // (npad x 128, leading dimension npad; only without U)
     const double* A = s->A;
-    const bool padded = s->band.packed || lda >= npad;  // rows up to the padded order may be read (CholTarget::padded)
+    const bool padded = chol_target(s, s->A, lda).padded();
     std::vector<SolveOp> ops;
     solve_plan(n, s->npos, s->band.sweep_kb, nrhs, ops);
     const dim3 tgrid((unsigned)(npad / 64), (unsigned)(ldt / 64));

@@ -117,9 +117,7 @@ int32_t madqp_q_kkt_eval(madqp_kkt* k, const madqp_state* st, const double* q, c
 int32_t madqp_q_kkt_factorize(madqp_kkt* k, int slot0);                                         // MPC_W_INFO slot: info
 // w = K^-1 p, optionally pcopy = p (kkt.hip: the condensed mode runs its per-variable passes fused)
 int32_t madqp_kkt_solve_from(madqp_kkt* k, const madqp_state* st, const double* p, double* w, double* pcopy);
-int32_t madqp_kkt_factor_result(madqp_kkt* k, int32_t info);
 int32_t madqp_chol_factor_q(madqp_chol* s, double* A, int64_t lda, double* d_slot);  // info -> *d_slot, no read-back
-void madqp_chol_factor_result(madqp_chol* s, int32_t info);                           // what the read-back said
 
 struct ProfScope {
     madqp_ctx* c;
@@ -130,6 +128,13 @@ struct ProfScope {
     ~ProfScope() {
         if (on) madqp_prof_end(c);
     }
+};
+// one timer scope for a whole call: the scopes of the launches inside are switched off while this lives
+struct ProfMute {
+    madqp_ctx* c;
+    uint32_t saved;
+    explicit ProfMute(madqp_ctx* ctx) : c(ctx), saved(ctx->prof) { c->prof = 0; }
+    ~ProfMute() { c->prof = saved; }
 };
 
 // gemm_f64.hip
@@ -215,7 +220,7 @@ int32_t madqp_sparse_gram_band(madqp_ctx* ctx, int64_t n, const Csr& v, const Cs
 int32_t madqp_syrk_assemble_impl(madqp_ctx* ctx, int64_t n, int64_t kdim, const double* B, int64_t ldb, const double* w,
                                  const double* base, int64_t ldbase, const double* dvec, double* C, int64_t ldc);
 
-// The device buffers an object owns (madqp_kkt, madqp_dkkt, madqp_batch): every allocation is recorded and freed by
+// The device buffers an object owns (madqp_kkt, madqp_dkkt, madqp_batch, madqp_chol): every allocation is recorded and freed by
 // release() or the destructor.  `who` is the caller's name for the message of a failure.
 struct DevOwner {
     madqp_ctx* ctx = nullptr;
@@ -248,7 +253,7 @@ struct DevOwner {
         if (*p && want <= *have) return MADQP_OK;
         if (*p) {
             (void)hipStreamSynchronize(ctx->stream);
-            drop(*p);
+            (void)free_one(p);
         }
         *have = 0;
         const int32_t r = alloc(p, want, who);
@@ -267,15 +272,17 @@ struct DevOwner {
             owned.pop_back();
         }
     }
-
-private:
-    void drop(void* q) {
+    // frees one buffer now (the caller knows that nothing on the stream still uses it); *p == nullptr afterwards
+    template <class T>
+    hipError_t free_one(T** p) {
         for (size_t i = 0; i < owned.size(); ++i)
-            if (owned[i] == q) {
+            if (owned[i] == *p) {
                 owned.erase(owned.begin() + (std::ptrdiff_t)i);
                 break;
             }
-        (void)hipFree(q);
+        const hipError_t e = *p ? hipFree(*p) : hipSuccess;
+        *p = nullptr;
+        return e;
     }
 };
 
@@ -290,8 +297,8 @@ int32_t madqp_chol_panel_solve(madqp_ctx* ctx, double* X, int64_t ldx, int64_t r
 int32_t madqp_trsv_tile(madqp_ctx* ctx, int32_t trans, const double* L, int64_t ld, const double* winv, double* v,
                         int64_t w, double* tmp, int32_t* ctl);
 
-// The band state of a Cholesky handle (madqp_chol_set_bandwidth, madqp_chol_set_packed; band_plan.inc), cleared and
-// committed as one
+// The band state of a Cholesky handle (madqp_chol_set_bandwidth, madqp_chol_set_packed; band_plan.inc), cleared
+// (chol.hip: band_clear) and committed as one
 struct madqp_chol_band {
     int64_t bw = -1;      // half-bandwidth (-1: none, the dense schedules and sweeps)
     int64_t extent = 0;   // of the plan: the largest i - j the factorisation touches; n - 1 without a band
@@ -301,41 +308,46 @@ struct madqp_chol_band {
     int64_t sweep_kb = -1;
     int32_t* d_jobs = nullptr;
     int32_t njobs = 0;
-    // back to "no band" for a handle of order n; frees the job list, which nothing on the stream may still read (chol.hip)
-    hipError_t clear(int64_t n);
+};
+// The plan of the mid-size schedule (chol.hip: mid_plan_build): which trailing tiles each block step updates, with which
+// panels; built at the first factorisation that asks for it
+struct MidPlan {
+    int32_t state = 0;                  // 0 not built, 1 in use, -1 no plan (the left-looking schedule runs)
+    std::vector<int32_t> count, first;  // per step: its number of units, and where they start in d_units
+    uint32_t* d_units = nullptr;        // the packed units of all steps (mid_plan.inc)
 };
 
 struct madqp_chol {
     madqp_ctx* ctx = nullptr;
     int64_t n = 0;
+    DevOwner mem;            // every device buffer below is this owner's
     double* winv = nullptr;  // ceil(n/128) blocks of 128x128 (col-major, ld 128): inverse diagonal blocks
-    double* tmp = nullptr;   // tmp_len doubles: the intermediate vector of a solve, then the sweeps' partial-sum slots
-    int64_t tmp_len = 0;
+    // The scratch of a solve, one buffer: [x | y | partial-sum slots of the forward sweep | of the backward sweep].  A solve
+    // on L fills and uses the tmp_len doubles from y on (y: its intermediate vector); a solve with U = L' the utmp_len
+    // doubles from x on (x: the polled copy of its solution), filled by one kernel.  sweep_x == nullptr: the buffer starts
+    // at y, no solve of this handle runs on U (one block, or more than 160).
+    double* sweep_x = nullptr;
+    double* sweep_y = nullptr;
+    int64_t tmp_len = 0, utmp_len = 0;
     int32_t* d_jobs = nullptr;  // sweep job list (chol.hip SweepPlan), nullptr when every block row is one job
     int32_t sweep_chunk = 0, sweep_maxc = 0, sweep_njobs = 0;
     bool sweep_band = false;  // MADQP_SWEEP_BAND of this handle: under a bandwidth the sweeps stay inside the band
     madqp_chol_band band;
     // the left-looking plan for the current (bandwidth, npos) (chol_plan.inc; chol.hip: handle_plan); empty: not built, or none needed yet
     std::vector<struct CholOp> plan;
-    int32_t* d_info = nullptr;
-    double* A = nullptr;  // last factored matrix (borrowed)
+    int32_t* d_info = nullptr;  // [0] info, [1..2] sweep tickets
+    // the last matrix handed to a factorisation (borrowed; chol.hip: adopt_matrix) -- nullptr: none, or forgotten
+    // (forget_factor), and the solves refuse with MADQP_ERR_STATE.  Whether that factorisation succeeded is the caller's
+    // knowledge, not the handle's.
+    double* A = nullptr;
     int64_t lda = 0;
-    bool factored = false;
     int64_t npos = 0;  // quasi-definite mode (madqp_chol_set_signature): A = L diag(I_npos, -I) L'; npos == n: Cholesky
-    // mid-size schedule (chol.hip, mid_plan_build): which trailing tiles each block step updates, with which panels;
-    // built at the first factorisation.  d_mid_plan: the packed units of all steps (mid_plan.inc); mid_units[k] /
-    // mid_units[nblk + k]: number of units of step k / where they start
-    uint32_t* d_mid_plan = nullptr;
-    int32_t* mid_units = nullptr;
-    int32_t mid_plan_state = 0;  // state: 0 not built, 1 in use, -1 no plan (the two-panel schedule runs)
-    // the backward sweep on U = L' (chol.hip, trsv_fwd_sweep_kernel<1, true>): U of the last mid-size factorisation (order
-    // npad, allocated at the first one), and the scratch of such a solve -- [y | x | partial sums of both sweeps], filled
-    // with the sentinel by one kernel per solve
+    MidPlan mid;
+    // the backward sweep on U = L' (chol.hip, trsv_fwd_sweep_kernel<true>): U of the last mid-size factorisation (order
+    // npad, allocated at the first one)
     double* upper = nullptr;
     int64_t upper_ld = 0;
-    double* utmp = nullptr;
-    int64_t utmp_len = 0;
-    bool upper_ok = false;  // the last factorisation left U and substitution images
+    bool upper_ok = false;  // the last factorisation left U
     // madqp_chol_solve_many: the transposed block of right-hand sides and, without U, the strip of one block row of L'
     // (solve_plan.inc: solve_plan_workspace), grown at the first call that needs more; from many_min right-hand sides on
     // the call takes the blocked path

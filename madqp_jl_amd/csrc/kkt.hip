@@ -807,17 +807,12 @@ extern "C" int32_t madqp_kkt_factorize(madqp_kkt* k, int32_t* info_host) {
     if (int32_t r = kkt_storage_ready(k, "madqp_kkt_factorize")) return r;
     return madqp_chol_factor(k->chol, k->K, k->ldk, info_host);
 }
-// queued form: the factorisation is enqueued, its info lands in the result block; madqp_kkt_factor_result hands the
-// value the caller read back to the solver object
+// queued form: the factorisation is enqueued, its info lands in the result block and comes back with the caller's next
+// madqp_read_results
 int32_t madqp_q_kkt_factorize(madqp_kkt* k, int slot0) {
     if (!k) return MADQP_ERR_ARG;
     if (int32_t r = kkt_storage_ready(k, "madqp_kkt_factorize")) return r;
     return madqp_chol_factor_q(k->chol, k->K, k->ldk, k->ctx->d_res + slot0);
-}
-int32_t madqp_kkt_factor_result(madqp_kkt* k, int32_t info) {
-    if (!k) return MADQP_ERR_ARG;
-    madqp_chol_factor_result(k->chol, info);
-    return MADQP_OK;
 }
 
 static int32_t kkt_solve_once(madqp_kkt* k, const madqp_state* st, double* w);
@@ -1054,9 +1049,13 @@ static int32_t kkt_solve_once(madqp_kkt* k, const madqp_state* st, double* w) {
 // the one-vector solve launched on offset pointers, the products with A / A' stay mat-vecs per column.
 // column c of the work blocks: [t | u | tn | b], each a block of nrhs columns at a stride of whole 256 bytes
 static int64_t kkt_pad32(int64_t v) { return (v + 31) / 32 * 32; }
+// the stride of the augmented form's b block: the order of the factorised matrix (kkt_form.inc), padded
+static int64_t kkt_many_sb(const madqp_kkt* k) {
+    return k->mode == KKT_AUGMENTED ? kkt_pad32(kkt_orders(k->mode, k->nx, k->m).stored_order) : 0;
+}
 static KktWork kkt_many_work(const madqp_kkt* k, const madqp_state* st, int64_t nrhs, int64_t c) {
     const int64_t sm = kkt_pad32(k->m), sn = k->mode == KKT_NORMAL ? kkt_pad32(st->n) : 0;
-    const int64_t sb = k->mode == KKT_AUGMENTED ? kkt_pad32(k->chol->n) : 0;
+    const int64_t sb = kkt_many_sb(k);
     double* t = k->many;
     double* u = t + nrhs * sm;
     double* tn = u + nrhs * sm;
@@ -1065,13 +1064,12 @@ static KktWork kkt_many_work(const madqp_kkt* k, const madqp_state* st, int64_t 
 }
 static int32_t kkt_solve_many_once(madqp_kkt* k, const madqp_state* st, double* W, int64_t ldw, int64_t nrhs) {
     int32_t r = 0;
-    const int64_t per = 2 * kkt_pad32(k->m) + (k->mode == KKT_NORMAL ? kkt_pad32(st->n) : 0) +
-                        (k->mode == KKT_AUGMENTED ? kkt_pad32(k->chol->n) : 0);
+    const int64_t per = 2 * kkt_pad32(k->m) + (k->mode == KKT_NORMAL ? kkt_pad32(st->n) : 0) + kkt_many_sb(k);
     if ((r = k->mem.grow(&k->many, &k->many_cap, nrhs * per, "madqp_kkt_solve_many: work vectors of the columns"))) return r;
     k->u_is_A_of = nullptr;
     for (int64_t c = 0; c < nrhs; ++c)
         if ((r = kkt_solve_before(k, st, W + c * ldw, kkt_many_work(k, st, nrhs, c)))) return r;
-    const int64_t ldb = k->mode == KKT_AUGMENTED ? kkt_pad32(k->chol->n) : ldw;
+    const int64_t ldb = k->mode == KKT_AUGMENTED ? kkt_many_sb(k) : ldw;
     if ((r = madqp_chol_solve_many(k->chol, kkt_factor_rhs(k, st, W, kkt_many_work(k, st, nrhs, 0)), ldb, nrhs))) return r;
     for (int64_t c = 0; c < nrhs; ++c)
         if ((r = kkt_solve_after(k, st, W + c * ldw, kkt_many_work(k, st, nrhs, c)))) return r;

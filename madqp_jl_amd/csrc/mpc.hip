@@ -501,7 +501,6 @@ int32_t body_fused(madqp_mpc* s, madqp_mpc_info* info_host) {
         return (v && went) ? differ() : v;
     };
     s->last_info = (int32_t)rb[MPC_SL_INFO];
-    TRY(madqp_kkt_factor_result(s->kkt, s->last_info));
     if (s->last_info != 0) {  // src/linear_solver.jl:6-17: what was queued behind the failed factorisation is void
         if (went) return differ();
         s->del_w *= 100.0;
