@@ -44,8 +44,6 @@ static_assert(S_COUNT == MADQP_BATCH_SCALARS, "scalar block layout is part of th
 enum { T_OBJ = 0, T_INF_PR, T_INF_DU, T_INF_COMPL, T_MU, T_DNORM, T_DEL_W, T_ALPHA_P, T_ALPHA_D, T_RATIO, T_COUNT };
 static_assert(T_COUNT == MADQP_BATCH_TRACE_LEN, "trace record layout is part of the ABI");
 
-enum { ST_ACTIVE = 0, ST_SOLVED = 1, ST_MAXITER = 6, ST_STEP_ERROR = -3, ST_INTERNAL = -1 };
-
 // Per-problem pattern (PAT_LEN int64 per problem, bq.pat): problem b has its own number of slacks ns_b (n_b = nx + ns_b),
 // of finite lower / upper bounds, and offsets into the index lists and into the arrays of length nlb / nub.  A batch made by
 // madqp_batch_create has one list of each kind that every problem points at (list offsets 0, storage offsets b * nlb);
@@ -206,7 +204,7 @@ __device__ unsigned long long madqp_batch_stamps[32];  // [31] = last stamp; slo
 
 __global__ void bq_count_active_kernel(const int32_t* __restrict__ status, int64_t B, int32_t* out) {
     int cnt = 0;
-    for (int64_t i = threadIdx.x; i < B; i += blockDim.x) cnt += (status[i] == ST_ACTIVE);
+    for (int64_t i = threadIdx.x; i < B; i += blockDim.x) cnt += (status[i] == MPC_ST_ACTIVE);
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off, 64);
     if (threadIdx.x == 0) *out = cnt;
 }
@@ -632,7 +630,7 @@ static int32_t launch_iteration(madqp_batch* b) {
     }
     int32_t r = factor_all(b, q.status);
     if (r) return r;
-    for (int trial = 1; trial < 3; ++trial) {  // src/linear_solver.jl:7: three trials in all
+    for (int trial = 1; trial < MPC_FACTOR_TRIALS; ++trial) {  // src/linear_solver.jl:7
         HIP_TRY(ctx, hipMemsetAsync(q.retry_count, 0, sizeof(int32_t), ctx->stream));
         {
             ProfScope ps(ctx, MADQP_PROF_VEC);

@@ -513,10 +513,10 @@ __device__ __forceinline__ bool wg_solve_system(const BQ& q, const madqp_state& 
     }
     wg::norm_inf3_kernel(pb.ntot, pb.w1, s.p, s.d, red);
     WG_SYNC();
-    const double ratio = red[0] / fmax(1.0, red[1]);
+    const double ratio = mpc_residual_ratio(red);
     WG_SYNC();
     if (threadIdx.x == 0) pb.scal[S_RATIO] = ratio;
-    return !((ratio != ratio) || (q.opt.check_residual && ratio > q.opt.tol_linear_solve));
+    return !mpc_solve_failed(ratio, q.opt.check_residual, q.opt.tol_linear_solve);
 }
 
 // callbacks obj / grad! / cons! (kkt.hip: madqp_kkt_eval)
@@ -527,7 +527,7 @@ __device__ __forceinline__ double wg_eval_model(const BQ& q, const madqp_state& 
     BSTAMP(10);
     wg::eval_grad_kernel(s.n, q.nx, (pb.H && q.nx) ? 1 : 0, pb.qv, s.x, s.f, red);
     WG_SYNC();
-    const double obj = pb.c0 + red[0] + 0.5 * red[1];
+    const double obj = mpc_objective(pb.c0, red[0], red[1]);
     WG_SYNC();
     if (q.m) {
         wg_gemv_n(q.m, q.nx, 1.0, pb.A, s.x, 0.0, s.c);
@@ -558,7 +558,7 @@ __device__ __forceinline__ double wg_eval_model_incr(const BQ& q, const madqp_st
     WG_SYNC();
     wg::eval_grad_kernel(s.n, q.nx, has_h ? 1 : 0, pb.qv, s.x, s.f, red);
     WG_SYNC();
-    const double obj = pb.c0 + red[0] + 0.5 * red[1];
+    const double obj = mpc_objective(pb.c0, red[0], red[1]);
     WG_SYNC();
     for (int64_t i = threadIdx.x; i < q.m; i += TPB) {
         const int64_t k = pb.slot[i];
@@ -573,7 +573,7 @@ __device__ __forceinline__ double wg_compl(const madqp_state& s, int affine, dou
     if (s.nlb + s.nub == 0) return 0.0;
     wg::compl_kernel(s, affine, ap, ad, nullptr, red);
     WG_SYNC();
-    const double v = (red[0] + red[1]) / (double)(s.nlb + s.nub);
+    const double v = mpc_compl_mean(red, (double)(s.nlb + s.nub));
     WG_SYNC();
     return v;
 }
@@ -596,82 +596,58 @@ __device__ __forceinline__ void wg_alpha_max(const madqp_state& s, double tau, d
         }
     WG_SYNC();
 }
-// (alpha_p, alpha_d) of get_fraction_to_boundary_step (src/kernels.jl:290-305)
-__device__ __forceinline__ void wg_fraction_to_boundary(const madqp_state& s, double tau, double* red, double& ap, double& ad) {
+// get_fraction_to_boundary_step (src/kernels.jl:290-305)
+__device__ __forceinline__ MpcSteps wg_fraction_to_boundary(const madqp_state& s, double tau, double* red) {
     double a[4];
     int64_t ib[4];
     wg_alpha_max(s, tau, red, a, ib);
-    ap = fmin(a[0], a[1]);
-    ad = fmin(a[2], a[3]);
+    return {mpc_min(a[0], a[1]), mpc_min(a[2], a[3])};
 }
 
 // update_step!(::MehrotraAdaptiveStep) (src/kernels.jl:325-374): element reads at the blocking indices
-__device__ __forceinline__ void wg_mehrotra_adaptive_step(const madqp_state& s, double gamma_f, double* red, double& alpha_p,
-                                          double& alpha_d) {
-    const double gamma_a = 1.0 / (1.0 - gamma_f);
-    double a[4];
+__device__ __forceinline__ MpcSteps wg_mehrotra_adaptive_step(const madqp_state& s, double gamma_f, double* red) {
+    double a[4], row[2][MPC_ROW_LEN] = {};
     int64_t ib[4];
     wg_alpha_max(s, 1.0, red, a, ib);
-    const double max_ap = fmin(a[0], a[1]), max_ad = fmin(a[2], a[3]);
-    const double mu_full = wg_compl(s, 1, max_ap, max_ad, red) / gamma_a;
-    const double* dx = s.d;
-    const double* dzl = s.d + s.n + s.m;
-    const double* dzu = dzl + s.nlb;
-    alpha_p = 1.0;
-    alpha_d = 1.0;
-    if (max_ap < 1.0) {
-        if (a[0] <= a[1]) {
-            const int64_t i = ib[0], j = s.ind_lb[i];
-            const double tmp = mu_full / (s.zl[j] + max_ad * dzl[i]);
-            alpha_p = (s.x[j] - s.xl[j] - tmp) / (-dx[j]);
-        } else {
-            const int64_t i = ib[1], j = s.ind_ub[i];
-            const double tmp = mu_full / (s.zu[j] + max_ad * dzu[i]);
-            alpha_p = (s.xu[j] - s.x[j] - tmp) / dx[j];
-        }
+    const double mean = wg_compl(s, 1, mpc_min(a[0], a[1]), mpc_min(a[2], a[3]), red);
+#pragma unroll
+    for (int dual = 0; dual < 2; ++dual) {
+        const int k = mpc_blocking(a, dual);
+        if (k < 0) continue;
+        const bool ub = k & 1;
+        const int64_t i = ib[k], j = (ub ? s.ind_ub : s.ind_lb)[i];
+        double* r = row[dual];
+        r[MPC_ROW_X] = s.x[j];
+        r[MPC_ROW_BOUND] = (ub ? s.xu : s.xl)[j];
+        r[MPC_ROW_Z] = (ub ? s.zu : s.zl)[j];
+        r[MPC_ROW_DX] = s.d[j];
+        r[MPC_ROW_DZ] = s.d[s.n + s.m + (ub ? s.nlb : 0) + i];
     }
-    if (max_ad < 1.0) {
-        if (a[2] <= a[3]) {
-            const int64_t i = ib[2], j = s.ind_lb[i];
-            const double tmp = mu_full / (s.x[j] + max_ap * dx[j] - s.xl[j]);
-            alpha_d = -(s.zl[j] - tmp) / dzl[i];
-        } else {
-            const int64_t i = ib[3], j = s.ind_ub[i];
-            const double tmp = mu_full / (s.xu[j] - s.x[j] - max_ap * dx[j]);
-            alpha_d = -(s.zu[j] - tmp) / dzu[i];
-        }
-    }
-    alpha_p = fmax(alpha_p, gamma_f * max_ap);
-    alpha_d = fmax(alpha_d, gamma_f * max_ad);
+    return mpc_mehrotra_step(a, row[0], row[1], mean, gamma_f);
 }
 
 // gondzio_correction_direction! (src/solver.jl:200-251); false for MadNLP.SolveException
 template <bool REFINE>
 __device__ __forceinline__ bool wg_gondzio(const BQ& q, int64_t b, const madqp_state& s, const Prob& pb,
                                                     double mu_curr, double* lds, double* red) {
-    const double delta = 0.1, bmin = 0.1, bmax = 10.0, tau_g = 0.995;
     double* w2 = q.w2 + b * q.ntst;
-    double ap, ad;
-    wg_fraction_to_boundary(s, tau_g, red, ap, ad);
+    MpcSteps alpha = wg_fraction_to_boundary(s, MPC_GZ_TAU, red);
     for (int c = 0; c < q.opt.max_ncorr; ++c) {
-        const double ta_p = fmin(ap + delta, 1.0), ta_d = fmin(ad + delta, 1.0);
-        const double ga = wg_compl(s, 1, ta_p, ta_d, red);
-        const double mu_g = (ga / mu_curr) * (ga / mu_curr) * ga;
-        wg::extra_correction_kernel(s, ta_p, ta_d, bmin * mu_g, bmax * mu_g, nullptr, nullptr);
+        const MpcSteps ta = mpc_trial_alpha(alpha);
+        const double mu_g = mpc_muc(wg_compl(s, 1, ta.p, ta.d, red), mu_curr);
+        wg::extra_correction_kernel(s, ta.p, ta.d, MPC_GZ_BMIN * mu_g, MPC_GZ_BMAX * mu_g, nullptr, nullptr);
         WG_SYNC();
         wg::rhs_kernel(s, 1, mu_g, nullptr);
         wg_copy(pb.ntot, s.d, w2);
         WG_SYNC();
         if (!wg_solve_system<false, REFINE>(q, s, pb, lds, red)) return false;
-        double ha_p, ha_d;
-        wg_fraction_to_boundary(s, tau_g, red, ha_p, ha_d);
-        if (ha_p < 1.005 * ap || ha_d < 1.005 * ad) {
+        const MpcSteps ha = wg_fraction_to_boundary(s, MPC_GZ_TAU, red);
+        if (mpc_trial_dropped(ha, alpha)) {
             wg_copy(pb.ntot, w2, s.d);
             WG_SYNC();
             break;
         }
-        ap = ha_p;
-        ad = ha_d;
+        alpha = ha;
     }
     return true;
 }
@@ -722,7 +698,7 @@ __global__ __launch_bounds__(TPB) void bq_init_pre_kernel(BQ q) {
     const madqp_state s = state_of(q, b);
     const Prob pb = prob_of<WG_SHARED != 0>(q, b);
     if (threadIdx.x == 0) {
-        q.status[b] = ST_ACTIVE;
+        q.status[b] = MPC_ST_ACTIVE;
         q.iters[b] = 0;
         if (q.trace) q.trace_count[b] = 0;
     }
@@ -735,7 +711,7 @@ __global__ __launch_bounds__(TPB) void bq_init_pre_kernel(BQ q) {
     wg_fill(s.n, 0.0, s.jacl);
     WG_SYNC();
     // init_regularization! (src/kernels.jl:380-384)
-    const double del_w = 1.0, del_c = (q.opt.regularization == 0) ? 0.0 : q.opt.delta_d;
+    const MpcReg reg = mpc_init_regularization(q.opt.regularization, q.opt.delta_p, q.opt.delta_d);
     const double obj = wg_eval_model(q, s, pb, red, lds + 2 * NB);  // :166-169
     wg::norm_inf3_kernel(s.m, pb.rhs, nullptr, nullptr, red);
     WG_SYNC();
@@ -746,9 +722,9 @@ __global__ __launch_bounds__(TPB) void bq_init_pre_kernel(BQ q) {
     const double norm_c = red[0];
     WG_SYNC();
     // init_starting_point! :16-18
-    wg_fill(s.n, del_w, s.reg);
-    wg_fill(s.n, del_w, s.pr_diag);
-    wg_fill(s.m, del_c, s.du_diag);
+    wg_fill(s.n, reg.del_w, s.reg);
+    wg_fill(s.n, reg.del_w, s.pr_diag);
+    wg_fill(s.m, reg.del_c, s.du_diag);
     WG_SYNC();
     wg_build_operands(q, s, pb);
     if (threadIdx.x == 0) {
@@ -759,11 +735,11 @@ __global__ __launch_bounds__(TPB) void bq_init_pre_kernel(BQ q) {
         sc[S_INF_PR] = sc[S_INF_DU] = sc[S_INF_COMPL] = sc[S_DNORM] = 0.0;
         sc[S_NORM_B] = norm_b;
         sc[S_NORM_C] = norm_c;
-        sc[S_DEL_W] = del_w;
-        sc[S_DEL_C] = del_c;
+        sc[S_DEL_W] = reg.del_w;
+        sc[S_DEL_C] = reg.del_c;
         sc[S_RATIO] = 0.0;
-        sc[S_REG_P] = q.opt.delta_p;
-        sc[S_REG_D] = q.opt.delta_d;
+        sc[S_REG_P] = reg.run_p;
+        sc[S_REG_D] = reg.run_d;
         sc[S_NFACT] = 1.0;  // the start-point factorisation (src/solver.jl:21)
     }
 }
@@ -776,21 +752,21 @@ __global__ __launch_bounds__(TPB) void bq_init_post_kernel(BQ q) {
     const int64_t b = blockIdx.x;
     const madqp_state s = state_of(q, b);
     const Prob pb = prob_of<WG_SHARED != 0>(q, b);
-    int status = ST_ACTIVE;
-    if (q.info[b] != 0) status = ST_INTERNAL;  // the start matrix (Sigma = 1) must be positive definite
-    if (status == ST_ACTIVE) {
+    int status = MPC_ST_ACTIVE;
+    if (q.info[b] != 0) status = MPC_ST_INTERNAL;  // the start matrix (Sigma = 1) must be positive definite
+    if (status == MPC_ST_ACTIVE) {
         wg::rhs_kernel(s, 2, 0.0, nullptr);  // set_initial_primal_rhs! :25
         WG_SYNC();
-        if (!wg_solve_system<false, REFINE>(q, s, pb, lds, red)) status = ST_STEP_ERROR;
+        if (!wg_solve_system<false, REFINE>(q, s, pb, lds, red)) status = MPC_ST_STEP_ERROR;
     }
-    if (status == ST_ACTIVE) {
+    if (status == MPC_ST_ACTIVE) {
         wg::axpy_kernel(s.n, 1.0, s.d, s.x);  // :28
         WG_SYNC();
         wg::rhs_kernel(s, 3, 0.0, nullptr);  // set_initial_dual_rhs! :31
         WG_SYNC();
-        if (!wg_solve_system<false, REFINE>(q, s, pb, lds, red)) status = ST_STEP_ERROR;
+        if (!wg_solve_system<false, REFINE>(q, s, pb, lds, red)) status = MPC_ST_STEP_ERROR;
     }
-    if (status == ST_ACTIVE) {
+    if (status == MPC_ST_ACTIVE) {
         wg_copy(s.m, s.d + s.n, s.y);  // :33
         WG_SYNC();
         wg_jtprod(q, pb, s.y, s.jacl, lds + 2 * NB);  // :37
@@ -805,18 +781,16 @@ __global__ __launch_bounds__(TPB) void bq_init_post_kernel(BQ q) {
             for (int k = 0; k < 4; ++k) mn[k] = red[k];
             WG_SYNC();
         }
-        const double delta_x = fmax(0.0, fmax(-1.5 * mn[0], -1.5 * mn[1]));
-        const double delta_s = fmax(0.0, fmax(-1.5 * mn[2], -1.5 * mn[3]));
-        auto shift = [&](double dx, double dz) {  // :80-83 (madqp_sp_shift: four ordered passes)
-            if (s.nlb) wg::sp_shift_kernel(s.nlb, s.ind_lb, s.x, dx);
+        auto shift = [&](MpcShift by) {  // :80-83 (madqp_sp_shift: four ordered passes)
+            if (s.nlb) wg::sp_shift_kernel(s.nlb, s.ind_lb, s.x, by.x);
             WG_SYNC();
-            if (s.nub) wg::sp_shift_kernel(s.nub, s.ind_ub, s.x, -dx);
+            if (s.nub) wg::sp_shift_kernel(s.nub, s.ind_ub, s.x, -by.x);
             WG_SYNC();
-            if (s.nlb) wg::sp_shift_kernel(s.nlb, s.ind_lb, s.zl, dz);
-            if (s.nub) wg::sp_shift_kernel(s.nub, s.ind_ub, s.zu, dz);
+            if (s.nlb) wg::sp_shift_kernel(s.nlb, s.ind_lb, s.zl, by.z);
+            if (s.nub) wg::sp_shift_kernel(s.nub, s.ind_ub, s.zu, by.z);
             WG_SYNC();
         };
-        shift(delta_x, 1.0 + delta_s);
+        shift(mpc_start_shift(mn));
         double sm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (s.nlb || s.nub) {
             wg::sp_sums_kernel(s, red);  // :85-94
@@ -824,16 +798,13 @@ __global__ __launch_bounds__(TPB) void bq_init_post_kernel(BQ q) {
             for (int k = 0; k < 8; ++k) sm[k] = red[k];
             WG_SYNC();
         }
-        double mu = 0.0;
-        if (s.nlb > 0) mu += sm[0] - sm[1];
-        if (s.nub > 0) mu += sm[2] - sm[3];
-        shift(mu / (2 * (sm[4] + sm[5])), mu / (2 * (sm[6] + sm[7])));  // :96-99
+        shift(mpc_start_shift2(sm, s.nlb > 0, s.nub > 0));  // :96-99
         wg::sp_project_kernel(s, q.bound_fac);  // :101-118
         WG_SYNC();
         if (s.nlb || s.nub) {
             wg::sp_check_kernel(s, red);  // :120-123
             WG_SYNC();
-            if (red[0] != 0.0) status = ST_INTERNAL;
+            if (red[0] != 0.0) status = MPC_ST_INTERNAL;
             WG_SYNC();
         }
     }
@@ -845,7 +816,7 @@ __global__ __launch_bounds__(TPB) void bq_iter_pre_kernel(BQ q) {
     __shared__ double red[32];
     __shared__ double lds[LDS_DOUBLES];
     const int64_t b = blockIdx.x;
-    if (q.status[b] != ST_ACTIVE) return;
+    if (q.status[b] != MPC_ST_ACTIVE) return;
     const madqp_state s = state_of(q, b);
     const Prob pb = prob_of<WG_SHARED != 0>(q, b);
     double* sc = pb.scal;
@@ -861,31 +832,13 @@ __global__ __launch_bounds__(TPB) void bq_iter_pre_kernel(BQ q) {
     BSTAMP(13);
     wg::inf_kernel(s, red);
     WG_SYNC();
-    const double nc = red[0], nd = red[1];
-    const double ncompl = (red[2] != red[2]) ? red[2] : ((red[3] != red[3]) ? red[3] : fmax(red[2], red[3]));
+    const double nrm[3] = {red[0], red[1], mpc_nanmax(red[2], red[3])};
     WG_SYNC();
-    const double inf_pr = nc / fmax(1.0, sc[S_NORM_B]);        // :264
-    const double inf_du = nd / fmax(1.0, sc[S_NORM_C]);        // :265-271
-    const double inf_compl = ncompl / fmax(1.0, sc[S_NORM_C]);  // :272
-    int status = ST_ACTIVE;
-    if (fmax(inf_pr, fmax(inf_du, inf_compl)) <= q.opt.tol)  // :279
-        status = ST_SOLVED;
-    else if (q.iters[b] >= q.opt.max_iter)
-        status = ST_MAXITER;
+    const MpcHead h = mpc_head(nrm, sc[S_NORM_B], sc[S_NORM_C], q.opt.tol, q.iters[b], q.opt.max_iter);  // :264-283
+    const int status = h.status;
     // update_regularization! (src/kernels.jl:386-417)
-    double del_w, del_c, rp = sc[S_REG_P], rd = sc[S_REG_D];
-    if (q.opt.regularization == 0) {
-        del_w = 0.0;
-        del_c = 0.0;
-    } else if (q.opt.regularization == 1) {
-        del_w = q.opt.delta_p;
-        del_c = q.opt.delta_d;
-    } else {
-        rp = fmax(rp / 10.0, q.opt.delta_min);
-        rd = fmin(rd / 10.0, -q.opt.delta_min);
-        del_w = rp;
-        del_c = rd;
-    }
+    const MpcReg reg = mpc_update_regularization(q.opt.regularization, q.opt.delta_p, q.opt.delta_d, q.opt.delta_min,
+                                                 sc[S_REG_P], sc[S_REG_D]);
     WG_SYNC();
     if (threadIdx.x == 0) {
         // the reference's print_iter line (src/structure.jl:178-195; MPCSolver.record): record number iters[b], before
@@ -894,9 +847,9 @@ __global__ __launch_bounds__(TPB) void bq_iter_pre_kernel(BQ q) {
         if (q.trace && k < q.trace_cap) {
             double* tr = q.trace + (b * q.trace_cap + k) * T_COUNT;
             tr[T_OBJ] = sc[S_OBJ];
-            tr[T_INF_PR] = inf_pr;
-            tr[T_INF_DU] = inf_du;
-            tr[T_INF_COMPL] = inf_compl;
+            tr[T_INF_PR] = h.inf_pr;
+            tr[T_INF_DU] = h.inf_du;
+            tr[T_INF_COMPL] = h.inf_compl;
             tr[T_MU] = sc[S_MU];
             tr[T_DNORM] = (k == 0) ? 0.0 : sc[S_DNORM];
             tr[T_DEL_W] = sc[S_DEL_W];
@@ -905,21 +858,21 @@ __global__ __launch_bounds__(TPB) void bq_iter_pre_kernel(BQ q) {
             tr[T_RATIO] = sc[S_RATIO];
             q.trace_count[b] = (int32_t)(k + 1);
         }
-        sc[S_INF_PR] = inf_pr;
-        sc[S_INF_DU] = inf_du;
-        sc[S_INF_COMPL] = inf_compl;
+        sc[S_INF_PR] = h.inf_pr;
+        sc[S_INF_DU] = h.inf_du;
+        sc[S_INF_COMPL] = h.inf_compl;
         q.status[b] = status;
-        if (status == ST_ACTIVE) {
-            sc[S_DEL_W] = del_w;
-            sc[S_DEL_C] = del_c;
-            sc[S_REG_P] = rp;
-            sc[S_REG_D] = rd;
+        if (status == MPC_ST_ACTIVE) {
+            sc[S_DEL_W] = reg.del_w;
+            sc[S_DEL_C] = reg.del_c;
+            sc[S_REG_P] = reg.run_p;
+            sc[S_REG_D] = reg.run_d;
             sc[S_NFACT] += 1.0;
         }
     }
-    if (status != ST_ACTIVE) return;
+    if (status != MPC_ST_ACTIVE) return;
     // set_aug_diagonal_reg! (src/kernels.jl:128-146)
-    wg::aug_diag_fill_kernel(s, del_w, del_c);
+    wg::aug_diag_fill_kernel(s, reg.del_w, reg.del_c);
     WG_SYNC();
     if (s.nlb) wg::aug_diag_lb_kernel(s);
     WG_SYNC();
@@ -935,7 +888,7 @@ __global__ __launch_bounds__(TPB) void bq_iter_pre_kernel(BQ q) {
 // the next (masked) assembly + Cholesky launches; every other problem sits the round out (retry_skip = 1)
 __global__ __launch_bounds__(TPB) void bq_retry_kernel(BQ q) {
     const int64_t b = blockIdx.x;
-    const bool retry = (q.status[b] == ST_ACTIVE) && (q.info[b] != 0);
+    const bool retry = (q.status[b] == MPC_ST_ACTIVE) && (q.info[b] != 0);
     if (threadIdx.x == 0) {
         q.retry_skip[b] = retry ? 0 : 1;
         if (retry) q.retry_list[atomicAdd(q.retry_count, 1)] = (int32_t)b;  // (the order of the list does not enter any result)
@@ -944,7 +897,7 @@ __global__ __launch_bounds__(TPB) void bq_retry_kernel(BQ q) {
     const madqp_state s = state_of(q, b);
     const Prob pb = prob_of<WG_SHARED != 0>(q, b);
     double* sc = pb.scal;
-    const double del_w = sc[S_DEL_W] * 100.0, del_c = sc[S_DEL_C] * 100.0;  // :14-15
+    const double del_w = mpc_retry(sc[S_DEL_W]), del_c = mpc_retry(sc[S_DEL_C]);  // :14-15
     WG_SYNC();
     if (threadIdx.x == 0) {
         sc[S_DEL_W] = del_w;
@@ -969,49 +922,42 @@ __global__ __launch_bounds__(TPB) void bq_iter_post_kernel(BQ q) {
     __shared__ double red[32];
     __shared__ double lds[LDS_DOUBLES];
     const int64_t b = blockIdx.x;
-    if (q.status[b] != ST_ACTIVE) return;
+    if (q.status[b] != MPC_ST_ACTIVE) return;
     const madqp_state s = state_of(q, b);
     const Prob pb = prob_of<WG_SHARED != 0>(q, b);
     double* sc = pb.scal;
-    int status = ST_ACTIVE;
-    if (q.info[b] != 0) status = ST_STEP_ERROR;  // still not factorized after the three trials of src/linear_solver.jl:7
+    int status = MPC_ST_ACTIVE;
+    if (q.info[b] != 0) status = MPC_ST_STEP_ERROR;  // still not factorized after the three trials of src/linear_solver.jl:7
     double mu = sc[S_MU], alpha_p = 0.0, alpha_d = 0.0, dnorm = 0.0, obj = sc[S_OBJ];
     BSTAMP(14);  // since the end of the pre kernel: assembly + factorisation of the whole batch
-    if (status == ST_ACTIVE) {
+    if (status == MPC_ST_ACTIVE) {
         wg::rhs_kernel(s, 0, 0.0, nullptr);  // set_predictive_rhs! :294
         WG_SYNC();
-        if (!wg_solve_system<!GONDZIO, REFINE>(q, s, pb, lds, red)) status = ST_STEP_ERROR;
+        if (!wg_solve_system<!GONDZIO, REFINE>(q, s, pb, lds, red)) status = MPC_ST_STEP_ERROR;
     }
-    if (status == ST_ACTIVE) {
-        double a_aff_p, a_aff_d;
-        wg_fraction_to_boundary(s, 1.0, red, a_aff_p, a_aff_d);           // :295
-        const double mu_affine = wg_compl(s, 1, a_aff_p, a_aff_d, red);   // :296
+    if (status == MPC_ST_ACTIVE) {
+        const MpcSteps a_aff = wg_fraction_to_boundary(s, 1.0, red);      // :295
+        const double mu_affine = wg_compl(s, 1, a_aff.p, a_aff.d, red);   // :296
         wg::correction_kernel(s);                                         // :297
         WG_SYNC();
         const double mu_curr = wg_compl(s, 0, 0.0, 0.0, red);  // update_barrier! src/kernels.jl:226-236
-        double sigma = 1.0;
-        if (s.nlb + s.nub > 0) {  // (mu_aff / mu)^3 as t*t*t, Julia's literal power (src/kernels.jl:229): the other drivers' bits
-            const double t3 = mu_affine / mu_curr;
-            sigma = fmin(fmax(t3 * t3 * t3, 1e-6), 10.0);
-        }
-        mu = fmax(q.opt.mu_min, sigma * mu_curr);
+        mu = mpc_barrier(mu_affine, mu_curr, (double)(s.nlb + s.nub), q.opt.mu_min, q.opt.step_rule, q.opt.step_param).mu;
         wg::rhs_kernel(s, 1, mu, nullptr);  // set_correction_rhs! :307
         WG_SYNC();
-        if (!wg_solve_system<!GONDZIO, REFINE>(q, s, pb, lds, red, /*keep=*/!GONDZIO)) status = ST_STEP_ERROR;
+        if (!wg_solve_system<!GONDZIO, REFINE>(q, s, pb, lds, red, /*keep=*/!GONDZIO)) status = MPC_ST_STEP_ERROR;
         // gondzio_correction_direction! (src/solver.jl:200-251)
         if constexpr (GONDZIO) {
-            if (status == ST_ACTIVE && q.opt.max_ncorr > 0 && !wg_gondzio<REFINE>(q, b, s, pb, mu_curr, lds, red))
-                status = ST_STEP_ERROR;
+            if (status == MPC_ST_ACTIVE && q.opt.max_ncorr > 0 && !wg_gondzio<REFINE>(q, b, s, pb, mu_curr, lds, red))
+                status = MPC_ST_STEP_ERROR;
         }
     }
-    if (status == ST_ACTIVE) {
+    if (status == MPC_ST_ACTIVE) {
         // update_step! (src/kernels.jl:307-374)
-        if (q.opt.step_rule == 2) {
-            wg_mehrotra_adaptive_step(s, q.opt.step_param, red, alpha_p, alpha_d);
-        } else {
-            const double tau = (q.opt.step_rule == 0) ? q.opt.step_param : fmax(1.0 - mu, q.opt.step_param);
-            wg_fraction_to_boundary(s, tau, red, alpha_p, alpha_d);
-        }
+        const MpcSteps alpha = (q.opt.step_rule == 2)
+                                   ? wg_mehrotra_adaptive_step(s, q.opt.step_param, red)
+                                   : wg_fraction_to_boundary(s, mpc_step_tau(mu, q.opt.step_rule, q.opt.step_param), red);
+        alpha_p = alpha.p;
+        alpha_d = alpha.d;
         wg::norm_inf3_kernel(s.n, s.d, nullptr, nullptr, red);  // print_iter, src/structure.jl:190
         WG_SYNC();
         dnorm = red[0];
@@ -1025,15 +971,14 @@ __global__ __launch_bounds__(TPB) void bq_iter_post_kernel(BQ q) {
             obj = wg_eval_model_incr(q, s, pb, alpha_p, red);  // :338-340 from the last solve's products
         else
             obj = wg_eval_model(q, s, pb, red, lds + 2 * NB);  // :338-340
-        const double eps = 2.220446049250313e-16;
-        if (s.nlb || s.nub) wg::adjust_boundary_kernel(s, eps * mu, 1.8189894035458565e-12, nullptr, nullptr);  // :342
+        if (s.nlb || s.nub) wg::adjust_boundary_kernel(s, mpc_adjust_c1(mu), MPC_ADJUST_C2, nullptr, nullptr);  // :342
         WG_SYNC();
     }
     BSTAMP(15);
     if (threadIdx.x == 0) {
         q.status[b] = status;
-        q.incr_ok[b] = (!GONDZIO && pb.hx && status == ST_ACTIVE) ? 3 : 0;  // bit 0: raw_at / raw_h belong to this step; bit 1: f, c, H x are this x's
-        if (status == ST_ACTIVE) {
+        q.incr_ok[b] = (!GONDZIO && pb.hx && status == MPC_ST_ACTIVE) ? 3 : 0;  // bit 0: raw_at / raw_h belong to this step; bit 1: f, c, H x are this x's
+        if (status == MPC_ST_ACTIVE) {
             sc[S_MU] = mu;
             sc[S_ALPHA_P] = alpha_p;
             sc[S_ALPHA_D] = alpha_d;

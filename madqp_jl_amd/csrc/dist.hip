@@ -986,6 +986,6 @@ extern "C" int32_t madqp_dkkt_eval(madqp_dkkt* k, const madqp_state* st, const d
     } else if ((r = madqp_ctx_sync(ctx))) {
         return r;
     }
-    *obj_host = c0 + sums[0] + 0.5 * sums[1];
+    *obj_host = mpc_objective(c0, sums[0], sums[1]);
     return MADQP_OK;
 }

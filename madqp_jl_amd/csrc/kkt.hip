@@ -1207,7 +1207,7 @@ extern "C" int32_t madqp_kkt_eval(madqp_kkt* k, const madqp_state* st, const dou
     if (r) return r;
     double sums[2] = {0.0, 0.0};
     if ((r = madqp_read_results(k->ctx, 2, sums))) return r;
-    *obj_host = c0 + sums[0] + 0.5 * sums[1];
+    *obj_host = mpc_objective(c0, sums[0], sums[1]);
     return MADQP_OK;
 }
 

@@ -30,8 +30,9 @@
 // ends here has lost one assembly).  The host replays every decision from the block and fails loudly if the device's
 // differ; where the device said "the host takes over" (failed factorisation or verdict, a second Gondzio trial) the
 // iterates have not moved and the round-4 flow continues from the same block.  MADQP_MPC_AHEAD=0: the round-4 form.
-// Same kernels, same arithmetic (mpc_rules.inc: each scalar rule is ONE host+device function, the block's fields are named
-// there once), same order on the stream: the iterates are bitwise those of the sequential form (tests/test_gpu_solver.py).
+// Same kernels, same arithmetic (mpc_rules.inc: each scalar rule is ONE host+device function, which the batched engine
+// calls too, the block's fields are named there once), same order on the stream: the iterates are bitwise those of the
+// sequential form (tests/test_gpu_solver.py).
 // A failed first factorisation (the x100 retries of src/linear_solver.jl:6-17) sends the rest of that iteration down it.
 #include <cmath>
 #include <cstdlib>
@@ -77,34 +78,28 @@ namespace {
 int64_t ntot(const madqp_state& s) { return s.n + s.m + s.nlb + s.nub; }
 
 // src/kernels.jl:386-417
+MpcReg next_regularization(const madqp_mpc* s) {
+    const madqp_mpc_options& o = s->opt;
+    return mpc_update_regularization(o.regularization, o.delta_p, o.delta_d, o.delta_min, s->reg_delta_p, s->reg_delta_d);
+}
 void update_regularization(madqp_mpc* s) {
-    switch (s->opt.regularization) {
-        case 0:
-            s->del_w = 0.0;
-            s->del_c = 0.0;
-            break;
-        case 1:
-            s->del_w = s->opt.delta_p;
-            s->del_c = s->opt.delta_d;
-            break;
-        default:
-            s->reg_delta_p = std::max(s->reg_delta_p / 10.0, s->opt.delta_min);
-            s->reg_delta_d = std::min(s->reg_delta_d / 10.0, -s->opt.delta_min);
-            s->del_w = s->reg_delta_p;
-            s->del_c = s->reg_delta_d;
-    }
+    const MpcReg r = next_regularization(s);
+    s->del_w = r.del_w;
+    s->del_c = r.del_c;
+    s->reg_delta_p = r.run_p;
+    s->reg_delta_d = r.run_d;
 }
 
 // src/linear_solver.jl:6-17
 int32_t factorize_regularized_system(madqp_mpc* s, int first_trial = 0) {
-    for (int trial = first_trial; trial < 3; ++trial) {
+    for (int trial = first_trial; trial < MPC_FACTOR_TRIALS; ++trial) {
         TRY(madqp_kkt_set_aug_diagonal_reg(s->kkt, &s->st, s->del_w, s->del_c));  // dispatched on the KKT type
         TRY(madqp_kkt_build(s->kkt, &s->st));
         TRY(madqp_kkt_factorize(s->kkt, &s->last_info));
         s->n_factorizations += 1;
         if (s->last_info == 0) break;
-        s->del_w *= 100.0;
-        s->del_c *= 100.0;
+        s->del_w = mpc_retry(s->del_w);
+        s->del_c = mpc_retry(s->del_c);
     }
     return MADQP_OK;
 }
@@ -158,73 +153,27 @@ int32_t read_idx(madqp_mpc* s, const int64_t* dptr, int64_t* out) {
 // update_step!(::MehrotraAdaptiveStep), src/kernels.jl:325-374 (scalar reads at the blocking indices)
 int32_t mehrotra_adaptive_step(madqp_mpc* s) {
     const madqp_state& st = s->st;
-    const double gamma_f = s->opt.step_param, gamma_a = 1.0 / (1.0 - gamma_f);
-    double a[4], max_ap, max_ad;
+    double a[4], max_ap, max_ad, mean, row[2][MPC_ROW_LEN] = {};
     int64_t ib[4];
     TRY(fraction_to_boundary(s, 1.0, &max_ap, &max_ad, a, ib));
-    double mu_full;
-    TRY(madqp_get_affine_complementarity_measure(s->ctx, &s->st, max_ap, max_ad, &mu_full));
-    mu_full /= gamma_a;
-    const double* dx = st.d;
-    const double* dzl = st.d + st.n + st.m;
-    const double* dzu = dzl + st.nlb;
-    double alpha_p = 1.0, alpha_d = 1.0;
-    auto at_lb = [&](const double* vec, int64_t i, double* out) {
+    TRY(madqp_get_affine_complementarity_measure(s->ctx, &s->st, max_ap, max_ad, &mean));
+    for (int dual = 0; dual < 2; ++dual) {
+        const int k = mpc_blocking(a, dual);
+        if (k < 0) continue;
+        const bool ub = k & 1;
+        const int64_t i = ib[k];
         int64_t j;
-        int32_t r = read_idx(s, st.ind_lb + i, &j);
-        return r ? r : read1(s, vec + j, out);
-    };
-    auto at_ub = [&](const double* vec, int64_t i, double* out) {
-        int64_t j;
-        int32_t r = read_idx(s, st.ind_ub + i, &j);
-        return r ? r : read1(s, vec + j, out);
-    };
-    if (max_ap < 1.0) {
-        double z, dz, x, b, d;
-        if (a[0] <= a[1]) {
-            const int64_t i = ib[0];
-            TRY(at_lb(st.zl, i, &z));
-            TRY(read1(s, dzl + i, &dz));
-            TRY(at_lb(st.x, i, &x));
-            TRY(at_lb(st.xl, i, &b));
-            TRY(at_lb(dx, i, &d));
-            const double tmp = mu_full / (z + max_ad * dz);
-            alpha_p = (x - b - tmp) / (-d);
-        } else {
-            const int64_t i = ib[1];
-            TRY(at_ub(st.zu, i, &z));
-            TRY(read1(s, dzu + i, &dz));
-            TRY(at_ub(st.x, i, &x));
-            TRY(at_ub(st.xu, i, &b));
-            TRY(at_ub(dx, i, &d));
-            const double tmp = mu_full / (z + max_ad * dz);
-            alpha_p = (b - x - tmp) / d;
-        }
+        TRY(read_idx(s, (ub ? st.ind_ub : st.ind_lb) + i, &j));
+        double* r = row[dual];
+        TRY(read1(s, st.x + j, r + MPC_ROW_X));
+        TRY(read1(s, (ub ? st.xu : st.xl) + j, r + MPC_ROW_BOUND));
+        TRY(read1(s, (ub ? st.zu : st.zl) + j, r + MPC_ROW_Z));
+        TRY(read1(s, st.d + j, r + MPC_ROW_DX));
+        TRY(read1(s, st.d + st.n + st.m + (ub ? st.nlb : 0) + i, r + MPC_ROW_DZ));
     }
-    if (max_ad < 1.0) {
-        double z, dz, x, b, d;
-        if (a[2] <= a[3]) {
-            const int64_t i = ib[2];
-            TRY(at_lb(st.x, i, &x));
-            TRY(at_lb(dx, i, &d));
-            TRY(at_lb(st.xl, i, &b));
-            TRY(at_lb(st.zl, i, &z));
-            TRY(read1(s, dzl + i, &dz));
-            const double tmp = mu_full / (x + max_ap * d - b);
-            alpha_d = -(z - tmp) / dz;
-        } else {
-            const int64_t i = ib[3];
-            TRY(at_ub(st.x, i, &x));
-            TRY(at_ub(dx, i, &d));
-            TRY(at_ub(st.xu, i, &b));
-            TRY(at_ub(st.zu, i, &z));
-            TRY(read1(s, dzu + i, &dz));
-            const double tmp = mu_full / (b - x - max_ap * d);
-            alpha_d = -(z - tmp) / dz;
-        }
-    }
-    s->alpha_p = std::max(alpha_p, gamma_f * max_ap);
-    s->alpha_d = std::max(alpha_d, gamma_f * max_ad);
+    const MpcSteps alpha = mpc_mehrotra_step(a, row[0], row[1], mean, s->opt.step_param);
+    s->alpha_p = alpha.p;
+    s->alpha_d = alpha.d;
     return MADQP_OK;
 }
 
@@ -339,7 +288,7 @@ extern "C" int32_t madqp_mpc_set_scalars(madqp_mpc* s, double mu, double del_w, 
 }
 
 // src/solver.jl:259-283: residuals and the termination test.
-// status_host: 0 = continue, 1 = SOLVE_SUCCEEDED, 6 = MAXIMUM_ITERATIONS_EXCEEDED
+// status_host: MPC_ST_ACTIVE = continue, MPC_ST_SOLVED = SOLVE_SUCCEEDED, MPC_ST_MAXITER = MAXIMUM_ITERATIONS_EXCEEDED
 extern "C" int32_t madqp_mpc_head(madqp_mpc* s, madqp_mpc_info* info_host, int32_t* status_host) {
     if (!s || !status_host) return MADQP_ERR_ARG;
     double nrm[3];
@@ -350,16 +299,12 @@ extern "C" int32_t madqp_mpc_head(madqp_mpc* s, madqp_mpc_info* info_host, int32
         TRY(madqp_get_inf(s->ctx, &s->st, nrm));
         s->n_readbacks += 1;
     }
-    s->inf_pr = nrm[0] / std::max(1.0, s->norm_b);
-    s->inf_du = nrm[1] / std::max(1.0, s->norm_c);
-    s->inf_compl = nrm[2] / std::max(1.0, s->norm_c);
+    const MpcHead h = mpc_head(nrm, s->norm_b, s->norm_c, s->opt.tol, s->k, s->opt.max_iter);
+    s->inf_pr = h.inf_pr;
+    s->inf_du = h.inf_du;
+    s->inf_compl = h.inf_compl;
     fill_info(s, info_host);
-    if (std::max(s->inf_pr, std::max(s->inf_du, s->inf_compl)) <= s->opt.tol)
-        *status_host = 1;
-    else if (s->k >= s->opt.max_iter)
-        *status_host = 6;
-    else
-        *status_host = 0;
+    *status_host = h.status;
     return MADQP_OK;
 }
 
@@ -503,8 +448,8 @@ int32_t body_fused(madqp_mpc* s, madqp_mpc_info* info_host) {
     s->last_info = (int32_t)rb[MPC_SL_INFO];
     if (s->last_info != 0) {  // src/linear_solver.jl:6-17: what was queued behind the failed factorisation is void
         if (went) return differ();
-        s->del_w *= 100.0;
-        s->del_c *= 100.0;
+        s->del_w = mpc_retry(s->del_w);
+        s->del_c = mpc_retry(s->del_c);
         TRY(factorize_regularized_system(s, 1));
         return body_after_factorization(s, info_host);
     }
@@ -552,10 +497,8 @@ int32_t body_fused(madqp_mpc* s, madqp_mpc_info* info_host) {
         // Queue the NEXT iteration's diagonal and assembly before waiting for the norms (see the head of this file) -- not
         // when this pass is the last one allowed, nor when the iterate it started from was already within 100 x the
         // tolerance: the loop then usually ends behind this pass or the next, and the assembly would be for nobody
-        const double worst = std::max(s->inf_pr, std::max(s->inf_du, s->inf_compl));
-        if (s->k + 1 < s->opt.max_iter && !(worst <= 100.0 * s->opt.tol)) {
-            madqp_mpc nx = *s;  // the regularisation of the next pass, from a copy of the scalars
-            update_regularization(&nx);
+        if (mpc_queue_next_assembly({s->inf_pr, s->inf_du, s->inf_compl, MPC_ST_ACTIVE}, s->opt.tol, s->k, s->opt.max_iter)) {
+            const MpcReg nx = next_regularization(s);  // the regularisation of the next pass; the scalars stay
             TRY(madqp_kkt_set_aug_diagonal_reg(s->kkt, &s->st, nx.del_w, nx.del_c));
             TRY(madqp_kkt_build(s->kkt, &s->st));
             s->prebuilt = true;
@@ -570,7 +513,7 @@ int32_t body_fused(madqp_mpc* s, madqp_mpc_info* info_host) {
     s->moved = true;
     s->k += 1;
     s->n_readbacks += 1;
-    s->obj = s->c0 + rb[MPC_SL_OBJ_LIN] + 0.5 * rb[MPC_SL_OBJ_QUAD];
+    s->obj = mpc_objective(s->c0, rb[MPC_SL_OBJ_LIN], rb[MPC_SL_OBJ_QUAD]);
     madqp_inf_from_block(rb + MPC_SL_INF, s->nrm_cached);
     s->head_cached = true;
     fill_info(s, info_host);

@@ -279,7 +279,7 @@ int32_t madqp_q_inf(madqp_ctx* ctx, const madqp_state* st, int slot0) {
 void madqp_inf_from_block(const double* out, double* out3) {
     out3[0] = out[0];
     out3[1] = out[1];
-    out3[2] = (out[2] != out[2]) ? out[2] : ((out[3] != out[3]) ? out[3] : std::max(out[2], out[3]));
+    out3[2] = mpc_nanmax(out[2], out[3]);
 }
 
 extern "C" int32_t madqp_get_inf(madqp_ctx* ctx, const madqp_state* st, double* out_host) {
@@ -302,12 +302,10 @@ extern "C" int32_t madqp_get_inf(madqp_ctx* ctx, const madqp_state* st, double* 
 int32_t madqp_adjust_boundary_dev(madqp_ctx* ctx, const madqp_state* st, double mu, const double* dec_dev,
                                   const double* mu_dev) {
     CHECK_STATE();
-    const double eps = 2.220446049250313e-16;
-    const double c1 = mu_dev ? eps : eps * mu;  // (the kernel multiplies by *mu_dev)
-    const double c2 = 1.8189894035458565e-12;  // eps^(3/4)
+    const double c1 = mu_dev ? MPC_EPS : mpc_adjust_c1(mu);  // (the kernel multiplies by *mu_dev)
     ProfScope ps(ctx, MADQP_PROF_VEC);
     if (std::max(st->nlb, st->nub) > 0)
-        LAUNCH(adjust_boundary_kernel, std::max(st->nlb, st->nub), *st, c1, c2, dec_dev, mu_dev);
+        LAUNCH(adjust_boundary_kernel, std::max(st->nlb, st->nub), *st, c1, MPC_ADJUST_C2, dec_dev, mu_dev);
     return MADQP_OK;
 }
 extern "C" int32_t madqp_adjust_boundary(madqp_ctx* ctx, const madqp_state* st, double mu) {

@@ -88,6 +88,35 @@ def test_batched_options(hip, variant):
         assert np.max(np.abs(r["solution"] - ref["solution"])) <= 1e-7
 
 
+@pytest.mark.parametrize("combo", ["adaptive_step_gondzio3", "mehrotra_step_adaptive_reg", "no_reg_normal_lp"])
+def test_batched_option_combinations(hip, combo):
+    """Options that meet in one scalar rule of the engine, two at a time: AdaptiveStep's tau with three Gondzio trials,
+    MehrotraAdaptiveStep's element reads under AdaptiveRegularization's shrinking pair, and del_w = del_c = 0 in the
+    normal equations of an LP -- problem by problem against the oracle."""
+    family = "lp" if combo == "no_reg_normal_lp" else "wigner"
+    qps = [Q.synthetic_qp(3100 + 13 * i, 40, 16, family) for i in range(4)]
+    kw, okw, form = {}, {}, "condensed"
+    if combo == "adaptive_step_gondzio3":
+        kw = dict(regularization=REG, step_rule=M.AdaptiveStep(0.99), max_ncorr=3)
+        okw = dict(regularization=OREG, step_rule=mpc.AdaptiveStep(0.99), max_ncorr=3)
+    elif combo == "mehrotra_step_adaptive_reg":
+        kw = dict(regularization=M.AdaptiveRegularization(1e-8, -1e-9, 1e-9), step_rule=M.MehrotraAdaptiveStep(0.99))
+        okw = dict(regularization=mpc.AdaptiveRegularization(1e-8, -1e-9, 1e-9), step_rule=mpc.MehrotraAdaptiveStep(0.99))
+    else:
+        form = "normal"
+        kw, okw = dict(regularization=M.NoRegularization()), dict(regularization=mpc.NoRegularization())
+    s = M.BatchedMPCSolver([to_device(q, hip) for q in qps], hip, kkt_system=form, **kw)
+    res = s.solve()
+    s.close()
+    for i, (qp, r) in enumerate(zip(qps, res)):
+        ref = mpc.solve(qp, kkt_system=form, **okw)
+        assert r["status"] == ref["status"] == M.SOLVE_SUCCEEDED, (i, r["status"], ref["status"])
+        assert r["iter"] == ref["iter"], (i, r["iter"], ref["iter"])
+        assert close(r["objective"], ref["objective"], 1e-9), (i, r["objective"], ref["objective"])
+        assert np.max(np.abs(r["solution"] - ref["solution"])) <= 1e-7
+        assert np.max(np.abs(r["multipliers"] - ref["multipliers"])) <= 1e-6
+
+
 def test_batched_is_the_per_problem_driver(hip):
     """Same library, two drivers: the batch and MPCSolver agree problem by problem; a problem that
     breaks down (indefinite H) ends with an error status and leaves the others untouched; a permuted

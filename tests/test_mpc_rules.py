@@ -1,8 +1,7 @@
-"""The result-block layout and the scalar rules of the fused iteration (madqp_jl_amd/csrc/mpc_rules.inc, compiled for the
-CPU by tests/csrc): the functions the native driver (csrc/mpc.hip) and its one-thread kernels (csrc/vec_kernels.hip) both
-call, held to the arithmetic of oracle/mpc.py -- update_barrier, solve_system's verdict, get_fraction_to_boundary_step and
-gondzio_correction_direction (oracle/mpc.py:795-812) -- bit for bit, and to explicit figures on both sides of every
-constant.  No GPU."""
+"""The result-block layout and the scalar rules of an interior-point iteration (madqp_jl_amd/csrc/mpc_rules.inc, compiled for the
+CPU by tests/csrc): the functions both native drivers call -- the host driver (csrc/mpc.hip) with its one-thread kernels
+(csrc/vec_kernels.hip), and the batched engine (csrc/batch_wg.inc) -- held to the arithmetic of oracle/mpc.py bit for bit, to
+explicit figures on both sides of every constant and branch, and to the oracle on non-finite operands.  No GPU."""
 import ctypes as C
 import math
 import os
@@ -357,3 +356,383 @@ def test_decide(lib, layout):
         for gondzio, max_ncorr in ((False, 0), (True, 1), (True, 2)):
             for check in (False, True):
                 assert same_bits(decide(lib, blk, gondzio, max_ncorr, check), ref_decide(layout, blk, gondzio, max_ncorr, check, 1e-8))
+
+
+# ---- the rules the batched engine calls too (csrc/batch_wg.inc), each against the oracle's own method on a stand-in solver --------
+def bind_more(lib):
+    ll = C.c_longlong
+    lib.mpc_nanmax_c.argtypes, lib.mpc_nanmax_c.restype = [C.c_double, C.c_double], C.c_double
+    lib.mpc_head_c.argtypes = [pd, C.c_double, C.c_double, C.c_double, ll, ll, pd]
+    lib.mpc_queue_next_assembly_c.argtypes = [pd, C.c_double, ll, ll]
+    lib.mpc_init_regularization_c.argtypes = [C.c_int, C.c_double, C.c_double, pd]
+    lib.mpc_update_regularization_c.argtypes = [C.c_int] + [C.c_double] * 5 + [pd]
+    lib.mpc_factorize_trials_c.argtypes = [C.c_int, pd]
+    lib.mpc_blocking_c.argtypes = [pd, C.c_int]
+    lib.mpc_mehrotra_step_c.argtypes = [pd, pd, pd, C.c_double, C.c_double, pd]
+    lib.mpc_objective_c.argtypes, lib.mpc_objective_c.restype = [C.c_double] * 3, C.c_double
+    lib.mpc_adjust_c.argtypes = [C.c_double, pd]
+    lib.mpc_start_shifts_c.argtypes = [pd, pd, C.c_int, C.c_int, pd]
+    return lib
+
+
+@pytest.fixture(scope="module")
+def rules(lib):
+    return bind_more(lib)
+
+
+@pytest.fixture(scope="module")
+def O():
+    from oracle import mpc
+    return mpc
+
+
+def same_or_nan(a, b):
+    """same_bits, but a NaN equals any NaN: its sign and payload are the processor's, not the rule's."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.array_equal(np.isnan(a), np.isnan(b)) and same_bits(np.where(np.isnan(a), 0.0, a), np.where(np.isnan(b), 0.0, b))
+
+
+class Stand:
+    """A stand-in for oracle.mpc.MPCSolver that holds only what one method reads."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def test_status_codes_are_the_abis(lib, O):
+    out = (C.c_int * 5)()
+    lib.mpc_status_codes_c(out)
+    assert list(out) == [0, O.SOLVE_SUCCEEDED, O.MAXIMUM_ITERATIONS_EXCEEDED, -3, -1] == [0, 1, 6, -3, -1]
+
+
+# -- iteration_head (oracle/mpc.py:821-833)
+def ref_head(O, nrm, norm_b, norm_c, tol, k, max_iter):
+    s = Stand(kkt=Stand(jtprod=lambda y: np.zeros(1)), y=None, jacl=np.zeros(1), c=np.array([nrm[0]]), f=np.array([nrm[1]]),
+              zl=np.zeros(1), zu=np.zeros(1), norm_b=norm_b, norm_c=norm_c, get_optimality_gap=lambda: f64(nrm[2]),
+              record=lambda: None, opt=Stand(tol=tol, max_iter=max_iter), k=k)
+    with np.errstate(all="ignore"):
+        st = O.MPCSolver.iteration_head(s)
+    return [s.inf_pr, s.inf_du, s.inf_compl], 0 if st is None else st
+
+
+def head(rules, nrm, norm_b, norm_c, tol, k, max_iter):
+    out, po = arr(np.zeros(3))
+    st = rules.mpc_head_c(arr(np.abs(nrm))[1], norm_b, norm_c, tol, k, max_iter, po)
+    return list(out), st
+
+
+def test_head_is_bitwise_the_oracles(rules, O):
+    rng = np.random.default_rng(21)
+    for _ in range(400):
+        nrm = 10.0 ** rng.uniform(-10, -6, 3)
+        norm_b, norm_c = 10.0 ** rng.uniform(-2, 2, 2)  # both sides of max(1, .)
+        k, max_iter = int(rng.integers(0, 4)), int(rng.integers(0, 4))
+        got, ref = head(rules, nrm, norm_b, norm_c, 1e-8, k, max_iter), ref_head(O, nrm, norm_b, norm_c, 1e-8, k, max_iter)
+        assert same_bits(got[0], ref[0]) and got[1] == ref[1]
+
+
+def test_head_on_both_sides_of_its_branches(rules, O):
+    tol = 1e-8
+    above = float(np.nextafter(tol, 1.0))
+    for nrm, k, max_iter, want in (([tol, tol, tol], 0, 10, 1), ([above, tol, tol], 0, 10, 0), ([tol, above, tol], 0, 10, 0),
+                                   ([tol, tol, above], 0, 10, 0), ([above, 0, 0], 10, 10, 6), ([above, 0, 0], 9, 10, 0),
+                                   ([tol, tol, tol], 10, 10, 1), ([0, 0, 0], 0, 0, 1), ([1, 1, 1], 0, 0, 6)):
+        got = head(rules, nrm, 1.0, 1.0, tol, k, max_iter)
+        assert got[1] == want == ref_head(O, nrm, 1.0, 1.0, tol, k, max_iter)[1], (nrm, k, max_iter)
+    # the scale is max(1, norm): norm_b scales the primal residual only, norm_c the other two
+    assert head(rules, [8.0, 8.0, 8.0], 4.0, 0.5, tol, 0, 9) == ([2.0, 8.0, 8.0], 0)
+    assert head(rules, [8.0, 8.0, 8.0], 0.5, 4.0, tol, 0, 9) == ([8.0, 2.0, 2.0], 0)
+
+
+def test_head_with_non_finite_operands(rules, O):
+    """max(inf_pr, inf_du, inf_compl) folds from the left with `>`: a NaN in the first place stays (not solved), one in a
+    later place is passed over -- Python's and std::max's order, which both native drivers now take."""
+    tol = 1e-8
+    table = [([NAN, 0, 0], 0), ([0, NAN, 0], 1), ([0, 0, NAN], 1), ([0, NAN, 1], 0), ([1, NAN, 0], 0), ([NAN, NAN, NAN], 0),
+             ([INF, 0, 0], 0), ([0, INF, 0], 0), ([0, 0, INF], 0), ([NAN, INF, 0], 0)]
+    for nrm, want in table:
+        got, ref = head(rules, nrm, 1.0, 1.0, tol, 0, 10), ref_head(O, nrm, 1.0, 1.0, tol, 0, 10)
+        assert same_bits(got[0], ref[0]) and got[1] == ref[1] == want, (nrm, got, ref)
+        assert head(rules, nrm, 1.0, 1.0, tol, 10, 10)[1] == ref_head(O, nrm, 1.0, 1.0, tol, 10, 10)[1] == (want or 6)
+    for nb, nc in ((NAN, 1.0), (1.0, NAN), (INF, INF), (NAN, NAN)):  # max(1.0, NaN) is 1.0; x / inf is 0
+        got, ref = head(rules, [3.0, 3.0, 3.0], nb, nc, tol, 0, 10), ref_head(O, [3.0, 3.0, 3.0], nb, nc, tol, 0, 10)
+        assert same_bits(got[0], ref[0]) and got[1] == ref[1], (nb, nc)
+    assert head(rules, [INF, 1.0, 1.0], INF, 1.0, tol, 0, 10)[1] == 0  # inf / inf: NaN first, not solved
+    # the optimality gap of the reduction kernels keeps a NaN on either side (np.max does, over the whole list)
+    nm = rules.mpc_nanmax_c
+    assert nm(1.0, 2.0) == 2.0 and nm(2.0, 1.0) == 2.0 and nm(INF, 1.0) == INF and nm(-0.0, 0.0) in (0.0, -0.0)
+    assert math.isnan(nm(NAN, 1.0)) and math.isnan(nm(1.0, NAN)) and math.isnan(nm(NAN, INF))
+    assert all(nm(a, b) == np.max([a, b]) for a, b in np.random.default_rng(1).uniform(0, 1, (50, 2)))
+
+
+def test_next_assembly_is_queued_unless_the_loop_is_about_to_end(rules):
+    q = lambda inf3, k, max_iter: bool(rules.mpc_queue_next_assembly_c(arr(inf3)[1], 1e-8, k, max_iter))
+    edge = 100.0 * 1e-8
+    assert not q([edge, 0, 0], 0, 10) and q([float(np.nextafter(edge, 1.0)), 0, 0], 0, 10)
+    assert q([0, 1.0, 0], 0, 10) and q([0, 0, 1.0], 0, 10) and not q([0, 0, 0], 0, 10)
+    assert q([1.0, 0, 0], 8, 10) and not q([1.0, 0, 0], 9, 10)  # the last pass allowed queues nothing
+    assert q([NAN, 0, 0], 0, 10) and not q([0, NAN, 0], 0, 10) and q([0, NAN, 1.0], 0, 10) and q([INF, 0, 0], 0, 10)
+
+
+# -- init_regularization, update_regularization (oracle/mpc.py:641-655)
+def oracle_reg(O, mode, dp, dd, dmin):
+    return (O.NoRegularization(), O.FixedRegularization(dp, dd), O.AdaptiveRegularization(dp, dd, dmin))[mode]
+
+
+def test_regularization_is_bitwise_the_oracles(rules, O):
+    rng = np.random.default_rng(23)
+    cases = [(10.0 ** rng.uniform(-12, -4), -10.0 ** rng.uniform(-12, -4), 10.0 ** rng.uniform(-12, -6)) for _ in range(60)]
+    # either side of delta_min: the shrinking pair stops at +-delta_min, from exactly 10 delta_min and one ulp around it
+    cases += [(1e-8, -1e-8, 1e-9), (float(np.nextafter(1e-8, 1)), -float(np.nextafter(1e-8, 1)), 1e-9),
+              (float(np.nextafter(1e-8, 0)), -float(np.nextafter(1e-8, 0)), 1e-9), (1e-9, -1e-9, 1e-9), (1e-12, -1e-12, 1e-9),
+              (0.0, 0.0, 0.0), (1e-8, 0.0, 1e-9), (INF, -INF, 1e-9), (NAN, NAN, 1e-9), (1e-8, -1e-8, NAN), (NAN, -1e-8, INF)]
+    for dp, dd, dmin in cases:
+        for mode in (0, 1, 2):
+            reg = oracle_reg(O, mode, dp, dd, dmin)
+            s = Stand(opt=Stand(regularization=reg))
+            out, po = arr(np.zeros(4))
+            rules.mpc_init_regularization_c(mode, dp, dd, po)
+            O.MPCSolver.init_regularization(s)
+            assert same_bits(out, [s.del_w, s.del_c, dp, dd]), (mode, dp, dd)
+            assert s.del_w == 1.0 and (mode != 0 or s.del_c == 0.0)
+            run = out[2:].copy()
+            for _ in range(5):  # the running pair over five passes
+                rules.mpc_update_regularization_c(mode, dp, dd, dmin, run[0], run[1], po)
+                O.MPCSolver.update_regularization(s)
+                want_run = [reg.delta_p, reg.delta_d] if mode == 2 else run
+                assert same_bits(out, [s.del_w, s.del_c] + list(want_run)), (mode, dp, dd, dmin, out)
+                run = out[2:].copy()
+    out, po = arr(np.zeros(4))
+    rules.mpc_update_regularization_c(2, 1e-8, -1e-8, 1e-9, 1e-8, -1e-8, po)
+    assert same_bits(out, [1e-8 / 10.0, -1e-8 / 10.0, 1e-8 / 10.0, -1e-8 / 10.0])
+    rules.mpc_update_regularization_c(2, 1e-8, -1e-8, 1e-9, 5e-9, -5e-9, po)
+    assert same_bits(out, [1e-9, -1e-9, 1e-9, -1e-9])
+    rules.mpc_update_regularization_c(2, 1e-8, -1e-8, 1e-9, NAN, NAN, po)  # max(NaN, x), min(NaN, x): the NaN stays
+    assert np.isnan(out).all()
+    rules.mpc_update_regularization_c(2, 1e-8, -1e-8, NAN, 1e-8, -1e-8, po)  # max(x, NaN), min(x, NaN): x
+    assert same_bits(out, [1e-9, -1e-9, 1e-9, -1e-9])
+
+
+# -- factorize_regularized_system (oracle/mpc.py:663-670)
+def test_retry_is_bitwise_the_oracles(rules, O):
+    rng = np.random.default_rng(27)
+    dels = [tuple(rng.uniform(-1, 1, 2) * 10.0 ** rng.uniform(-12, 0)) for _ in range(40)]
+    dels += [(1e-8, -1e-8), (0.0, -0.0), (1e300, -1e300), (INF, -INF), (NAN, 1.0), (1.0, NAN)]
+    for dw, dc in dels:
+        for failures in range(5):  # 0 .. 2 failed trials go on; from 3 the third is the last all the same
+            calls = []
+            kkt = Stand(build_and_factorize=lambda: calls.append(1), is_factorized=lambda: len(calls) > failures)
+            s = Stand(del_w=f64(dw), del_c=f64(dc), kkt=kkt, set_aug_diagonal_reg=lambda: None)
+            with np.errstate(all="ignore"):
+                O.MPCSolver.factorize_regularized_system(s)
+            d2, p2 = arr([dw, dc])
+            n = rules.mpc_factorize_trials_c(failures, p2)
+            assert n == len(calls) == min(failures + 1, 3) and same_bits(d2, [s.del_w, s.del_c]), (dw, dc, failures)
+    d2, p2 = arr([1e-8, -1e-8])
+    assert rules.mpc_factorize_trials_c(1, p2) == 2 and same_bits(d2, [1e-8 * 100.0, -1e-8 * 100.0])
+
+
+# -- update_step, the MehrotraAdaptiveStep branch (oracle/mpc.py:616-639)
+def ref_mehrotra(O, a4, ib, lb, ub, mean, gamma_f):
+    """lb, ub: dicts of the arrays the branch reads over the lower / the upper bounds (x, b, z, dx, dz)."""
+    s = Stand(opt=Stand(step_rule=O.MehrotraAdaptiveStep(gamma_f)), d=Stand(zl=lb["dz"], zu=ub["dz"]),
+              get_alpha_max_primal=lambda tau: (a4[0], a4[1], ib[0], ib[1]),
+              get_alpha_max_dual=lambda tau: (a4[2], a4[3], ib[2], ib[3]),
+              get_affine_complementarity_measure=lambda ap, ad: f64(mean),
+              zl_r=lb["z"], x_lr=lb["x"], xl_r=lb["b"], dx_lr=lb["dx"], zu_r=ub["z"], x_ur=ub["x"], xu_r=ub["b"], dx_ur=ub["dx"])
+    with np.errstate(all="ignore"):
+        O.MPCSolver.update_step(s)
+    return [s.alpha_p, s.alpha_d]
+
+
+def mehrotra(rules, a4, ib, lb, ub, mean, gamma_f):
+    """The drivers' part: the rows at the blocking indices mpc_blocking names, then the rule."""
+    rows = np.full((2, 5), -77.0)  # (a row the rule must not read where its step is free)
+    for dual in (0, 1):
+        k = rules.mpc_blocking_c(arr(a4)[1], dual)
+        assert k in (-1, 2 * dual, 2 * dual + 1)
+        if k >= 0:
+            t = ub if k & 1 else lb
+            rows[dual] = [t[key][ib[k]] for key in ("x", "b", "z", "dx", "dz")]
+    out, po = arr(np.zeros(2))
+    rules.mpc_mehrotra_step_c(arr(a4)[1], arr(rows[0])[1], arr(rows[1])[1], mean, gamma_f, po)
+    return list(out)
+
+
+def bound_arrays(rng, n, upper):
+    x, gap = rng.uniform(-2, 2, n), 10.0 ** rng.uniform(-6, 0, n)
+    return dict(x=x, b=x + gap if upper else x - gap, z=10.0 ** rng.uniform(-6, 1, n), dx=rng.uniform(-1, 1, n),
+                dz=rng.uniform(-1, 1, n))
+
+
+def test_mehrotra_step_is_bitwise_the_oracles(rules, O):
+    rng = np.random.default_rng(29)
+    for it in range(600):
+        lb, ub = bound_arrays(rng, 5, False), bound_arrays(rng, 5, True)
+        a4 = [float(v) if rng.random() < 0.7 else 1.0 for v in rng.uniform(0, 1, 4)]  # 1.0: nothing blocks on that side
+        if it % 7 == 0:
+            a4[1], a4[3] = a4[0], a4[2]  # ties go to the lower bound
+        ib = [int(rng.integers(0, 5)) if a < 1.0 else -1 for a in a4]
+        mean, gamma_f = 10.0 ** rng.uniform(-9, 1), float(rng.choice([0.99, 0.9, 0.5]))
+        assert same_bits(mehrotra(rules, a4, ib, lb, ub, mean, gamma_f), ref_mehrotra(O, a4, ib, lb, ub, mean, gamma_f)), (a4, ib)
+
+
+def test_mehrotra_step_on_both_sides_of_its_branches(rules, O):
+    one = lambda x, b, z, dx, dz: dict(x=np.array([x]), b=np.array([b]), z=np.array([z]), dx=np.array([dx]), dz=np.array([dz]))
+    lb, ub = one(1.0, 0.0, 2.0, -4.0, -3.0), one(1.0, 3.0, 2.0, 5.0, -6.0)
+    below = float(np.nextafter(1.0, 0.0))
+    blocking = lambda a4, dual: rules.mpc_blocking_c(arr(a4)[1], dual)
+    assert [blocking([1.0, 1.0, 1.0, 1.0], d) for d in (0, 1)] == [-1, -1]              # nothing below 1: both steps free
+    assert [blocking([below, 1.0, 1.0, below], d) for d in (0, 1)] == [0, 3]            # one ulp below: lower / upper
+    assert [blocking([0.5, 0.5, 0.25, 0.25], d) for d in (0, 1)] == [0, 2]              # a tie is the lower bound's
+    assert [blocking([0.5, float(np.nextafter(0.5, 0)), 0.25, float(np.nextafter(0.25, 0))], d) for d in (0, 1)] == [1, 3]
+    assert [blocking([NAN, 0.5, 0.5, NAN], d) for d in (0, 1)] == [-1, 3]  # min(NaN, x) is NaN: free; min(x, NaN) is x, NaN <= x false
+    for a4, ib in (([1.0, 1.0, 1.0, 1.0], [-1] * 4), ([0.5, 1.0, 1.0, 1.0], [0, -1, -1, -1]), ([1.0, 0.5, 1.0, 1.0], [-1, 0, -1, -1]),
+                   ([1.0, 1.0, 0.5, 1.0], [-1, -1, 0, -1]), ([1.0, 1.0, 1.0, 0.5], [-1, -1, -1, 0]), ([0.5, 0.5, 0.25, 0.25], [0] * 4),
+                   ([0.25, 0.5, 0.5, 0.25], [0] * 4), ([below, 1.0, below, 1.0], [0, -1, 0, -1])):
+        for mean in (0.0, 1e-3, 10.0):  # (a large mean: the blocking formula falls below gamma_f max_alpha, the floor wins)
+            got = mehrotra(rules, a4, ib, lb, ub, mean, 0.99)
+            assert same_bits(got, ref_mehrotra(O, a4, ib, lb, ub, mean, 0.99)), (a4, mean, got)
+    # figures: gamma_a = 1 / (1 - 0.5) = 2, mu_full = 0.8 / 2 = 0.4; primal at the lower bound: tmp = 0.4 / (2 + 0.5 * -3) = 0.8,
+    # alpha_p = (1 - 0 - 0.8) / 4 = 0.05 < 0.5 * 0.25: the floor; dual at the upper: tmp = 0.4 / (3 - 1 - 0.25 * 5) = 0.5333..,
+    # alpha_d = -(2 - tmp) / -6
+    got = mehrotra(rules, [0.25, 1.0, 1.0, 0.5], [0, -1, -1, 0], lb, ub, 0.8, 0.5)
+    tmp = 0.4 / (3.0 - 1.0 - 0.25 * 5.0)
+    assert same_bits(got, [0.125, max(-(2.0 - tmp) / -6.0, 0.25)]) and got[1] == 0.25
+    got = mehrotra(rules, [0.25, 1.0, 1.0, 0.5], [0, -1, -1, 0], lb, ub, 0.08, 0.5)
+    tmp = 0.04 / (3.0 - 1.0 - 0.25 * 5.0)  # a tenth of the mean: both formulas lie above their floors
+    assert same_bits(got, [(1.0 - 0.04 / (2.0 + 0.5 * -3.0)) / 4.0, -(2.0 - tmp) / -6.0]) and got[0] > 0.125 and got[1] > 0.25
+
+
+def test_mehrotra_step_with_non_finite_operands(rules, O):
+    """max(alpha, gamma_f max_alpha) keeps a NaN alpha (its first operand), as the oracle and the host driver always did."""
+    one = lambda x, b, z, dx, dz: dict(x=np.array([x]), b=np.array([b]), z=np.array([z]), dx=np.array([dx]), dz=np.array([dz]))
+    a4, ib = [0.5, 1.0, 0.25, 1.0], [0, -1, 0, -1]
+    ub = one(1.0, 3.0, 2.0, 5.0, -6.0)
+    for pos in range(5):
+        for bad in (NAN, INF, -INF, 0.0):
+            v = [1.0, 0.0, 2.0, -4.0, -3.0]
+            v[pos] = bad
+            for mean in (1e-3, NAN, INF, 0.0):
+                got = mehrotra(rules, a4, ib, one(*v), ub, mean, 0.99)
+                assert same_or_nan(got, ref_mehrotra(O, a4, ib, one(*v), ub, mean, 0.99)), (pos, bad, mean, got)
+    got = mehrotra(rules, a4, ib, one(1.0, 0.0, 0.0, 0.0, 0.0), ub, 0.0, 0.99)  # 0 / 0 in both formulas: no floor under a NaN
+    assert same_or_nan(got, ref_mehrotra(O, a4, ib, one(1.0, 0.0, 0.0, 0.0, 0.0), ub, 0.0, 0.99)) and np.isnan(got).all()
+    got = mehrotra(rules, a4, ib, one(1.0, 0.0, 2.0, 0.0, 0.0), ub, 0.0, 0.99)  # x / -0 and -x / 0: -inf, the floors
+    assert same_bits(got, [0.99 * 0.5, 0.99 * 0.25])
+    got = mehrotra(rules, a4, ib, one(NAN, 0.0, 2.0, -4.0, -3.0), ub, 1e-3, 0.99)
+    assert math.isnan(got[0]) and math.isnan(got[1])
+    for gamma_f in (NAN, 0.0):  # gamma_a = NaN, or 1: no floor (gamma_f = 1 divides by zero, which the oracle refuses)
+        got = mehrotra(rules, a4, ib, one(1.0, 0.0, 2.0, -4.0, -3.0), ub, 1e-3, gamma_f)
+        assert same_or_nan(got, ref_mehrotra(O, a4, ib, one(1.0, 0.0, 2.0, -4.0, -3.0), ub, 1e-3, gamma_f))
+    assert same_or_nan(mehrotra(rules, [1.0] * 4, [-1] * 4, ub, ub, NAN, 0.99), [1.0, 1.0])  # no bound blocks: the mean is not read
+
+
+# -- the objective and adjust_boundary (oracle/mpc.py:189-196)
+def test_objective_and_adjust_boundary_constants(rules, O):
+    rng = np.random.default_rng(31)
+    for c0, lin, quad in rng.uniform(-1, 1, (100, 3)) * 10.0 ** rng.uniform(-3, 3, (100, 1)):
+        assert same_bits(rules.mpc_objective_c(c0, lin, quad), f64(c0) + f64(lin) + 0.5 * f64(quad))
+    for t in ((NAN, 1, 1), (1, NAN, 1), (1, 1, NAN), (INF, -INF, 1), (1, INF, -INF), (INF, 1, 1)):
+        with np.errstate(invalid="ignore"):
+            assert same_bits(rules.mpc_objective_c(*map(float, t)), f64(t[0]) + f64(t[1]) + 0.5 * f64(t[2]))
+    out, po = arr(np.zeros(2))
+    for mu in list(10.0 ** rng.uniform(-11, 0, 50)) + [0.0, 1e-11, 0.1, INF, NAN]:
+        rules.mpc_adjust_c(float(mu), po)
+        assert same_bits(out, [O.EPS * f64(mu), O.EPS ** 0.75])
+    # ... and they are the two the oracle's adjust_boundary acts on: a bound at distance c1 stays, one ulp nearer it moves by c2 max(1, |x|)
+    mu = 0.1
+    rules.mpc_adjust_c(mu, po)
+    c1, c2 = out
+    for x in (0.25, -7.5):
+        # (bounds an exact power-of-two multiple of c1 away, so that x - xl is that distance to the bit)
+        xl, xu = np.array([x - 2 * c1 * 2.0 ** 52, x - c1 * 2.0 ** 51]), np.array([x + 2 * c1 * 2.0 ** 52, x + c1 * 2.0 ** 51])
+        xs = np.array([x, x])
+        want_l, want_u = xl.copy(), xu.copy()
+        for j in range(2):
+            if xs[j] - xl[j] < c1:
+                want_l[j] = xl[j] - c2 * max(1.0, abs(xs[j]))
+            if xu[j] - xs[j] < c1:
+                want_u[j] = xu[j] + c2 * max(1.0, abs(xs[j]))
+        O.adjust_boundary(xs, xl, xu, np.arange(2), np.arange(2), mu)
+        assert same_bits(xl, want_l) and same_bits(xu, want_u)
+    xs, xl, xu = np.array([1.0, 1.0, 4.0]), np.array([1.0 - 1e-3, 1.0, 4.0]), np.array([2.0, 1.0, 4.0])
+    O.adjust_boundary(xs, xl, xu, np.arange(3), np.arange(3), mu)
+    assert same_bits(xl, [1.0 - 1e-3, 1.0 - c2, 4.0 - c2 * 4.0]) and same_bits(xu, [2.0, 1.0 + c2, 4.0 + c2 * 4.0])
+
+
+# -- init_starting_point's two shifts (oracle/mpc.py:711-726)
+def ref_start_shifts(x, l, u, zl, zu, ilb, iub):
+    """oracle/mpc.py:711-726, line for line, on copies; returns the four shifts and what the rule is given: the four minima
+    before the first shift and the eight sums behind it (csrc/vec_kernels.inc: sp_mins_kernel, sp_sums_kernel)."""
+    x, zl, zu = x.copy(), zl.copy(), zu.copy()
+    mn = [np.min(x[ilb] - l[ilb], initial=0.0), np.min(u[iub] - x[iub], initial=0.0), np.min(zl[ilb], initial=0.0),
+          np.min(zu[iub], initial=0.0)]
+    delta_x = max(0.0, -1.5 * np.min(x[ilb] - l[ilb], initial=0.0), -1.5 * np.min(u[iub] - x[iub], initial=0.0))
+    delta_s = max(0.0, -1.5 * np.min(zl[ilb], initial=0.0), -1.5 * np.min(zu[iub], initial=0.0))
+    x[ilb] = x[ilb] + delta_x
+    x[iub] = x[iub] - delta_x
+    zl[ilb] += 1.0 + delta_s
+    zu[iub] += 1.0 + delta_s
+    sm = [x[ilb] @ zl[ilb], l[ilb] @ zl[ilb], u[iub] @ zu[iub], x[iub] @ zu[iub], np.sum(zl[ilb]), np.sum(zu[iub]),
+          np.sum(x[ilb] - l[ilb]), np.sum(u[iub] - x[iub])]
+    mu = 0.0
+    if len(ilb) > 0:
+        mu += x[ilb] @ zl[ilb] - l[ilb] @ zl[ilb]
+    if len(iub) > 0:
+        mu += u[iub] @ zu[iub] - x[iub] @ zu[iub]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        delta_x2 = np.float64(mu) / (2 * (np.sum(zl[ilb]) + np.sum(zu[iub])))
+        delta_s2 = np.float64(mu) / (2 * (np.sum(x[ilb] - l[ilb]) + np.sum(u[iub] - x[iub])))
+    return [delta_x, 1.0 + delta_s, delta_x2, delta_s2], mn, sm
+
+
+def start_shifts(rules, mn, sm, has_lb, has_ub):
+    out, po = arr(np.zeros(4))
+    rules.mpc_start_shifts_c(arr(mn)[1], arr(sm)[1], int(has_lb), int(has_ub), po)
+    return out
+
+
+def test_start_shifts_are_bitwise_the_oracles(rules):
+    rng = np.random.default_rng(33)
+    for it in range(300):
+        n = 9
+        ilb = np.flatnonzero(rng.random(n) < (0.0 if it % 10 == 0 else 0.7))  # every tenth: no lower bound / no upper bound / none
+        iub = np.flatnonzero(rng.random(n) < (0.0 if it % 10 in (1, 0) and it % 20 < 10 else 0.7))
+        x = rng.uniform(-2, 2, n)
+        shift = rng.uniform(-0.5, 1.5, n) if it % 3 else rng.uniform(0.1, 1.5, n)  # x outside its bounds or all inside
+        l, u = x - shift, x + rng.uniform(-0.5, 1.5, n) if it % 3 else x + rng.uniform(0.1, 1.5, n)
+        zl = rng.uniform(-1, 1, n) if it % 2 else rng.uniform(0.1, 1, n)
+        zu = rng.uniform(-1, 1, n) if it % 2 else rng.uniform(0.1, 1, n)
+        want, mn, sm = ref_start_shifts(x, l, u, zl, zu, ilb, iub)
+        assert same_bits(start_shifts(rules, mn, sm, len(ilb) > 0, len(iub) > 0), want), (it, mn, sm)
+
+
+def test_start_shifts_on_both_sides_of_their_branches(rules):
+    sm = [3.0, 1.0, 7.0, 2.0, 0.5, 1.5, 0.25, 0.75]
+    ss = lambda mn, lb=True, ub=True, s=sm: start_shifts(rules, mn, s, lb, ub)
+    assert same_bits(ss([0.0, 0.0, 0.0, 0.0])[:2], [0.0, 1.0])                   # all inside: nothing moves (max(0.0, -0.0, -0.0) is 0.0)
+    assert same_bits(ss([-2.0, 0.0, 0.0, -4.0])[:2], [3.0, 7.0])                 # 1.5 times the worst violation, on either side
+    assert same_bits(ss([0.0, -2.0, -4.0, 0.0])[:2], [3.0, 7.0])
+    assert same_bits(ss([-2.0, -3.0, -1.0, -0.5])[:2], [4.5, 2.5])
+    assert same_bits(ss([-5e-324, 0.0, 0.0, 0.0])[:2], [-1.5 * -5e-324, 1.0])
+    # the second pair: mu over twice the sums, each side's part only where that side has bounds
+    assert same_bits(ss([0] * 4)[2:], [7.0 / (2 * 2.0), 7.0 / (2 * 1.0)])
+    assert same_bits(ss([0] * 4, ub=False)[2:], [2.0 / (2 * 2.0), 2.0 / (2 * 1.0)])
+    assert same_bits(ss([0] * 4, lb=False)[2:], [5.0 / (2 * 2.0), 5.0 / (2 * 1.0)])
+    got = ss([0] * 4, lb=False, ub=False, s=[0.0] * 8)                           # no bound at all: 0 / 0
+    assert same_bits(got[:2], [0.0, 1.0]) and np.isnan(got[2:]).all()
+    # non-finite operands: max(0.0, a, b) passes a NaN over in either place; an infinite violation is an infinite shift
+    py = lambda mn: [max(0.0, -1.5 * f64(mn[0]), -1.5 * f64(mn[1])), 1.0 + max(0.0, -1.5 * f64(mn[2]), -1.5 * f64(mn[3]))]
+    for mn in ([NAN, -2.0, 0, 0], [-2.0, NAN, 0, 0], [NAN, NAN, NAN, NAN], [0, 0, NAN, -2.0], [0, 0, -2.0, NAN], [-INF, 0, 0, -INF],
+               [NAN, 0.0, 0.0, NAN]):
+        assert same_bits(ss(mn)[:2], py(mn)), mn
+    assert same_bits(ss([NAN, -2.0, -2.0, NAN])[:2], [3.0, 4.0]) and same_bits(ss([NAN] * 4)[:2], [0.0, 1.0])
+    for k in range(8):
+        for bad in (NAN, INF, -INF):
+            s2 = list(sm)
+            s2[k] = bad
+            with np.errstate(invalid="ignore", divide="ignore"):
+                mu = (f64(s2[0]) - f64(s2[1])) + (f64(s2[2]) - f64(s2[3]))
+                want = [mu / (2 * (f64(s2[4]) + f64(s2[5]))), mu / (2 * (f64(s2[6]) + f64(s2[7])))]
+            assert same_bits(ss([0] * 4, s=s2)[2:], want), (k, bad)
