@@ -25,7 +25,7 @@
 // factor_block) on a CholTarget -- one matrix (madqp_chol_factor), a batch of small matrices at fixed strides (madqp_chol_factor_batched)
 // or a panel of the multi-GPU loop (madqp_chol_factor_panel, ...); ONE panel solve of a 128-column block (madqp_chol_panel_solve), shared with the
 // mid-size schedule (factor_mid) and dist.hip; the environment is read in one place (CholModes).
-// The handle (struct madqp_chol, common.h): ONE owner of its device buffers (DevOwner: destroy is a synchronise and a delete,
+// The handle (struct madqp_chol, below): ONE owner of its device buffers (DevOwner: destroy is a synchronise and a delete,
 // the paths that must leave the handle usable release what they allocated), ONE way to take a matrix (adopt_matrix) and to
 // forget its factor (forget_factor: the solves refuse while there is no matrix -- the handle keeps no record of whether a
 // factorisation succeeded), ONE description of a solve's sweeps (Sweeps) and ONE launcher of their three kernel forms
@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "common.h"
+#include "panel_image.h"
 #include "band_plan.inc"
 #include "mid_plan.inc"
 #include "solve_plan.inc"
@@ -56,7 +57,8 @@ constexpr int64_t SOLVE_MANY_MIN_DEFAULT = 32;
 #define P2_LDS_LD (NB + 1)
 #endif
 constexpr int LDS_LD = P2_LDS_LD;
-constexpr int64_t WBLK = 2 * NB * NB;  // doubles per block in chol->winv: [Wcm | Wrm]
+static_assert(IMG_NB == NB, "panel_image.h describes this file's blocks");
+constexpr int64_t WBLK = IMG_WBLK;  // doubles per block in chol->winv: [Wcm | Wrm], the form they travel in (panel_image.h)
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 #include "gemm_core.inc"
@@ -1369,7 +1371,66 @@ static const CholModes& chol_modes() {  // filled once, at the first use
     return m;
 }
 
-// ---- the handle (struct madqp_chol: common.h) ----------------------------------------------------------------------------
+// ---- the handle --------------------------------------------------------------------------------------------------------
+// The band state of a Cholesky handle (madqp_chol_set_bandwidth, madqp_chol_set_packed; band_plan.inc), cleared
+// (chol.hip: band_clear) and committed as one
+struct madqp_chol_band {
+    int64_t bw = -1;      // half-bandwidth (-1: none, the dense schedules and sweeps)
+    int64_t extent = 0;   // of the plan: the largest i - j the factorisation touches; n - 1 without a band
+    bool packed = false;  // packed band storage: the lda of a factorisation is the packed leading dimension (>= extent)
+    // the sweeps under the band (MADQP_SWEEP_BAND): blocks a block row reads left of its diagonal block (-1: the dense
+    // sweeps), and the band's own job list where the dense sweeps have one
+    int64_t sweep_kb = -1;
+    int32_t* d_jobs = nullptr;
+    int32_t njobs = 0;
+};
+// The plan of the mid-size schedule (chol.hip: mid_plan_build): which trailing tiles each block step updates, with which
+// panels; built at the first factorisation that asks for it
+struct MidPlan {
+    int32_t state = 0;                  // 0 not built, 1 in use, -1 no plan (the left-looking schedule runs)
+    std::vector<int32_t> count, first;  // per step: its number of units, and where they start in d_units
+    uint32_t* d_units = nullptr;        // the packed units of all steps (mid_plan.inc)
+};
+
+struct madqp_chol {
+    madqp_ctx* ctx = nullptr;
+    int64_t n = 0;
+    DevOwner mem;            // every device buffer below is this owner's
+    double* winv = nullptr;  // ceil(n/128) blocks of 128x128 (col-major, ld 128): inverse diagonal blocks
+    // The scratch of a solve, one buffer: [x | y | partial-sum slots of the forward sweep | of the backward sweep].  A solve
+    // on L fills and uses the tmp_len doubles from y on (y: its intermediate vector); a solve with U = L' the utmp_len
+    // doubles from x on (x: the polled copy of its solution), filled by one kernel.  sweep_x == nullptr: the buffer starts
+    // at y, no solve of this handle runs on U (one block, or more than 160).
+    double* sweep_x = nullptr;
+    double* sweep_y = nullptr;
+    int64_t tmp_len = 0, utmp_len = 0;
+    int32_t* d_jobs = nullptr;  // sweep job list (chol.hip SweepPlan), nullptr when every block row is one job
+    int32_t sweep_chunk = 0, sweep_maxc = 0, sweep_njobs = 0;
+    bool sweep_band = false;  // MADQP_SWEEP_BAND of this handle: under a bandwidth the sweeps stay inside the band
+    madqp_chol_band band;
+    // the left-looking plan for the current (bandwidth, npos) (chol_plan.inc; chol.hip: handle_plan); empty: not built, or none needed yet
+    std::vector<CholOp> plan;
+    int32_t* d_info = nullptr;  // [0] info, [1..2] sweep tickets
+    // the last matrix handed to a factorisation (borrowed; chol.hip: adopt_matrix) -- nullptr: none, or forgotten
+    // (forget_factor), and the solves refuse with MADQP_ERR_STATE.  Whether that factorisation succeeded is the caller's
+    // knowledge, not the handle's.
+    double* A = nullptr;
+    int64_t lda = 0;
+    int64_t npos = 0;  // quasi-definite mode (madqp_chol_set_signature): A = L diag(I_npos, -I) L'; npos == n: Cholesky
+    MidPlan mid;
+    // the backward sweep on U = L' (chol.hip, trsv_fwd_sweep_kernel<true>): U of the last mid-size factorisation (order
+    // npad, allocated at the first one)
+    double* upper = nullptr;
+    int64_t upper_ld = 0;
+    bool upper_ok = false;  // the last factorisation left U
+    // madqp_chol_solve_many: the transposed block of right-hand sides and, without U, the strip of one block row of L'
+    // (solve_plan.inc: solve_plan_workspace), grown at the first call that needs more; from many_min right-hand sides on
+    // the call takes the blocked path
+    double* many_ws = nullptr;
+    int64_t many_ws_len = 0;
+    int64_t many_min = 0;  // (madqp_chol_create: the measured default)
+};
+
 // back to "no band"; frees the band's job list, which nothing on the stream may still read
 static hipError_t band_clear(madqp_chol* s) {
     const hipError_t e = s->mem.free_one(&s->band.d_jobs);
@@ -1846,15 +1907,14 @@ int32_t madqp_chol_factor_batched(madqp_ctx* ctx, double* A, int64_t lda, int64_
 // ---------------------------------------------------------------------------------------------
 // Pieces of the factorisation for the multi-GPU path: the diagonal tile of a step of the 2-D block-cyclic
 // Cholesky (dist.hip: dop_potrf_tile) is an order-nb matrix the distributed object owns -- factor_begin adopts it,
-// factor_panel runs the blocked factorisation on it, panel_pack lays out [info | inverse diagonal blocks | L] for the
-// broadcast.  All asynchronous on the context's stream.
+// factor_panel runs the blocked factorisation on it, pack_image lays out [info | inverse diagonal blocks | L] for the
+// broadcast (madqp_chol_pack_diag: the diagonal part, what dist.hip takes; madqp_chol_panel_pack: every row below too).
+// All asynchronous on the context's stream.
 namespace {
 __global__ void info_store_kernel(const int32_t* __restrict__ info, double* __restrict__ hdr) {
     hdr[0] = (double)*info;
     hdr[1] = 0.0;
 }
-constexpr int64_t PACK_HDR = 2;  // doubles: [info, 0] (keeps the payload 16-byte aligned)
-
 bool panel_ok(const madqp_chol* s, int64_t j0, int64_t w) {
     return s->A && j0 >= 0 && w > 0 && j0 % NB == 0 && j0 + w <= s->n && (w % NB == 0 || j0 + w == s->n);
 }
@@ -1879,22 +1939,25 @@ extern "C" int32_t madqp_chol_factor_panel(madqp_chol* s, int64_t j0, int64_t w)
     return r ? r : sweep_images(s, s->A, s->lda, j0, w);  // (the caller packs / reads the images of this panel next)
 }
 
-// buf = [info, 0 | inverse diagonal blocks of the panel | L[j0:n, j0+c] for c = 0..w-1]
-extern "C" int32_t madqp_chol_panel_pack(madqp_chol* s, int64_t j0, int64_t w, double* buf) {
+// buf = [info, 0 | inverse diagonal blocks of the panel | L[j0:j0+rows, j0+c] for c = 0..w-1] (panel_image.h)
+static int32_t pack_image(madqp_chol* s, int64_t j0, int64_t w, int64_t rows, double* buf) {
     if (!s) return MADQP_ERR_ARG;
     madqp_ctx* ctx = s->ctx;
     ARG_TRY(ctx, panel_ok(s, j0, w) && buf);
     ProfScope ps(ctx, MADQP_PROF_VEC);
-    const int64_t nblk = (w + NB - 1) / NB, rows = s->n - j0;
     hipLaunchKernelGGL(info_store_kernel, dim3(1), dim3(1), 0, ctx->stream, s->d_info, buf);
     LAUNCH_CHECK(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(buf + PACK_HDR, s->winv + (j0 / NB) * WBLK, nblk * WBLK * sizeof(double),
+    HIP_TRY(ctx, hipMemcpyAsync(buf + IMG_HDR, s->winv + (j0 / NB) * WBLK, img_blocks(w) * sizeof(double),
                                 hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpy2DAsync(buf + PACK_HDR + nblk * WBLK, rows * sizeof(double),
-                                  s->A + j0 + j0 * s->lda, s->lda * sizeof(double), rows * sizeof(double),
-                                  (size_t)w, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpy2DAsync(buf + img_L(w), rows * sizeof(double), s->A + j0 + j0 * s->lda, s->lda * sizeof(double),
+                                  rows * sizeof(double), (size_t)w, hipMemcpyDeviceToDevice, ctx->stream));
     return MADQP_OK;
 }
+extern "C" int32_t madqp_chol_panel_pack(madqp_chol* s, int64_t j0, int64_t w, double* buf) {
+    return pack_image(s, j0, w, s ? s->n - j0 : 0, buf);  // every row from the panel's first down
+}
+int32_t madqp_chol_pack_diag(madqp_chol* s, int64_t j0, int64_t w, double* buf) { return pack_image(s, j0, w, w, buf); }
+int64_t madqp_chol_order(const madqp_chol* s) { return s ? s->n : -1; }
 
 // ---- the sweeps of one solve, described once: madqp_chol_solve (both of its paths) and madqp_trsv_tile build this and launch
 // through launch_sweep ----

@@ -297,61 +297,8 @@ int32_t madqp_chol_panel_solve(madqp_ctx* ctx, double* X, int64_t ldx, int64_t r
 int32_t madqp_trsv_tile(madqp_ctx* ctx, int32_t trans, const double* L, int64_t ld, const double* winv, double* v,
                         int64_t w, double* tmp, int32_t* ctl);
 
-// The band state of a Cholesky handle (madqp_chol_set_bandwidth, madqp_chol_set_packed; band_plan.inc), cleared
-// (chol.hip: band_clear) and committed as one
-struct madqp_chol_band {
-    int64_t bw = -1;      // half-bandwidth (-1: none, the dense schedules and sweeps)
-    int64_t extent = 0;   // of the plan: the largest i - j the factorisation touches; n - 1 without a band
-    bool packed = false;  // packed band storage: the lda of a factorisation is the packed leading dimension (>= extent)
-    // the sweeps under the band (MADQP_SWEEP_BAND): blocks a block row reads left of its diagonal block (-1: the dense
-    // sweeps), and the band's own job list where the dense sweeps have one
-    int64_t sweep_kb = -1;
-    int32_t* d_jobs = nullptr;
-    int32_t njobs = 0;
-};
-// The plan of the mid-size schedule (chol.hip: mid_plan_build): which trailing tiles each block step updates, with which
-// panels; built at the first factorisation that asks for it
-struct MidPlan {
-    int32_t state = 0;                  // 0 not built, 1 in use, -1 no plan (the left-looking schedule runs)
-    std::vector<int32_t> count, first;  // per step: its number of units, and where they start in d_units
-    uint32_t* d_units = nullptr;        // the packed units of all steps (mid_plan.inc)
-};
-
-struct madqp_chol {
-    madqp_ctx* ctx = nullptr;
-    int64_t n = 0;
-    DevOwner mem;            // every device buffer below is this owner's
-    double* winv = nullptr;  // ceil(n/128) blocks of 128x128 (col-major, ld 128): inverse diagonal blocks
-    // The scratch of a solve, one buffer: [x | y | partial-sum slots of the forward sweep | of the backward sweep].  A solve
-    // on L fills and uses the tmp_len doubles from y on (y: its intermediate vector); a solve with U = L' the utmp_len
-    // doubles from x on (x: the polled copy of its solution), filled by one kernel.  sweep_x == nullptr: the buffer starts
-    // at y, no solve of this handle runs on U (one block, or more than 160).
-    double* sweep_x = nullptr;
-    double* sweep_y = nullptr;
-    int64_t tmp_len = 0, utmp_len = 0;
-    int32_t* d_jobs = nullptr;  // sweep job list (chol.hip SweepPlan), nullptr when every block row is one job
-    int32_t sweep_chunk = 0, sweep_maxc = 0, sweep_njobs = 0;
-    bool sweep_band = false;  // MADQP_SWEEP_BAND of this handle: under a bandwidth the sweeps stay inside the band
-    madqp_chol_band band;
-    // the left-looking plan for the current (bandwidth, npos) (chol_plan.inc; chol.hip: handle_plan); empty: not built, or none needed yet
-    std::vector<struct CholOp> plan;
-    int32_t* d_info = nullptr;  // [0] info, [1..2] sweep tickets
-    // the last matrix handed to a factorisation (borrowed; chol.hip: adopt_matrix) -- nullptr: none, or forgotten
-    // (forget_factor), and the solves refuse with MADQP_ERR_STATE.  Whether that factorisation succeeded is the caller's
-    // knowledge, not the handle's.
-    double* A = nullptr;
-    int64_t lda = 0;
-    int64_t npos = 0;  // quasi-definite mode (madqp_chol_set_signature): A = L diag(I_npos, -I) L'; npos == n: Cholesky
-    MidPlan mid;
-    // the backward sweep on U = L' (chol.hip, trsv_fwd_sweep_kernel<true>): U of the last mid-size factorisation (order
-    // npad, allocated at the first one)
-    double* upper = nullptr;
-    int64_t upper_ld = 0;
-    bool upper_ok = false;  // the last factorisation left U
-    // madqp_chol_solve_many: the transposed block of right-hand sides and, without U, the strip of one block row of L'
-    // (solve_plan.inc: solve_plan_workspace), grown at the first call that needs more; from many_min right-hand sides on
-    // the call takes the blocked path
-    double* many_ws = nullptr;
-    int64_t many_ws_len = 0;
-    int64_t many_min = 0;  // (madqp_chol_create: the measured default)
-};
+// chol.hip, for the grid path (dist.hip), which knows the handle by these alone: its order, and the packed image
+// (panel_image.h) of the DIAGONAL part of a factored panel -- buf = [info, 0 | inverse blocks of the panel |
+// L(j0:j0+w, j0:j0+w), leading dimension w].  j0 = 0, w = n: what madqp_chol_panel_pack writes.
+int64_t madqp_chol_order(const madqp_chol* s);
+int32_t madqp_chol_pack_diag(madqp_chol* s, int64_t j0, int64_t w, double* buf);

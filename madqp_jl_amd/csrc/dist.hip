@@ -2,7 +2,7 @@
 // configs[4]) -- the HIP / RCCL instantiation of dist_core.inc (schedule and layout are described there).
 //
 // Rank-local kernels: the MFMA GEMM core (gemm_f64.hip) for the panel solves and the trailing updates, the diagonal
-// tile through the blocked Cholesky of chol.hip (factor_begin / factor_panel / panel_pack on an order-nb object), the
+// tile through the blocked Cholesky of chol.hip (factor_begin / factor_panel / pack_diag on an order-nb object), the
 // tile solves through the sweep kernels of chol.hip, GEMVs of gemv.hip.  Collectives: RCCL (ncclBroadcast / ncclReduce
 // / ncclAllReduce on the world communicator and on row / column communicators made with ncclCommSplit), resolved at
 // run time from the RCCL the process already has (torch's) -- or, when the caller hands in `madqp_comm_ops`, its
@@ -14,6 +14,7 @@
 
 #include "grid_kernels.h"
 #include "kkt_form.inc"
+#include "panel_image.h"
 
 namespace {
 struct Rccl {
@@ -77,7 +78,8 @@ struct Dev {
     madqp_chol* chol_last;  // order of the (partial) last tile, or nullptr
     madqp_chol* chol_full;  // order n (P == 1): whole panels through the one-GPU panel factorisation, or nullptr
     int64_t nb, wlast;
-    int32_t* ctl;           // 4 ints: tile sweeps
+    DevOwner mem;
+    int32_t* ctl;           // 4 ints: tile sweeps (mem's)
     bool two_streams;
     int prof_cls;           // timer class of the masked GEMM (panel updates, or the assembly)
 };
@@ -144,29 +146,30 @@ __global__ void dist_info_store_kernel(const double* info, double* hdr) {
     hdr[0] = *info;
     hdr[1] = 0.0;
 }
-__global__ void dist_info_merge_kernel(double* info, const double* hdr) {
-    if (*info == 0.0 && hdr[0] != 0.0) *info = hdr[0];
-}
+// a header's info, relative to column col0 + 1 (col0 = 0: global already), becomes global and is merged into *info
 __global__ void dist_info_global_kernel(double* hdr, double col0, double* info) {
-    if (hdr[0] != 0.0) hdr[0] += col0;  // tile-relative (1-based) -> global column
+    if (hdr[0] != 0.0) hdr[0] += col0;
     if (*info == 0.0 && hdr[0] != 0.0) *info = hdr[0];
 }
-__global__ __launch_bounds__(256) void dist_vsub_kernel(double* a, const double* b, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) a[i] -= b[i];
+MQ_KERNEL dist_vsub_kernel(double* a, const double* b, int64_t n) {
+    GRID_STRIDE(i, n) a[i] -= b[i];
 }
 // out[i] = loc[((I0 + i/nb) div R) nb + i mod nb] when tile I0 + i/nb belongs to residue r (mod R), else 0
-__global__ __launch_bounds__(256) void dist_group_pack_kernel(double* __restrict__ out, const double* __restrict__ loc,
-                                                              int64_t I0, int64_t wg, int64_t nb, int64_t R, int64_t r) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < wg; i += (int64_t)gridDim.x * 256) {
+MQ_KERNEL dist_group_pack_kernel(double* __restrict__ out, const double* __restrict__ loc, int64_t I0, int64_t wg, int64_t nb,
+                                 int64_t R, int64_t r) {
+    GRID_STRIDE(i, wg) {
         const int64_t I = I0 + i / nb;
         out[i] = (I % R == r) ? loc[(I / R) * nb + i % nb] : 0.0;
     }
 }
 int32_t dop_group_pack(Dev* dev, double* out, const double* loc, int64_t I0, int64_t wg, int64_t nb, int64_t R, int64_t r) {
-    if (wg <= 0) return 0;
-    hipLaunchKernelGGL(dist_group_pack_kernel, dim3((unsigned)std::min<int64_t>((wg + 255) / 256, 1024)), dim3(256), 0,
-                       dev->ctx->stream, out, loc, I0, wg, nb, R, r);
-    LAUNCH_CHECK(dev->ctx);
+    madqp_ctx* ctx = dev->ctx;
+    if (wg > 0) LAUNCH(dist_group_pack_kernel, wg, out, loc, I0, wg, nb, R, r);
+    return 0;
+}
+int32_t dop_vsub(Dev* dev, double* a, const double* b, int64_t n) {
+    madqp_ctx* ctx = dev->ctx;
+    if (n > 0) LAUNCH(dist_vsub_kernel, n, a, b, n);
     return 0;
 }
 int32_t dop_info_store(Dev* dev, const double* info, double* hdr) {
@@ -174,18 +177,12 @@ int32_t dop_info_store(Dev* dev, const double* info, double* hdr) {
     LAUNCH_CHECK(dev->ctx);
     return 0;
 }
-int32_t dop_info_merge(Dev* dev, double* info, const double* hdr) {
-    hipLaunchKernelGGL(dist_info_merge_kernel, dim3(1), dim3(1), 0, dev->ctx->stream, info, hdr);
+int32_t dop_info_global(Dev* dev, double* hdr, int64_t col0, double* info) {
+    hipLaunchKernelGGL(dist_info_global_kernel, dim3(1), dim3(1), 0, dev->ctx->stream, hdr, (double)col0, info);
     LAUNCH_CHECK(dev->ctx);
     return 0;
 }
-int32_t dop_vsub(Dev* dev, double* a, const double* b, int64_t n) {
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL(dist_vsub_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0,
-                       dev->ctx->stream, a, b, n);
-    LAUNCH_CHECK(dev->ctx);
-    return 0;
-}
+int32_t dop_info_merge(Dev* dev, double* info, double* hdr) { return dop_info_global(dev, hdr, 0, info); }
 
 // ---- rank-local linear algebra
 // C = beta C + alpha X Y' on the 128-tiles (ti, tj) with ti >= row0[tj]
@@ -212,48 +209,32 @@ int32_t dop_gemm(Dev* dev, double* C, int64_t ldc, const double* Cin, int64_t ld
     return madqp_gemm_tn(dev->ctx, g, dev->prof_cls);
 }
 
-// Cholesky of the w x w diagonal tile at T (in place); buf <- [info, 0 | inverse 128-blocks | L (w x w, ld w)];
-// info: the tile's first failing column as a GLOBAL 1-based column (col0 = columns before the tile), merged into *info
+// Columns [j0, j0 + w) of the matrix at A through the blocked Cholesky of handle s (begin, panel, pack);
+// buf <- [info, 0 | inverse 128-blocks | L(j0:j0+w, j0:j0+w), ld w] (panel_image.h), its info -- relative to column
+// col0 + 1 -- made global and merged into *info
+int32_t factor_and_pack(Dev* dev, madqp_chol* s, double* A, int64_t ld, int64_t j0, int64_t w, double* buf, int64_t col0,
+                        double* info) {
+    int32_t r;
+    if ((r = madqp_chol_factor_begin(s, A, ld))) return r;
+    if ((r = madqp_chol_factor_panel(s, j0, w))) return r;
+    if ((r = madqp_chol_pack_diag(s, j0, w, buf))) return r;
+    return dop_info_global(dev, buf, col0, info);
+}
+// Cholesky of the w x w diagonal tile at T (in place); col0 = the columns before the tile
 int32_t dop_potrf_tile(Dev* dev, double* T, int64_t ld, int64_t w, double* buf, int64_t col0, double* info) {
     madqp_chol* s = (w == dev->nb) ? dev->chol_nb : dev->chol_last;
-    if (!s || s->n != w) return madqp_fail(dev->ctx, MADQP_ERR_STATE, "no Cholesky object for a tile of order %lld", (long long)w);
-    int32_t r;
-    if ((r = madqp_chol_factor_begin(s, T, ld))) return r;
-    if ((r = madqp_chol_factor_panel(s, 0, w))) return r;
-    if ((r = madqp_chol_panel_pack(s, 0, w, buf))) return r;
-    hipLaunchKernelGGL(dist_info_global_kernel, dim3(1), dim3(1), 0, dev->ctx->stream, buf, (double)col0, info);
-    LAUNCH_CHECK(dev->ctx);
-    return 0;
+    if (!s || madqp_chol_order(s) != w)
+        return madqp_fail(dev->ctx, MADQP_ERR_STATE, "no Cholesky object for a tile of order %lld", (long long)w);
+    return factor_and_pack(dev, s, T, ld, 0, w, buf, col0, info);
 }
-
 // P == 1: the panel of step k -- local column block lc, rows from k nb down -- is factored, solved and updated inside by
-// the one-GPU panel factorisation; buf <- [info, 0 | inverse 128-blocks | L_kk (w x w, ld w)], info (LAPACK's, global
-// column) merged into *info
-__global__ void dist_info_from_int_kernel(const int32_t* chol_info, double* hdr, double* info) {
-    hdr[0] = (double)*chol_info;
-    hdr[1] = 0.0;
-    if (*info == 0.0 && hdr[0] != 0.0) *info = hdr[0];
-}
+// the one-GPU panel factorisation, whose info is LAPACK's (a global column)
 int32_t dop_panel_local(Dev* dev, double* K, int64_t ld, int64_t lc, int64_t k, int64_t nb, int64_t w, double* buf,
                         double* info) {
-    madqp_chol* s = dev->chol_full;
-    madqp_ctx* ctx = dev->ctx;
-    if (!s) return madqp_fail(ctx, MADQP_ERR_STATE, "no order-n Cholesky object (P == 1 expected)");
+    if (!dev->chol_full) return madqp_fail(dev->ctx, MADQP_ERR_STATE, "no order-n Cholesky object (P == 1 expected)");
     // the factorisation addresses a column by its GLOBAL index j0 = k nb: shift the base so that this is local block lc
     // (only the columns of the panel are touched)
-    double* base = K + (lc - k) * nb * ld;
-    int32_t r;
-    if ((r = madqp_chol_factor_begin(s, base, ld))) return r;
-    if ((r = madqp_chol_factor_panel(s, k * nb, w))) return r;
-    const int64_t nblk = (w + 127) / 128;
-    hipLaunchKernelGGL(dist_info_from_int_kernel, dim3(1), dim3(1), 0, ctx->stream, s->d_info, buf, info);
-    LAUNCH_CHECK(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(buf + 2, s->winv + (k * nb / 128) * (2 * 128 * 128), (size_t)nblk * 2 * 128 * 128 * sizeof(double),
-                                hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpy2DAsync(buf + 2 + nblk * 2 * 128 * 128, (size_t)w * sizeof(double), K + k * nb + lc * nb * ld,
-                                  (size_t)ld * sizeof(double), (size_t)w * sizeof(double), (size_t)w, hipMemcpyDeviceToDevice,
-                                  ctx->stream));
-    return 0;
+    return factor_and_pack(dev, dev->chol_full, K + (lc - k) * nb * ld, ld, k * nb, w, buf, 0, info);
 }
 
 // X (rows x w, leading dimension ldx) <- X L^-T with the images W of L's diagonal 128-blocks (recursive, MFMA)
@@ -261,7 +242,7 @@ int32_t trsm_range(Dev* dev, double* X, int64_t ldx, int64_t rows, int64_t rread
                    const double* W, int64_t j0, int64_t wd) {
     if (wd <= 128)  // one block: block substitution (chol.hip); only the last tile has a short block, and no tile rows below it
         return madqp_chol_panel_solve(dev->ctx, X + j0 * ldx, ldx, rows, rread, L + j0 + j0 * ldl, ldl,
-                                      W + (j0 / 128) * (2 * 128 * 128), wd);
+                                      W + (j0 / IMG_NB) * IMG_WBLK, wd);
     const int64_t h = ((wd + 127) / 128 + 1) / 2 * 128;
     int32_t r = trsm_range(dev, X, ldx, rows, rread, L, ldl, W, j0, h);
     if (r) return r;
@@ -415,7 +396,6 @@ void dev_destroy(Dev* dev) {
     if (dev->chol_nb) madqp_chol_destroy(dev->chol_nb);
     if (dev->chol_last) madqp_chol_destroy(dev->chol_last);
     if (dev->chol_full) madqp_chol_destroy(dev->chol_full);
-    if (dev->ctl) (void)hipFree(dev->ctl);
     for (auto& e : dev->ev)
         if (e) (void)hipEventDestroy(e);
     if (dev->ev_main) (void)hipEventDestroy(dev->ev_main);
@@ -457,8 +437,7 @@ extern "C" int32_t madqp_dist_create(madqp_ctx* ctx, int32_t rank, int32_t world
     ARG_TRY(ctx, !ops || (ops->bcast && ops->reduce_sum && ops->allreduce_sum && ops->send && ops->recv));
     Dev* dev = new (std::nothrow) Dev();
     if (!dev) return madqp_fail(ctx, MADQP_ERR_ALLOC, "host allocation failed");
-    memset(dev, 0, sizeof(*dev));
-    dev->ctx = ctx;
+    dev->ctx = dev->mem.ctx = ctx;
     dev->main = ctx->stream;
     dev->nb = nb;
     dev->prof_cls = MADQP_PROF_POTRF_GEMM;
@@ -467,6 +446,7 @@ extern "C" int32_t madqp_dist_create(madqp_ctx* ctx, int32_t rank, int32_t world
     static const int two = getenv("MADQP_DIST_STREAMS") ? atoi(getenv("MADQP_DIST_STREAMS")) : 1;
     dev->two_streams = two != 0 && !ops;  // host-staged collectives synchronise anyway
     hipError_t e = hipMalloc(&dev->ctl, 4 * sizeof(int32_t));
+    if (e == hipSuccess) dev->mem.owned.push_back(dev->ctl);  // (this call's own error text: not DevOwner::alloc)
     if (e == hipSuccess && dev->two_streams) {
         e = hipStreamCreateWithFlags(&dev->sP, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&dev->sU, hipStreamNonBlocking);
@@ -505,7 +485,7 @@ extern "C" int32_t madqp_dist_create(madqp_ctx* ctx, int32_t rank, int32_t world
         }
         nccl_id128 = &own_id;
     }
-    if ((world > 1 || d->force_comm) && !ops) {  // RCCL: world communicator, then one per process row / column
+    if (!distcore::single_rank(d) && !ops) {  // RCCL: world communicator, then one per process row / column
         if (!rccl().ok) {
             madqp_dist_destroy(d);
             return madqp_fail(ctx, MADQP_ERR_STATE, "RCCL is not available in this process (librccl.so)");
@@ -544,8 +524,7 @@ extern "C" int32_t madqp_dist_create(madqp_ctx* ctx, int32_t rank, int32_t world
 
 extern "C" int32_t madqp_dist_layout(madqp_dist* d, int64_t* out8) {
     if (!d || !out8) return MADQP_ERR_ARG;
-    const int64_t v[8] = {d->p, d->q, d->mt, d->nt, d->mloc, d->nloc, d->ld, d->ncp};
-    memcpy(out8, v, sizeof(v));
+    distcore::layout8(d, out8);
     return MADQP_OK;
 }
 
@@ -599,9 +578,7 @@ extern "C" int32_t madqp_dist_comm_info(madqp_dist* d, int64_t* out8) {
 // solve bands | broadcast images, staging and vectors | levels of the operand staircases | 0)
 extern "C" int32_t madqp_dist_memory(madqp_dist* d, int64_t* out8) {
     if (!d || !out8) return MADQP_ERR_ARG;
-    const int64_t v[8] = {d->bytes_total, d->bytes_K, 8 * d->xw_count, 8 * d->yw_count, d->bytes_band, d->bytes_stage,
-                          d->nlev, 0};
-    memcpy(out8, v, sizeof(v));
+    distcore::memory8(d, out8);
     return MADQP_OK;
 }
 
@@ -651,26 +628,23 @@ __global__ __launch_bounds__(256) void dk_add_diag_kernel(int64_t ntile, const i
     }
 }
 // local-row order <-> global order: out_loc[li*nb + r] = x[(li*R + res)*nb + r]
-__global__ __launch_bounds__(256) void dk_gather_kernel(int64_t cnt, int64_t nb, int64_t R, int64_t res, int64_t n,
-                                                        const double* __restrict__ x, double* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * 256) {
+MQ_KERNEL dk_gather_kernel(int64_t cnt, int64_t nb, int64_t R, int64_t res, int64_t n, const double* __restrict__ x,
+                           double* __restrict__ out) {
+    GRID_STRIDE(i, cnt) {
         const int64_t g = ((i / nb) * R + res) * nb + i % nb;
         out[i] = (g < n) ? x[g] : 0.0;
     }
 }
-__global__ __launch_bounds__(256) void dk_scatter_add_kernel(int64_t cnt, int64_t nb, int64_t R, int64_t res, int64_t n,
-                                                             const double* __restrict__ loc, double alpha,
-                                                             double* __restrict__ y) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * 256) {
+MQ_KERNEL dk_scatter_add_kernel(int64_t cnt, int64_t nb, int64_t R, int64_t res, int64_t n, const double* __restrict__ loc,
+                                double alpha, double* __restrict__ y) {
+    GRID_STRIDE(i, cnt) {
         const int64_t g = ((i / nb) * R + res) * nb + i % nb;
         if (g < n) y[g] += alpha * loc[i];
     }
 }
 // w = alpha * g + beta * w  (beta == 0: w is not read)
-__global__ __launch_bounds__(256) void dk_axpby_kernel(int64_t n, double alpha, const double* __restrict__ g, double beta,
-                                                       double* __restrict__ w) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        w[i] = (beta == 0.0) ? alpha * g[i] : alpha * g[i] + beta * w[i];
+MQ_KERNEL dk_axpby_kernel(int64_t n, double alpha, const double* __restrict__ g, double beta, double* __restrict__ w) {
+    GRID_STRIDE(i, n) w[i] = (beta == 0.0) ? alpha * g[i] : alpha * g[i] + beta * w[i];
 }
 }  // namespace
 
@@ -769,29 +743,17 @@ static int32_t dk_check(madqp_dkkt* k, const madqp_state* st) {
 }
 
 // partial products of the blocks this rank owns, accumulated into the all-reduce buffers (which the caller zeroed):
-//   gn += alpha A' u (u: m),   gm += alpha A x (x: global order),   gn += alpha H x
-static int32_t dk_At_partial(madqp_dkkt* k, double alpha, const double* u) {
+//   trans = 1: gn += alpha A' v (v: m),   trans = 0: gm += alpha A v (v: global order),   dk_H_partial: gn += alpha H x
+static int32_t dk_A_partial(madqp_dkkt* k, int32_t trans, double alpha, const double* v) {
     madqp_dist* d = k->d;
+    double* out = trans ? k->gn : k->gm;
     if (!k->m) return MADQP_OK;
     if (d->P == 1 && d->Q == 1)  // one rank owns every block, local order = global order: one product
-        return madqp_gemv_impl(k->ctx, 1, k->m, d->n, alpha, k->AI, k->ldai, u, 1.0, k->gn, MADQP_PROF_GEMV);
+        return madqp_gemv_impl(k->ctx, trans, k->m, d->n, alpha, k->AI, k->ldai, v, 1.0, out, MADQP_PROF_GEMV);
     for (int64_t li : k->own_li) {
-        const int64_t I = li * d->P + d->p, w = distcore::tsize(d, I);
-        int32_t r = madqp_gemv_impl(k->ctx, 1, k->m, w, alpha, k->AI + li * d->nb, k->ldai, u, 1.0, k->gn + I * d->nb,
-                                    MADQP_PROF_GEMV);
-        if (r) return r;
-    }
-    return MADQP_OK;
-}
-static int32_t dk_A_partial(madqp_dkkt* k, double alpha, const double* x) {
-    madqp_dist* d = k->d;
-    if (!k->m) return MADQP_OK;
-    if (d->P == 1 && d->Q == 1)
-        return madqp_gemv_impl(k->ctx, 0, k->m, d->n, alpha, k->AI, k->ldai, x, 1.0, k->gm, MADQP_PROF_GEMV);
-    for (int64_t li : k->own_li) {
-        const int64_t I = li * d->P + d->p, w = distcore::tsize(d, I);
-        int32_t r = madqp_gemv_impl(k->ctx, 0, k->m, w, alpha, k->AI + li * d->nb, k->ldai, x + I * d->nb, 1.0, k->gm,
-                                    MADQP_PROF_GEMV);
+        const int64_t I = li * d->P + d->p, off = I * d->nb;  // the block's place in the vector of length n
+        int32_t r = madqp_gemv_impl(k->ctx, trans, k->m, distcore::tsize(d, I), alpha, k->AI + li * d->nb, k->ldai,
+                                    trans ? v : v + off, 1.0, trans ? out + off : out, MADQP_PROF_GEMV);
         if (r) return r;
     }
     return MADQP_OK;
@@ -807,7 +769,7 @@ static int32_t dk_H_partial(madqp_dkkt* k, double alpha, const double* x) {
     // the diagonal may hold anything -- the Julia glue's COO map never fills them): in the row-major view of the
     // mat-vec kernels that is the side c >= r, so it is madqp_symv_upper, which reads nothing else (the
     // first version called madqp_symv_lower here and read exactly the tiles a rank is NOT required to hold).
-    if (d->world == 1 && !d->force_comm && d->n >= 2048 && (((uintptr_t)k->H) & 15) == 0 && k->ldh % 2 == 0)
+    if (distcore::single_rank(d) && d->n >= 2048 && (((uintptr_t)k->H) & 15) == 0 && k->ldh % 2 == 0)
         return madqp_symv_upper(ctx, d->n, alpha, k->H, k->ldh, x, 1.0, k->gn, MADQP_PROF_GEMV);
     {
         ProfScope ps(ctx, MADQP_PROF_VEC);
@@ -817,14 +779,14 @@ static int32_t dk_H_partial(madqp_dkkt* k, double alpha, const double* x) {
     }
     for (int64_t lj = 0; lj < d->nt; ++lj) {
         const int64_t J = lj * d->Q + d->q, w = distcore::tsize(d, J);
-        const int64_t li0 = (J > d->p) ? (J - d->p + d->P - 1) / d->P : 0;  // first local tile row with I >= J
+        bool has_diag = false;  // the diagonal tile is the first one of the panel
+        const int64_t li0 = distcore::first_lower(d, J, &has_diag);
         if (li0 >= d->mt) continue;
         const double* Pn = k->H + li0 * nb + lj * nb * k->ldh;
         const int64_t rows = d->mloc - li0 * nb;
         int32_t r = madqp_gemv_impl(ctx, 1, w, rows, 1.0, Pn, k->ldh, x + J * nb, 1.0, k->yr + li0 * nb, MADQP_PROF_GEMV);
         if (r) return r;
-        const bool has_diag = (li0 * d->P + d->p == J);  // the diagonal tile is the first one of the panel
-        const int64_t skip = has_diag ? nb : 0;          // its transpose part is already in the product above
+        const int64_t skip = has_diag ? nb : 0;  // its transpose part is already in the product above
         if (rows - skip > 0) {
             r = madqp_gemv_impl(ctx, 0, w, rows - skip, 1.0, Pn + skip, k->ldh, k->xr + li0 * nb + skip, 1.0,
                                 k->yc + lj * nb, MADQP_PROF_GEMV);
@@ -834,10 +796,6 @@ static int32_t dk_H_partial(madqp_dkkt* k, double alpha, const double* x) {
     ProfScope ps(ctx, MADQP_PROF_VEC);
     LAUNCH(dk_scatter_add_kernel, d->mloc, d->mloc, nb, (int64_t)d->P, (int64_t)d->p, d->n, k->yr, alpha, k->gn);
     LAUNCH(dk_scatter_add_kernel, d->nloc, d->nloc, nb, (int64_t)d->Q, (int64_t)d->q, d->n, k->yc, alpha, k->gn);
-    return MADQP_OK;
-}
-static int32_t dk_zero(madqp_dkkt* k, double* ptr, int64_t count) {
-    if (count > 0) HIP_TRY(k->ctx, hipMemsetAsync(ptr, 0, (size_t)count * sizeof(double), k->ctx->stream));
     return MADQP_OK;
 }
 
@@ -855,7 +813,7 @@ extern "C" int32_t madqp_dkkt_build(madqp_dkkt* k, const madqp_state* st) {
             // one rank: A_I and A_J are the same columns, so K = H + S'S with ONE operand stream S = sqrt(Theta) A
             // (what the one-GPU assembly does, gemm_f64.hip); several ranks: K_loc = H_loc + A_I' (Theta A_J)
             hipLaunchKernelGGL(dk_scale_rows_kernel, dim3(gx, (unsigned)k->m16), dim3(256), 0, ctx->stream, k->m, d->ncp,
-                               k->AJ, k->ldaj, k->theta, k->SJ, d->ncp, (d->world == 1 && !d->force_comm) ? 1 : 0);
+                               k->AJ, k->ldaj, k->theta, k->SJ, d->ncp, distcore::single_rank(d) ? 1 : 0);
             LAUNCH_CHECK(ctx);
         }
     }
@@ -869,8 +827,10 @@ extern "C" int32_t madqp_dkkt_build(madqp_dkkt* k, const madqp_state* st) {
                                           (size_t)d->nloc, ctx->stream));
     } else {
         d->dev->prof_cls = MADQP_PROF_SYRK;
-        const bool one = (d->world == 1 && !d->force_comm);  // (ld == ncp on a 1 x 1 grid)
-        r = distcore::assemble_product(d, k->H, k->ldh, one ? k->SJ : k->AI, one ? d->ncp : k->ldai, k->SJ, d->ncp, k->m16);
+        if (distcore::single_rank(d))  // (ld == ncp on a 1 x 1 grid)
+            r = distcore::assemble_product(d, k->H, k->ldh, k->SJ, d->ncp, k->SJ, d->ncp, k->m16);
+        else
+            r = distcore::assemble_product(d, k->H, k->ldh, k->AI, k->ldai, k->SJ, d->ncp, k->m16);
         d->dev->prof_cls = MADQP_PROF_POTRF_GEMM;
         if (r) return r;
     }
@@ -903,14 +863,14 @@ extern "C" int32_t madqp_dkkt_solve(madqp_dkkt* k, const madqp_state* st, double
             ProfScope ps(ctx, MADQP_PROF_VEC);
             LAUNCH(condense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, wx, wy, k->t, k->u);
         }
-        if ((r = dk_zero(k, k->gn, k->nx)) || (r = dk_At_partial(k, 1.0, k->u))) return r;
+        if ((r = dop_zero(k->d->dev, k->gn, k->nx)) || (r = dk_A_partial(k, 1, 1.0, k->u))) return r;
         if ((r = distcore::comm_allreduce(d, k->gn, k->nx, GRP_WORLD))) return r;
         ProfScope ps(ctx, MADQP_PROF_VEC);
         LAUNCH(dk_axpby_kernel, k->nx, k->nx, 1.0, k->gn, 1.0, wx);  // rhs_x = r1_x + A' (theta t)
     }
     if ((r = madqp_dist_solve(d, wx))) return r;
     if (k->m) {
-        if ((r = dk_zero(k, k->gm, k->m)) || (r = dk_A_partial(k, 1.0, wx))) return r;
+        if ((r = dop_zero(k->d->dev, k->gm, k->m)) || (r = dk_A_partial(k, 0, 1.0, wx))) return r;
         if ((r = distcore::comm_allreduce(d, k->gm, k->m, GRP_WORLD))) return r;
         ProfScope ps(ctx, MADQP_PROF_VEC);
         LAUNCH(decondense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, k->t, k->gm, wx, wy);
@@ -924,7 +884,7 @@ extern "C" int32_t madqp_dkkt_jtprod(madqp_dkkt* k, double* out, const double* y
     madqp_ctx* ctx = k->ctx;
     ARG_TRY(ctx, (out || k->nx + k->ns == 0) && (y || k->m == 0));
     int32_t r;
-    if ((r = dk_zero(k, k->gn, k->nx)) || (r = dk_At_partial(k, 1.0, y))) return r;
+    if ((r = dop_zero(k->d->dev, k->gn, k->nx)) || (r = dk_A_partial(k, 1, 1.0, y))) return r;
     if ((r = distcore::comm_allreduce(k->d, k->gn, k->nx, GRP_WORLD))) return r;
     ProfScope ps(ctx, MADQP_PROF_VEC);
     if (k->nx) LAUNCH(dk_axpby_kernel, k->nx, k->nx, 1.0, k->gn, 0.0, out);
@@ -941,8 +901,8 @@ extern "C" int32_t madqp_dkkt_mul(madqp_dkkt* k, const madqp_state* st, double* 
     ARG_TRY(ctx, w && v);
     const int64_t nx = k->nx, n = st->n;
     // gn = A' vy + H vx, gm = A vx: one all-reduce of n_x + m doubles
-    if ((r = dk_zero(k, k->gn, nx + k->m)) || (r = dk_At_partial(k, 1.0, v + n)) || (r = dk_H_partial(k, 1.0, v)) ||
-        (r = dk_A_partial(k, 1.0, v)))
+    if ((r = dop_zero(k->d->dev, k->gn, nx + k->m)) || (r = dk_A_partial(k, 1, 1.0, v + n)) || (r = dk_H_partial(k, 1.0, v)) ||
+        (r = dk_A_partial(k, 0, 1.0, v)))
         return r;
     if ((r = distcore::comm_allreduce(k->d, k->gn, nx + k->m, GRP_WORLD))) return r;
     {
@@ -962,7 +922,7 @@ extern "C" int32_t madqp_dkkt_eval(madqp_dkkt* k, const madqp_state* st, const d
     madqp_ctx* ctx = k->ctx;
     ARG_TRY(ctx, obj_host && (k->nx == 0 || q) && (k->m == 0 || rhs));
     const int64_t nx = k->nx, n = st->n;
-    if ((r = dk_zero(k, k->gn, nx + k->m)) || (r = dk_H_partial(k, 1.0, st->x)) || (r = dk_A_partial(k, 1.0, st->x)))
+    if ((r = dop_zero(k->d->dev, k->gn, nx + k->m)) || (r = dk_H_partial(k, 1.0, st->x)) || (r = dk_A_partial(k, 0, 1.0, st->x)))
         return r;
     if ((r = distcore::comm_allreduce(k->d, k->gn, nx + k->m, GRP_WORLD))) return r;
     double sums[2] = {0.0, 0.0};

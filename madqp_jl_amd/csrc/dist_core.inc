@@ -38,11 +38,10 @@
 #include <cstring>
 #include <vector>
 
+#include "panel_image.h"  // [info, 0 | inverse 128-blocks | L]: the form diagonal tiles and operands travel in
+
 enum { GRP_WORLD = 0, GRP_ROW = 1, GRP_COL = 2 };
-static const int64_t DIST_NB128 = 128;
-static const int64_t DIST_WBLK = 2 * 128 * 128;  // doubles per inverse 128-block image [Wcm | Wrm]
-static const int64_t DIST_HDR = 2;               // doubles: [info, 0]
-static const int DIST_MAXLEV = 32;               // levels of the operand staircases
+static const int DIST_MAXLEV = 32;  // levels of the operand staircases
 
 struct madqp_dist {
     Dev* dev;
@@ -68,7 +67,8 @@ struct madqp_dist {
     int64_t xl_row0[DIST_MAXLEV], xl_ld[DIST_MAXLEV], xl_off[DIST_MAXLEV];  // XW: first stored local row, ld, offset
     int64_t yl_row0[DIST_MAXLEV], yl_ld[DIST_MAXLEV], yl_off[DIST_MAXLEV];  // YW: the same over local columns
     int64_t xw_count, yw_count;                            // doubles allocated (0: in place)
-    int64_t bytes_total, bytes_K, bytes_band, bytes_stage; // device bytes of this handle (madqp_dist_memory)
+    // device bytes of this handle and of what madqp_dist_memory tells apart: matrix, XW, YW, bands, staging (distcore::buffers)
+    int64_t bytes_total, bytes_K, bytes_xw, bytes_yw, bytes_band, bytes_stage;
     double* bstage2;       // force_comm only: where a piece sent to oneself is received (exercises ncclSend / ncclRecv)
     int64_t* done;         // host: per local tile column, the number of panels already applied to it
     double* seg;           // transpose segment: tiles of nb x nb
@@ -76,7 +76,7 @@ struct madqp_dist {
     double *sloc, *tloc;   // partial sums of the sweeps (mloc / nloc)
     // solve groups: G consecutive tiles; the G x G tile triangle on the diagonal of group g and the inverse 128-blocks of
     // its diagonal tiles live on rank g mod world (slot g div world), collected during the factorisation
-    int64_t G, NG;
+    int64_t G, NG, my_groups;  // (my_groups: the band slots of this rank)
     int64_t bslot, bwslot;  // doubles per slot: (G nb)^2 (leading dimension G nb) / G (nb/128) inverse-block images
     double *band, *bandW;
     double* bstage;         // staging of one step's pieces: [diagonal image | G tiles]
@@ -90,10 +90,8 @@ struct madqp_dist {
     int32_t force_comm;    // issue the collectives even in groups of one rank (RCCL smoke test on a single GPU)
     int32_t factored;      // a factorisation ran to its end (whatever its info)
     char err[256];
-    int64_t want[17];      // doubles per device buffer (create), allocated by allocate() once every rank says it fits
     int32_t fits;          // this rank's own verdict: its byte total against its free device memory
 };
-constexpr int DIST_NWANT = 17;
 
 namespace distcore {
 
@@ -115,6 +113,16 @@ inline int64_t pad128(int64_t v) { return std::max<int64_t>(128, (v + 127) / 128
 // ---------------------------------------------------------------- collectives
 inline int group_size(const madqp_dist* d, int g) { return g == GRP_WORLD ? d->world : g == GRP_ROW ? d->Q : d->P; }
 inline int group_rank(const madqp_dist* d, int g) { return g == GRP_WORLD ? d->rank : g == GRP_ROW ? d->q : d->p; }
+// a single rank with nothing forced: no collective runs, the factor stays where it lies
+inline bool single_rank(const madqp_dist* d) { return d->world == 1 && !d->force_comm; }
+// group g has traffic: more than one member, or the collectives are issued regardless (force_comm)
+inline bool group_traffic(const madqp_dist* d, int g) { return group_size(d, g) > 1 || d->force_comm; }
+
+#define DTRY(expr)                 \
+    do {                           \
+        int32_t r_ = (expr);       \
+        if (r_) return r_;         \
+    } while (0)
 
 inline int32_t host_reserve(madqp_dist* d, size_t bytes) {
     if (bytes <= d->hostbuf_bytes) return 0;
@@ -122,6 +130,17 @@ inline int32_t host_reserve(madqp_dist* d, size_t bytes) {
     d->hostbuf = malloc(bytes);
     d->hostbuf_bytes = d->hostbuf ? bytes : 0;
     return d->hostbuf ? 0 : MADQP_ERR_ALLOC;
+}
+// The host-staged form of a collective on `count` doubles at buf: through the host buffer, out of the device when this
+// rank contributes (`out`), back into it when this rank receives (`in`); call(ops, hostbuf) is the caller's callback
+template <class Call>
+inline int32_t host_staged(madqp_dist* d, double* buf, int64_t count, bool out, bool in, Call call) {
+    const size_t bytes = (size_t)count * 8;
+    DTRY(host_reserve(d, bytes));
+    if (out) DTRY(dop_d2h(d->dev, d->hostbuf, buf, bytes));
+    if (call(d->host, d->hostbuf)) return MADQP_ERR_STATE;
+    if (in) DTRY(dop_h2d(d->dev, buf, d->hostbuf, bytes));
+    return 0;
 }
 
 inline int32_t comm_send(madqp_dist* d, const double* buf, int64_t count, int dst);
@@ -157,7 +176,8 @@ inline int32_t comm_bcast_p2p(madqp_dist* d, double* buf, int64_t count, int roo
 }
 // root: rank WITHIN the group (q for a row group, p for a column group, world rank for the world)
 inline int32_t comm_bcast(madqp_dist* d, double* buf, int64_t count, int root, int g) {
-    if (count <= 0 || (group_size(d, g) == 1 && !d->force_comm)) return 0;
+    if (count <= 0 || !group_traffic(d, g)) return 0;
+    const bool is_root = group_rank(d, g) == root;
     if (bcast_p2p() && group_size(d, g) > 1) return comm_bcast_p2p(d, buf, count, root, g);
     if (bcast_p2p() && d->force_comm && !d->host && d->bstage2) {
         // one rank, RCCL forced: the image goes to this rank itself through ncclSend / ncclRecv, in pieces of the staging
@@ -177,39 +197,28 @@ inline int32_t comm_bcast(madqp_dist* d, double* buf, int64_t count, int root, i
         }
         return 0;
     }
-    if (group_rank(d, g) == root) d->bytes_sent += 8 * count;
-    if (d->host) {
-        int32_t r = host_reserve(d, (size_t)count * 8);
-        if (r) return r;
-        if (group_rank(d, g) == root && (r = dop_d2h(d->dev, d->hostbuf, buf, (size_t)count * 8))) return r;
-        if ((r = d->host->bcast(d->host->user, d->hostbuf, count * 8, root, g))) return MADQP_ERR_STATE;
-        if (group_rank(d, g) != root && (r = dop_h2d(d->dev, buf, d->hostbuf, (size_t)count * 8))) return r;
-        return 0;
-    }
+    if (is_root) d->bytes_sent += 8 * count;
+    if (d->host)
+        return host_staged(d, buf, count, is_root, !is_root, [&](const madqp_comm_ops* h, void* hb) {
+            return h->bcast(h->user, hb, count * 8, root, g);
+        });
     return dop_nccl_bcast(d->dev, d->nccl[g], buf, count, root);
 }
 // sum over the group into the root's buffer (in place); other ranks' buffers are left as they are
 inline int32_t comm_reduce(madqp_dist* d, double* buf, int64_t count, int root, int g) {
-    if (count <= 0 || (group_size(d, g) == 1 && !d->force_comm)) return 0;
-    if (d->host) {
-        int32_t r = host_reserve(d, (size_t)count * 8);
-        if (r) return r;
-        if ((r = dop_d2h(d->dev, d->hostbuf, buf, (size_t)count * 8))) return r;
-        if ((r = d->host->reduce_sum(d->host->user, (double*)d->hostbuf, count, root, g))) return MADQP_ERR_STATE;
-        if (group_rank(d, g) == root && (r = dop_h2d(d->dev, buf, d->hostbuf, (size_t)count * 8))) return r;
-        return 0;
-    }
+    if (count <= 0 || !group_traffic(d, g)) return 0;
+    if (d->host)
+        return host_staged(d, buf, count, true, group_rank(d, g) == root, [&](const madqp_comm_ops* h, void* hb) {
+            return h->reduce_sum(h->user, (double*)hb, count, root, g);
+        });
     return dop_nccl_reduce(d->dev, d->nccl[g], buf, count, root);
 }
 inline int32_t comm_allreduce(madqp_dist* d, double* buf, int64_t count, int g) {
-    if (count <= 0 || (group_size(d, g) == 1 && !d->force_comm)) return 0;
-    if (d->host) {
-        int32_t r = host_reserve(d, (size_t)count * 8);
-        if (r) return r;
-        if ((r = dop_d2h(d->dev, d->hostbuf, buf, (size_t)count * 8))) return r;
-        if ((r = d->host->allreduce_sum(d->host->user, (double*)d->hostbuf, count, g))) return MADQP_ERR_STATE;
-        return dop_h2d(d->dev, buf, d->hostbuf, (size_t)count * 8);
-    }
+    if (count <= 0 || !group_traffic(d, g)) return 0;
+    if (d->host)
+        return host_staged(d, buf, count, true, true, [&](const madqp_comm_ops* h, void* hb) {
+            return h->allreduce_sum(h->user, (double*)hb, count, g);
+        });
     return dop_nccl_allreduce(d->dev, d->nccl[g], buf, count);
 }
 
@@ -217,32 +226,22 @@ inline int32_t comm_allreduce(madqp_dist* d, double* buf, int64_t count, int g) 
 inline int32_t comm_send(madqp_dist* d, const double* buf, int64_t count, int dst) {
     if (count <= 0) return 0;
     d->bytes_sent += 8 * count;
-    if (d->host) {
-        int32_t r = host_reserve(d, (size_t)count * 8);
-        if (r) return r;
-        if ((r = dop_d2h(d->dev, d->hostbuf, buf, (size_t)count * 8))) return r;
-        return d->host->send(d->host->user, d->hostbuf, count * 8, dst) ? MADQP_ERR_STATE : 0;
-    }
+    if (d->host)  // (out only: buf is not written)
+        return host_staged(d, const_cast<double*>(buf), count, true, false, [&](const madqp_comm_ops* h, void* hb) {
+            return h->send(h->user, hb, count * 8, dst);
+        });
     return dop_nccl_send(d->dev, d->nccl[GRP_WORLD], buf, count, dst);
 }
 inline int32_t comm_recv(madqp_dist* d, double* buf, int64_t count, int src) {
     if (count <= 0) return 0;
-    if (d->host) {
-        int32_t r = host_reserve(d, (size_t)count * 8);
-        if (r) return r;
-        if (d->host->recv(d->host->user, d->hostbuf, count * 8, src)) return MADQP_ERR_STATE;
-        return dop_h2d(d->dev, buf, d->hostbuf, (size_t)count * 8);
-    }
+    if (d->host)
+        return host_staged(d, buf, count, false, true, [&](const madqp_comm_ops* h, void* hb) {
+            return h->recv(h->user, hb, count * 8, src);
+        });
     return dop_nccl_recv(d->dev, d->nccl[GRP_WORLD], buf, count, src);
 }
 inline int32_t comm_p2p_begin(madqp_dist* d) { return d->host ? 0 : dop_nccl_group(d->dev, 1); }
 inline int32_t comm_p2p_end(madqp_dist* d) { return d->host ? 0 : dop_nccl_group(d->dev, 0); }
-
-#define DTRY(expr)                 \
-    do {                           \
-        int32_t r_ = (expr);       \
-        if (r_) return r_;         \
-    } while (0)
 
 // ---------------------------------------------------------------- factorisation
 // Streams (HIP build; no-ops in the CPU build).  The rank-local KERNELS of a rank all run on one stream, U, in program
@@ -265,7 +264,7 @@ enum { ST_U = 0, ST_P = 1 };
 enum { MK_UPDATE_COL = 1, MK_POTRF = 2, MK_DIAG_BCAST = 3, MK_TRSM = 4, MK_PACK = 5, MK_EXCHANGE = 6, MK_BULK = 7 };
 
 struct StepGeom {
-    int64_t w, lr, lc, nblk, r0, c0, ldx, ldy;
+    int64_t w, lr, lc, r0, c0, ldx, ldy;
     int kp, kq;
 };
 inline StepGeom geom(const madqp_dist* d, int64_t k) {
@@ -275,7 +274,6 @@ inline StepGeom geom(const madqp_dist* d, int64_t k) {
     g.kq = (int)(k % d->Q);
     g.lr = k / d->P;
     g.lc = k / d->Q;
-    g.nblk = (g.w + 127) / 128;
     g.r0 = first_after(k, d->p, d->P);
     g.c0 = first_after(k, d->q, d->Q);
     g.ldx = g.r0 < d->mt ? d->ld - g.r0 * d->nb : 0;  // rows of the row operand incl. padding (multiple of 128)
@@ -288,8 +286,8 @@ inline StepGeom geom(const madqp_dist* d, int64_t k) {
 // entries -- so that a tile column is brought up to date by ONE wide product when it is needed (update_col_range)
 // instead of being read, modified and written once per step.  In a process row of ONE rank (Q == 1) the row operands are
 // the factored panels of the local matrix themselves; on a 1 x 1 grid so are the column operands.
-inline bool x_in_place(const madqp_dist* d) { return d->Q == 1 && !d->force_comm; }
-inline bool y_is_x(const madqp_dist* d) { return d->P == 1 && d->Q == 1 && !d->force_comm; }
+inline bool x_in_place(const madqp_dist* d) { return !group_traffic(d, GRP_ROW); }
+inline bool y_is_x(const madqp_dist* d) { return single_rank(d); }
 inline int level_of(const madqp_dist* d, int64_t k) {
     int s = 0;
     while (s + 1 < d->nlev && k >= d->lev_k0[s + 1]) ++s;
@@ -322,32 +320,29 @@ inline int32_t panel_chain(madqp_dist* d, int64_t k) {
     const StepGeom g = geom(d, k);
     if (d->q != g.kq) return 0;
     const int64_t nb = d->nb, ld = d->ld, w = g.w;
-    const int64_t dcount = DIST_HDR + g.nblk * DIST_WBLK + w * w;
-    if (d->P == 1 && !d->force_comm) {
+    if (!group_traffic(d, GRP_COL)) {
         // A process column of ONE rank holds the whole panel: no diagonal tile to broadcast, no separate panel solve --
         // the panel goes through the one-GPU panel factorisation as it stands (chol.hip: recursive, its in-panel
         // products over the full panel height), which also leaves [info | inverse blocks | L_kk] in diagbuf
         dop_mark(dev, MK_POTRF, k);
         DTRY(dop_panel_local(dev, d->K, ld, g.lc, k, nb, w, d->diagbuf, d->info_dev));
-        DTRY(dop_copy(dev, d->Wdiag + g.lr * d->wslot, d->diagbuf + DIST_HDR, g.nblk * DIST_WBLK));  // for the solves
+        DTRY(dop_copy(dev, d->Wdiag + g.lr * d->wslot, d->diagbuf + IMG_HDR, img_blocks(w)));  // for the solves
     } else {
         if (d->p == g.kp) {
             dop_mark(dev, MK_POTRF, k);
             DTRY(dop_potrf_tile(dev, d->K + g.lr * nb + g.lc * nb * ld, ld, w, d->diagbuf, k * nb, d->info_dev));
-            DTRY(dop_copy(dev, d->Wdiag + g.lr * d->wslot, d->diagbuf + DIST_HDR, g.nblk * DIST_WBLK));  // for the solves
+            DTRY(dop_copy(dev, d->Wdiag + g.lr * d->wslot, d->diagbuf + IMG_HDR, img_blocks(w)));  // for the solves
         }
-        if (group_size(d, GRP_COL) > 1 || d->force_comm) {
-            DTRY(dop_link(dev, ST_U, ST_P));
-            DTRY(dop_stream(dev, ST_P));
-            dop_mark(dev, MK_DIAG_BCAST, k);
-            DTRY(comm_bcast(d, d->diagbuf, dcount, g.kp, GRP_COL));
-            DTRY(dop_link(dev, ST_P, ST_U));
-            DTRY(dop_stream(dev, ST_U));
-        }
+        DTRY(dop_link(dev, ST_U, ST_P));
+        DTRY(dop_stream(dev, ST_P));
+        dop_mark(dev, MK_DIAG_BCAST, k);
+        DTRY(comm_bcast(d, d->diagbuf, img_count(w, w), g.kp, GRP_COL));
+        DTRY(dop_link(dev, ST_P, ST_U));
+        DTRY(dop_stream(dev, ST_U));
         if (d->p != g.kp) DTRY(dop_info_merge(dev, d->info_dev, d->diagbuf));
         if (g.r0 < d->mt) {  // C <- C L_kk^-T for my tile rows below k
-            const double* Wk = d->diagbuf + DIST_HDR;
-            const double* Lk = Wk + g.nblk * DIST_WBLK;  // w x w, leading dimension w
+            const double* Wk = d->diagbuf + IMG_HDR;
+            const double* Lk = d->diagbuf + img_L(w);  // w x w, leading dimension w
             dop_mark(dev, MK_TRSM, k);
             DTRY(dop_trsm(dev, d->K + g.r0 * nb + g.lc * nb * ld, ld, d->mloc - g.r0 * nb, g.ldx, Lk, w, Wk, w));
         }
@@ -356,7 +351,7 @@ inline int32_t panel_chain(madqp_dist* d, int64_t k) {
         double* X = d->Xrow[k & 1];
         dop_mark(dev, MK_PACK, k);
         DTRY(dop_info_store(dev, d->info_dev, X));  // the header carries info to every rank
-        if (g.ldx > 0) DTRY(dop_copy2d(dev, X + DIST_HDR, g.ldx, d->K + g.r0 * nb + g.lc * nb * ld, ld, g.ldx, w));
+        if (g.ldx > 0) DTRY(dop_copy2d(dev, X + IMG_HDR, g.ldx, d->K + g.r0 * nb + g.lc * nb * ld, ld, g.ldx, w));
     }
     return 0;
 }
@@ -391,8 +386,8 @@ inline int32_t band_collect(madqp_dist* d, int64_t k) {
     const int64_t grp = k / G, j = k - grp * G, gend = std::min((grp + 1) * G, d->T);
     const int owner = (int)(grp % d->world);
     const int64_t slot = grp / d->world, ldb = G * nb;
-    const int64_t dcount = g.nblk * DIST_WBLK + w * w;
-    if (d->world == 1 && !d->force_comm) return 0;  // one rank solves with the factor where it is (solve: dop_solve_local)
+    const int64_t dcount = img_blocks(w) + w * w;  // the diagonal image without its header
+    if (single_rank(d)) return 0;  // one rank solves with the factor where it is (solve: dop_solve_local)
     // force_comm (one rank going through every collective of the schedule, RCCL's point-to-point calls included): a piece
     // whose source is the owner is SENT TO ONESELF and received in a second staging area, inside the same group call
     // -- otherwise ncclSend / ncclRecv / the group bracket would never run on the hardware a one-GPU box has
@@ -408,7 +403,7 @@ inline int32_t band_collect(madqp_dist* d, int64_t k) {
         const int src = (int)((I % d->P) * d->Q + g.kq);
         if (d->rank != src) continue;
         if (I == k) {
-            DTRY(dop_copy(dev, d->bstage, d->diagbuf + DIST_HDR, dcount));
+            DTRY(dop_copy(dev, d->bstage, d->diagbuf + IMG_HDR, dcount));
         } else {
             const int64_t rows = tsize(d, I);
             DTRY(dop_copy2d(dev, d->bstage + d->wslot + nb * nb + (I - k - 1) * nb * nb, rows,
@@ -439,8 +434,8 @@ inline int32_t band_collect(madqp_dist* d, int64_t k) {
         };
         double* B = d->band + slot * d->bslot;
         const double* dimg = piece(k, 0);
-        DTRY(dop_copy(dev, d->bandW + slot * d->bwslot + j * (nb / 128) * DIST_WBLK, dimg, g.nblk * DIST_WBLK));
-        DTRY(dop_copy2d(dev, B + j * nb + j * nb * ldb, ldb, dimg + g.nblk * DIST_WBLK, w, w, w));
+        DTRY(dop_copy(dev, d->bandW + slot * d->bwslot + j * d->wslot, dimg, img_blocks(w)));
+        DTRY(dop_copy2d(dev, B + j * nb + j * nb * ldb, ldb, dimg + img_blocks(w), w, w, w));
         for (int64_t I = k + 1; I < gend; ++I) {
             const int64_t rows = tsize(d, I);
             DTRY(dop_copy2d(dev, B + (I - grp * G) * nb + j * nb * ldb, ldb,
@@ -464,19 +459,18 @@ inline int32_t operands_exchange(madqp_dist* d, int64_t k) {
     double* xblk = xw_block(d, k, &ldxw) + g.r0 * nb;  // first valid row of block k of the row operands
     if (!x_in_place(d)) {
         double* X = d->Xrow[k & 1];
-        DTRY(comm_bcast(d, X, DIST_HDR + g.ldx * w, g.kq, GRP_ROW));
+        DTRY(comm_bcast(d, X, IMG_HDR + g.ldx * w, g.kq, GRP_ROW));
         if (d->q != g.kq) DTRY(dop_info_merge(dev, d->info_dev, X));
-        if (g.ldx > 0) DTRY(dop_copy2d(dev, xblk, ldxw, X + DIST_HDR, g.ldx, g.ldx, w));
+        if (g.ldx > 0) DTRY(dop_copy2d(dev, xblk, ldxw, X + IMG_HDR, g.ldx, g.ldx, w));
     }
     if (!y_is_x(d)) {
         double* yblk = yw_block(d, k, &ldyw);  // block k of the column operands, row = local column (rows >= c0 nb exist)
-        const bool direct = (group_size(d, GRP_COL) == 1 && !d->force_comm);  // P == 1: my row operand has every tile
         for (int pr = 0; pr < d->P; ++pr) {
             const SegPlan sp = seg_plan(d, g, pr);
             if (sp.cnt == 0) continue;
             const int64_t J0 = sp.lj0 * d->Q + d->q;
             const int64_t yoff = sp.lj0 * nb;
-            if (direct) {  // operand rows -> column operand, one launch
+            if (!group_traffic(d, GRP_COL)) {  // P == 1, my row operand has every tile: rows -> column operand, one launch
                 const int64_t xoff = (J0 / d->P - g.r0) * nb;
                 DTRY(dop_gather_tiles(dev, yblk + yoff, ldyw, sp.s * nb, xblk + xoff, ldxw, sp.jstep * nb, sp.cnt, nb, w,
                                       d->ncp - yoff, sp.s * nb, 0));
@@ -497,19 +491,26 @@ inline int32_t operands_exchange(madqp_dist* d, int64_t k) {
     return 0;
 }
 
+// first local tile row li with global tile I = li P + p >= J, and whether that tile is the diagonal one (I == J)
+inline int64_t first_lower(const madqp_dist* d, int64_t J, bool* has_diag) {
+    const int64_t li0 = first_after(J - 1, d->p, d->P);
+    *has_diag = (li0 * d->P + d->p == J);
+    return li0;
+}
+
 // Local tile column lj (global J) receives the panels ka .. kb-1 (all < J) in ONE product:
 //   C[I, J] -= sum_{k = ka}^{kb-1} X_p(k)[I] Y_q(k)[J]'   for my tile rows I >= J,   K = (kb - ka) nb
 inline int32_t update_col_range(madqp_dist* d, int64_t lj, int64_t ka, int64_t kb) {
     const int64_t nb = d->nb, J = lj * d->Q + d->q;
     if (ka >= kb || lj >= d->nt) return 0;
-    const int64_t li0 = (J > d->p) ? (J - d->p + d->P - 1) / d->P : 0;  // first local tile row with I >= J
+    bool has_diag = false;
+    const int64_t li0 = first_lower(d, J, &has_diag);
     if (li0 >= d->mt) return 0;
     const int64_t M = d->mloc - li0 * nb, N = tsize(d, J);
     if (M <= 0 || N <= 0) return 0;
     // 128-wide tile columns of the nb-wide tile column: when its first local tile is the diagonal tile (I == J) only that
     // tile's lower 128-tiles are needed -- nothing reads the upper triangle of a diagonal tile of K (28 of its 64
     // 128-tiles at nb = 1024: 2 % of a wide update, 1.8 % of the assembly)
-    const bool has_diag = (li0 * d->P + d->p == J);
     std::vector<int64_t> row0((size_t)((N + 127) / 128), 0);
     if (has_diag)
         for (size_t tc = 0; tc < row0.size(); ++tc) row0[tc] = (int64_t)tc;
@@ -536,9 +537,8 @@ inline int32_t assemble_product(madqp_dist* d, const double* Cin, int64_t ldcin,
     const int64_t t128 = d->nb / 128, tiles_n = (d->nloc + 127) / 128;
     std::vector<int64_t> row0((size_t)tiles_n);
     for (int64_t tn = 0; tn < tiles_n; ++tn) {
-        const int64_t J = (tn / t128) * d->Q + d->q;
-        const int64_t li0 = (J > d->p) ? (J - d->p + d->P - 1) / d->P : 0;
-        const bool has_diag = (li0 * d->P + d->p == J);  // lower 128-tiles of a diagonal tile only (update_col_range)
+        bool has_diag = false;  // lower 128-tiles of a diagonal tile only (update_col_range)
+        const int64_t li0 = first_lower(d, (tn / t128) * d->Q + d->q, &has_diag);
         row0[(size_t)tn] = li0 * t128 + (has_diag ? tn % t128 : 0);
     }
     return dop_gemm(d->dev, d->K, d->ld, Cin, ldcin, X, ldx, Y, ldy, d->mloc, d->nloc, kdim, 1.0, Cin ? 1.0 : 0.0,
@@ -567,7 +567,7 @@ inline int32_t factor_steps(madqp_dist* d) {
         // in between runs on the other process columns.  A single rank has nobody to overlap with: its next column
         // is the panel of the next step and gets everything there, in one product (the plain left-looking schedule).
         dop_mark(dev, MK_BULK, k);
-        if (d->world == 1 && !d->force_comm) continue;
+        if (single_rank(d)) continue;
         int64_t lja = mine ? nxt / d->Q + 1 : first_after(nxt, d->q, d->Q);
         if (lja < d->nt && d->done[lja] < nxt) {
             DTRY(dop_bulk(dev, 1));  // leaves room for the collectives' kernels (dist.hip)
@@ -607,32 +607,35 @@ inline int32_t factor(madqp_dist* d, int32_t* info_host) {
 // solve of order <= G nb there (the band slot, sweep kernels of chol.hip), ONE broadcast of the solved rows to everyone
 // -- the solution ends up replicated without an all-gather -- then the products with the local tiles outside the
 // group's triangle.
+// One group of one sweep (trans = 0 forward, 1 backward): the group's partial sums -- `loc`, kept in local order over
+// residue r of R -- are reduced to the group's owner, which subtracts them from the group's rows of rhs, solves with its
+// band slot and broadcasts the solved rows
+inline int32_t group_solve(madqp_dist* d, int32_t trans, int64_t grp, double* rhs, const double* loc, int64_t R, int64_t r) {
+    Dev* dev = d->dev;
+    const int64_t nb = d->nb, G = d->G, I0 = grp * G, I1 = std::min(I0 + G, d->T);
+    const int64_t wg = std::min(d->n, I1 * nb) - I0 * nb, slot = grp / d->world;
+    const int owner = (int)(grp % d->world);
+    double* bg = rhs + I0 * nb;
+    DTRY(dop_group_pack(dev, d->gvec, loc, I0, wg, nb, R, r));
+    DTRY(comm_reduce(d, d->gvec, wg, owner, GRP_WORLD));
+    if (d->rank == owner) {
+        DTRY(dop_vsub(dev, bg, d->gvec, wg));
+        DTRY(dop_tile_solve(dev, trans, d->band + slot * d->bslot, G * nb, d->bandW + slot * d->bwslot, bg, wg, d->vtile));
+    }
+    return comm_bcast(d, bg, wg, owner, GRP_WORLD);
+}
+
 inline int32_t solve(madqp_dist* d, double* rhs) {
     Dev* dev = d->dev;
-    const int64_t nb = d->nb, ld = d->ld, G = d->G, ldb = G * nb;
+    const int64_t nb = d->nb, ld = d->ld, G = d->G;
     if (d->T == 0) return 0;
+    if (single_rank(d)) return dop_solve_local(dev, rhs);  // the factor is the local matrix
     if (d->mloc) DTRY(dop_zero(dev, d->sloc, d->mloc));
     if (d->nloc) DTRY(dop_zero(dev, d->tloc, d->nloc));
-    const bool alone = (d->world == 1 && !d->force_comm);
-    if (alone) return dop_solve_local(dev, rhs);  // one rank: the factor is the local matrix
     // forward: y_g = B_g^-1 (b_g - sum_{J before g} L[g, J] y_J)
     for (int64_t grp = 0; grp < d->NG; ++grp) {
         const int64_t I0 = grp * G, I1 = std::min(I0 + G, d->T);
-        const int64_t wg = std::min(d->n, I1 * nb) - I0 * nb;
-        const int owner = (int)(grp % d->world);
-        double* bg = rhs + I0 * nb;
-        const double* sg = d->sloc + I0 * nb;  // one rank: local order = global order
-        if (!alone) {
-            DTRY(dop_group_pack(dev, d->gvec, d->sloc, I0, wg, nb, d->P, d->p));
-            DTRY(comm_reduce(d, d->gvec, wg, owner, GRP_WORLD));
-            sg = d->gvec;
-        }
-        if (d->rank == owner) {
-            DTRY(dop_vsub(dev, bg, sg, wg));
-            DTRY(dop_tile_solve(dev, 0, d->band + (grp / d->world) * d->bslot, ldb, d->bandW + (grp / d->world) * d->bwslot, bg,
-                                wg, d->vtile));
-        }
-        DTRY(comm_bcast(d, bg, wg, owner, GRP_WORLD));
+        DTRY(group_solve(d, 0, grp, rhs, d->sloc, d->P, d->p));
         const int64_t r0 = first_after(I1 - 1, d->p, d->P);  // my tile rows below the group
         const int64_t rows = d->mloc - r0 * nb;
         if (r0 < d->mt && rows > 0)
@@ -644,21 +647,7 @@ inline int32_t solve(madqp_dist* d, double* rhs) {
     // backward: x_g = B_g^-T (y_g - sum_{I after g} L[I, g]' x_I)
     for (int64_t grp = d->NG - 1; grp >= 0; --grp) {
         const int64_t I0 = grp * G, I1 = std::min(I0 + G, d->T);
-        const int64_t wg = std::min(d->n, I1 * nb) - I0 * nb;
-        const int owner = (int)(grp % d->world);
-        double* bg = rhs + I0 * nb;
-        const double* tg = d->tloc + I0 * nb;
-        if (!alone) {
-            DTRY(dop_group_pack(dev, d->gvec, d->tloc, I0, wg, nb, d->Q, d->q));
-            DTRY(comm_reduce(d, d->gvec, wg, owner, GRP_WORLD));
-            tg = d->gvec;
-        }
-        if (d->rank == owner) {
-            DTRY(dop_vsub(dev, bg, tg, wg));
-            DTRY(dop_tile_solve(dev, 1, d->band + (grp / d->world) * d->bslot, ldb, d->bandW + (grp / d->world) * d->bwslot, bg,
-                                wg, d->vtile));
-        }
-        DTRY(comm_bcast(d, bg, wg, owner, GRP_WORLD));
+        DTRY(group_solve(d, 1, grp, rhs, d->tloc, d->Q, d->q));
         const int64_t cend = first_after(I0 - 1, d->q, d->Q);  // my tile columns with J < I0 (first_after(-1) = 0)
         const int64_t cols = std::min(cend * nb, d->nloc);
         if (I0 > 0 && cols > 0)
@@ -670,13 +659,53 @@ inline int32_t solve(madqp_dist* d, double* rhs) {
 }
 
 // ---------------------------------------------------------------- create / destroy
+// Every device buffer of the handle, in the order they are allocated: where its pointer lives, its doubles (0: not
+// needed on this grid) and the figure of madqp_dist_memory it counts under.  create sums it, allocate and destroy walk it.
+struct DistBuf {
+    double** ptr;
+    int64_t count;
+    int64_t* bytes;
+};
+inline std::vector<DistBuf> buffers(madqp_dist* d) {
+    const int64_t nb = d->nb, stage = d->wslot + nb * nb + d->G * nb * nb;  // [diagonal image | G tiles]
+    const int64_t xrow = x_in_place(d) ? 0 : IMG_HDR + d->ld * nb;          // broadcast image of a row operand
+    const int64_t slots = std::max<int64_t>(d->my_groups, 1);
+    return {
+        {&d->K, d->ld * d->ncp + 128, &d->bytes_K},
+        {&d->Wdiag, std::max<int64_t>(d->mt, 1) * d->wslot, &d->bytes_stage},
+        {&d->diagbuf, img_count(nb, nb), &d->bytes_stage},
+        {&d->Xrow[0], xrow, &d->bytes_stage},
+        {&d->Xrow[1], xrow, &d->bytes_stage},
+        {&d->XW, d->xw_count, &d->bytes_xw},
+        {&d->YW, d->yw_count, &d->bytes_yw},
+        {&d->seg, group_traffic(d, GRP_COL) ? std::max<int64_t>(d->nt, 1) * nb * nb : 0, &d->bytes_stage},  // transposed broadcasts
+        {&d->vtile, 2 * d->G * nb + 64, &d->bytes_stage},
+        {&d->band, slots * d->bslot, &d->bytes_band},
+        {&d->bandW, slots * d->bwslot, &d->bytes_band},
+        {&d->bstage, stage, &d->bytes_stage},
+        {&d->bstage2, d->force_comm ? stage : 0, &d->bytes_stage},
+        {&d->gvec, d->G * nb, &d->bytes_stage},
+        {&d->sloc, d->ld, &d->bytes_stage},
+        {&d->tloc, d->ncp, &d->bytes_stage},
+        {&d->info_dev, 2, &d->bytes_stage},
+    };
+}
+// out8 of madqp_dist_layout and madqp_dist_memory
+inline void layout8(const madqp_dist* d, int64_t* out8) {
+    const int64_t v[8] = {d->p, d->q, d->mt, d->nt, d->mloc, d->nloc, d->ld, d->ncp};
+    memcpy(out8, v, sizeof(v));
+}
+inline void memory8(const madqp_dist* d, int64_t* out8) {
+    const int64_t v[8] = {d->bytes_total, d->bytes_K, d->bytes_xw, d->bytes_yw, d->bytes_band, d->bytes_stage, d->nlev, 0};
+    memcpy(out8, v, sizeof(v));
+}
+
 inline int32_t create(Dev* dev, int32_t rank, int32_t world, int32_t P, int32_t Q, int64_t n, int64_t nb,
                       const madqp_comm_ops* host, int32_t force_comm, madqp_dist** out) {
     *out = nullptr;
     if (P < 1 || Q < 1 || P * Q != world || rank < 0 || rank >= world || n < 0 || nb < 128 || nb % 128) return MADQP_ERR_ARG;
-    madqp_dist* d = new (std::nothrow) madqp_dist();
+    madqp_dist* d = new (std::nothrow) madqp_dist();  // (every field zero)
     if (!d) return MADQP_ERR_ALLOC;
-    memset(d, 0, sizeof(*d));
     d->dev = dev;
     d->rank = rank;
     d->world = world;
@@ -695,7 +724,7 @@ inline int32_t create(Dev* dev, int32_t rank, int32_t world, int32_t P, int32_t 
     d->ncp = pad128(d->nloc);
     d->host = host;
     d->force_comm = force_comm;  // (decides where the operands live: before anything is allocated)
-    d->wslot = (nb / 128) * DIST_WBLK;
+    d->wslot = img_blocks(nb);
     // solve groups of G tiles: 4096 rows unless MADQP_DIST_GROUP says otherwise
     const char* genv = getenv("MADQP_DIST_GROUP");
     d->G = std::max<int64_t>(1, genv ? atoll(genv) : 4096 / nb);
@@ -704,8 +733,7 @@ inline int32_t create(Dev* dev, int32_t rank, int32_t world, int32_t P, int32_t 
     d->bslot = d->G * nb * d->G * nb;
     d->bwslot = d->G * d->wslot;
     // (a single rank solves with the factor where it lies -- dop_solve_local -- and collects no bands)
-    const int64_t my_groups = (world == 1 && !force_comm) ? 0 : (d->NG > rank ? (d->NG - rank + world - 1) / world : 0);
-    const int64_t dmax = DIST_HDR + d->wslot + nb * nb;
+    d->my_groups = single_rank(d) ? 0 : (d->NG > rank ? (d->NG - rank + world - 1) / world : 0);
     // levels of the operand staircases: ~T/24 steps each (at least 2; MADQP_DIST_LEVEL_STEPS), one level when both
     // operands are read in place.  Memory (1/2 + 1/(2 nlev)) of the rectangles; an update over several levels is one
     // product per level (K = a level's steps x nb >= 2 nb).
@@ -737,42 +765,16 @@ inline int32_t create(Dev* dev, int32_t rank, int32_t world, int32_t P, int32_t 
     // with the figure, not inside the N-th allocation -- and refused by EVERY rank (allocate() below): byte totals and
     // free memory differ between ranks, and a rank that went on alone would wait for the others in the communicator
     // set-up or in its first collective for ever (ADVICE r4)
-    const int64_t counts[DIST_NWANT] = {
-        d->ld * d->ncp + 128,                                                     // K
-        std::max<int64_t>(d->mt, 1) * d->wslot,                                    // Wdiag
-        dmax,                                                                     // diagbuf
-        x_in_place(d) ? 0 : DIST_HDR + d->ld * nb,                                 // Xrow[0]: broadcast images of a row operand
-        x_in_place(d) ? 0 : DIST_HDR + d->ld * nb,                                 // Xrow[1]
-        d->xw_count,                                                              // XW
-        d->yw_count,                                                              // YW
-        (P == 1 && !force_comm) ? 0 : std::max<int64_t>(d->nt, 1) * nb * nb,        // seg: transposed broadcasts
-        2 * d->G * nb + 64,                                                       // vtile
-        std::max<int64_t>(my_groups, 1) * d->bslot,                                // band
-        std::max<int64_t>(my_groups, 1) * d->bwslot,                               // bandW
-        d->wslot + nb * nb + d->G * nb * nb,                                       // bstage
-        force_comm ? d->wslot + nb * nb + d->G * nb * nb : 0,                      // bstage2
-        d->G * nb,                                                                // gvec
-        d->ld,                                                                    // sloc
-        d->ncp,                                                                   // tloc
-        2,                                                                        // info_dev
-    };
-    int64_t total = 0;
-    for (int i = 0; i < DIST_NWANT; ++i) {
-        d->want[i] = counts[i];
-        total += counts[i] > 0 ? std::max<int64_t>(counts[i], 1) * 8 : 0;
-    }
-    d->bytes_total = total;
-    d->bytes_K = (d->ld * d->ncp + 128) * 8;
-    d->bytes_band = std::max<int64_t>(my_groups, 1) * (d->bslot + d->bwslot) * 8;
-    d->bytes_stage = total - d->bytes_K - d->bytes_band - 8 * (d->xw_count + d->yw_count);
+    for (const DistBuf& b : buffers(d)) *b.bytes += 8 * std::max<int64_t>(b.count, 0);
+    d->bytes_total = d->bytes_K + d->bytes_xw + d->bytes_yw + d->bytes_band + d->bytes_stage;
     *out = d;  // (on an error the caller reads d->err and destroys it)
     const int64_t avail = dop_mem_free(dev);  // -1: unknown
-    d->fits = !(avail >= 0 && total > avail);
+    d->fits = !(avail >= 0 && d->bytes_total > avail);
     if (!d->fits)
         snprintf(d->err, sizeof(d->err),
                  "rank %d of the %d x %d grid needs %.2f GB of device memory (local matrix %lld x %lld: %.2f GB, stored "
                  "operands of the lazy updates %.2f + %.2f GB, solve bands %.2f GB) and %.2f GB are free",
-                 rank, P, Q, total * 1e-9, (long long)d->ld, (long long)d->ncp, d->bytes_K * 1e-9, d->xw_count * 8e-9,
+                 rank, P, Q, d->bytes_total * 1e-9, (long long)d->ld, (long long)d->ncp, d->bytes_K * 1e-9, d->xw_count * 8e-9,
                  d->yw_count * 8e-9, d->bytes_band * 1e-9, avail * 1e-9);
     return 0;
 }
@@ -781,7 +783,7 @@ inline int32_t create(Dev* dev, int32_t rank, int32_t world, int32_t P, int32_t 
 // or RCCL on a scratch word once the world communicator exists.  < 0: the collective itself failed.
 inline int agree_count(madqp_dist* d, int mine) {
     double v = mine ? 1.0 : 0.0;
-    if (d->world == 1 && !d->force_comm) return mine;
+    if (single_rank(d)) return mine;
     if (d->host) return d->host->allreduce_sum(d->host->user, &v, 1, GRP_WORLD) ? -1 : (int)(v + 0.5);
     if (!d->nccl[GRP_WORLD]) return -1;
     double* t = (double*)dop_alloc(d->dev, sizeof(double));
@@ -806,13 +808,11 @@ inline int32_t allocate(madqp_dist* d) {
                      "(rank %d could: %.2f GB); every rank refuses", bad, d->P, d->Q, d->rank, d->bytes_total * 1e-9);
         return bad < 0 ? MADQP_ERR_STATE : MADQP_ERR_ALLOC;
     }
-    double** const slots[DIST_NWANT] = {&d->K,    &d->Wdiag, &d->diagbuf, &d->Xrow[0], &d->Xrow[1], &d->XW,   &d->YW,   &d->seg,     &d->vtile,
-                                        &d->band, &d->bandW, &d->bstage,  &d->bstage2, &d->gvec,    &d->sloc, &d->tloc, &d->info_dev};
     bool ok = true;
-    for (int i = 0; i < DIST_NWANT && ok; ++i) {
-        if (d->want[i] <= 0) continue;
-        *slots[i] = (double*)dop_alloc(dev, (size_t)d->want[i] * sizeof(double));
-        ok = ok && *slots[i];
+    for (const DistBuf& b : buffers(d)) {
+        if (b.count <= 0 || !ok) continue;
+        *b.ptr = (double*)dop_alloc(dev, (size_t)b.count * sizeof(double));
+        ok = *b.ptr != nullptr;
     }
     d->done = (int64_t*)calloc((size_t)std::max<int64_t>(d->nt, 1), sizeof(int64_t));
     ok = ok && d->done;
@@ -833,10 +833,8 @@ inline void destroy(madqp_dist* d) {
     Dev* dev = d->dev;
     dop_sync(dev);
     free(d->done);
-    double* ptrs[] = {d->K, d->Wdiag, d->diagbuf, d->Xrow[0], d->Xrow[1], d->XW, d->YW, d->seg,  d->vtile,
-                      d->sloc, d->tloc, d->info_dev, d->band, d->bandW, d->bstage, d->bstage2, d->gvec};
-    for (double* ptr : ptrs)
-        if (ptr) dop_free(dev, ptr);
+    for (const DistBuf& b : buffers(d))
+        if (*b.ptr) dop_free(dev, *b.ptr);
     free(d->hostbuf);
     delete d;
 }

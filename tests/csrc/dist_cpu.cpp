@@ -11,6 +11,7 @@
 #include <new>
 
 #include "../../include/madqp.h"
+#include "../../madqp_jl_amd/csrc/panel_image.h"
 
 #include <vector>
 
@@ -99,11 +100,10 @@ static int32_t dop_potrf_tile(Dev*, double* T, int64_t ld, int64_t w, double* bu
             T[i + j * ld] = v / l;
         }
     }
-    const int64_t nblk = (w + 127) / 128;
     buf[0] = first;
     buf[1] = 0.0;
-    memset(buf + 2, 0, (size_t)(nblk * 2 * 128 * 128) * sizeof(double));  // inverse blocks: not used by these loops
-    double* L = buf + 2 + nblk * 2 * 128 * 128;
+    memset(buf + IMG_HDR, 0, (size_t)img_blocks(w) * sizeof(double));  // inverse blocks: not used by these loops
+    double* L = buf + img_L(w);
     for (int64_t j = 0; j < w; ++j)
         for (int64_t i = 0; i < w; ++i) L[i + j * w] = T[i + j * ld];
     if (*info == 0.0 && first != 0.0) *info = first;
@@ -120,8 +120,7 @@ static int32_t dop_panel_local(Dev* dev, double* K, int64_t ld, int64_t lc, int6
     // rows below the tile: everything this rank holds (P == 1: all rows of the matrix) -- the caller's local row count
     // is not known here, so the extent comes from the leading dimension's owner: dist_core passes ld >= rows; the
     // padded rows are zero and stay zero
-    const int64_t nblk = (w + 127) / 128;
-    const double* L = buf + 2 + nblk * 2 * 128 * 128;
+    const double* L = buf + img_L(w);
     const int64_t below = ld - (k * nb + w);
     return below > 0 ? dop_trsm(dev, T + w, ld, below, below, L, w, nullptr, w) : 0;
 }
@@ -233,9 +232,7 @@ extern "C" {
 const char* madqp_distcpu_last_error() { return g_last_error; }
 // (total, K, XW, YW, bands, staging, levels, 0) -- madqp_dist_memory of the product
 int32_t madqp_distcpu_memory(madqp_dist* d, int64_t* out8) {
-    const int64_t v[8] = {d->bytes_total, d->bytes_K, 8 * d->xw_count, 8 * d->yw_count, d->bytes_band, d->bytes_stage,
-                          d->nlev, 0};
-    memcpy(out8, v, sizeof(v));
+    distcore::memory8(d, out8);
     return 0;
 }
 int32_t madqp_distcpu_create(int32_t rank, int32_t world, int32_t P, int32_t Q, int64_t n, int64_t nb,
@@ -260,8 +257,7 @@ int32_t madqp_distcpu_destroy(madqp_dist* d) {
     return 0;
 }
 int32_t madqp_distcpu_layout(madqp_dist* d, int64_t* out8) {
-    const int64_t v[8] = {d->p, d->q, d->mt, d->nt, d->mloc, d->nloc, d->ld, d->ncp};
-    memcpy(out8, v, sizeof(v));
+    distcore::layout8(d, out8);
     return 0;
 }
 int32_t madqp_distcpu_matrix(madqp_dist* d, double** K, int64_t* ld) {

@@ -198,3 +198,18 @@ def test_the_memory_verdict_is_collective(cpuref, tmp_path):
         assert rec["rc_again"] == 0, rec
     assert "GB of device memory" in recs[1]["err"] and "are free" in recs[1]["err"], recs[1]["err"]
     assert "other rank(s)" in recs[0]["err"] and "every rank refuses" in recs[0]["err"], recs[0]["err"]
+
+
+def test_schedule_under_address_and_undefined_sanitizers():
+    """tests/csrc_dist/dist_sched_main.cpp: a stand-alone program (never loaded into Python) in which ONE rank walks the
+    whole schedule with every collective forced -- operand staircases over several levels, the operand exchange with its
+    tile gathers, the band collection with its send-to-self, the group sweeps -- over in-process collectives, under both
+    sanitizers.  Per case it factors, solves and holds max|A x - b| / max|b| to 1e-12, or (the case with a negative
+    diagonal entry) info to that column; the send queue must be empty at the end."""
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "csrc_dist")], stdout=subprocess.DEVNULL)
+    out = subprocess.run([os.path.join(ROOT, "tests", "_build", "dist_sched_check")], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = out.stdout.strip().splitlines()
+    assert lines[-1] == "dist schedule ok" and len(lines) == 6 and "FAILED" not in out.stdout, out.stdout
+    assert " info 438 " in lines[4] and all(" info 0 " in ln and " queue 0 " in ln for ln in lines[:4]), out.stdout
