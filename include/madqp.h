@@ -355,6 +355,13 @@ int32_t madqp_chol_solve_many_info(madqp_chol* s, int64_t nrhs, int64_t* out_hos
  * Replaces mul!(y, kkt.AT, x) / mul!(y, kkt.AT', x) (src/KKT/normalkkt.jl:162-164,194,200,214-215). */
 int32_t madqp_gemv(madqp_ctx* ctx, int32_t trans, int64_t rows, int64_t cols, double alpha,
                    const double* A, int64_t lda, const double* x, double beta, double* y);
+/* The same product on nrhs vectors: Y[:, c] = alpha op(A) X[:, c] + beta Y[:, c], column c of X at X + c ldx (ldx >= the
+ * contraction length), of Y at Y + c ldy (ldy >= the output length); A, trans, rows, cols, lda as above.  A is read
+ * ceil(nrhs / 128) times per call, not nrhs times (fp64 MFMA; csrc/many_plan.inc).  beta == 0 ASSIGNS, as madqp_gemv does: Y is
+ * not read, whatever it held (a NaN included) is gone.  Nothing outside rows x cols of A or the stated lengths of the
+ * columns is read or written.  X and Y must not overlap.  Deterministic; the summation order differs from madqp_gemv's. */
+int32_t madqp_gemv_many(madqp_ctx* ctx, int32_t trans, int64_t rows, int64_t cols, int64_t nrhs, double alpha,
+                        const double* A, int64_t lda, const double* X, int64_t ldx, double beta, double* Y, int64_t ldy);
 
 /* ----------------------------------------------------------- solver state view */
 /* Device-pointer view of MPCSolver (src/structure.jl:1-75) + the diagonal fields of the
@@ -506,12 +513,33 @@ int32_t madqp_kkt_set_refine(madqp_kkt* kkt, int32_t steps);
  * (ldw >= n + m + nlb + nub), each solved in place as madqp_kkt_solve solves one; nrhs == 1 IS madqp_kkt_solve(kkt, st, W),
  * nrhs == 0 does nothing; MADQP_ERR_ARG for nrhs < 0, a short ldw or a NULL W with work to do.  Every KKT form: the passes
  * before the factor solve run per column (the kernels of the one-vector solve on offset pointers), then ONE
- * madqp_chol_solve_many of all columns, then the passes after it per column.  The products with A / A' stay mat-vecs per
- * column: with a dense A they are the larger part of a many-column solve (their GEMM form is not in this library yet).
+ * madqp_chol_solve_many of all columns, then the passes after it per column.  By default the products with A / A' are
+ * mat-vecs per column too: with a dense A they are the larger part of a many-column solve.  madqp_kkt_set_block_products
+ * (below) runs them on the block of all columns instead.
  * madqp_kkt_set_refine is honoured (residuals per column, corrections through one solve of the residual block).  The work
  * vectors of the columns belong to the object and grow at the first call that needs more (that call synchronises).
  * Afterwards madqp_kkt_mul_solved has nothing to reuse: it is madqp_kkt_mul. */
 int32_t madqp_kkt_solve_many(madqp_kkt* kkt, const madqp_state* st, double* W, int64_t ldw, int64_t nrhs);
+/* MadNLP.mul!(w, kkt, v, alpha, beta) for nrhs pairs of columns: column c of W (at W + c ldw) <- alpha K (column c of V, at
+ * V + c ldv) + beta (column c of W); ldw, ldv >= n + m + nlb + nub.  nrhs == 1 IS madqp_kkt_mul(kkt, st, W, V, alpha, beta),
+ * nrhs == 0 does nothing; MADQP_ERR_ARG for nrhs < 0, a short ldw or ldv, a NULL pointer with work to do or W == V.  For
+ * nrhs >= 2 the products with A, A' and H run on the block: the dense operands are read once per 128 columns
+ * (madqp_gemv_many), the CSR arrays once per 32 columns with bitwise the sums of the one-vector product; the per-variable
+ * passes behind them stay per column.  Against the column loop over madqp_kkt_mul the dense forms differ by rounding (another
+ * summation order), an object whose A and H are sparse or diagonal gives the same bits.  The workspace belongs to the
+ * object and grows at the first call that needs more (that call synchronises).  Afterwards madqp_kkt_mul_solved is
+ * madqp_kkt_mul. */
+int32_t madqp_kkt_mul_many(madqp_kkt* kkt, const madqp_state* st, double* W, int64_t ldw, const double* V, int64_t ldv,
+                           int64_t nrhs, double alpha, double beta);
+/* on = 1: madqp_kkt_solve_many with nrhs >= 2 runs the A / A' products of its two stages once on the block of all columns
+ * (every form that has them: condensed and normal; the augmented forms have none) and takes its refinement residuals
+ * from madqp_kkt_mul_many.  on = 0 (the default): the column loop, bit for bit what it was before this switch existed.
+ * MADQP_ERR_ARG for any other value. */
+int32_t madqp_kkt_set_block_products(madqp_kkt* kkt, int32_t on);
+/* What madqp_kkt_solve_many with nrhs columns would run as, four values: out_host[0] 0 the column loop / 1 the block
+ * products; [1] passes over the arrays of A or A' per call (stages and refinement residuals); [2] passes over H per call
+ * (refinement residuals only); [3] doubles of workspace for blocks of columns the object holds now. */
+int32_t madqp_kkt_many_info(madqp_kkt* kkt, int64_t nrhs, int64_t* out_host);
 /* MadNLP.mul!(w, kkt, v, alpha, beta) (src/KKT/normalkkt.jl:207-219), with H for a QP */
 int32_t madqp_kkt_mul(madqp_kkt* kkt, const madqp_state* st, double* w, const double* v,
                       double alpha, double beta);

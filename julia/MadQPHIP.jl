@@ -320,6 +320,23 @@ function mul!(w::MadNLP.AbstractKKTVector{T}, kkt::HIPKKTSystem, v::MadNLP.Abstr
     return w
 end
 
+# mul! for a block: column c of the device matrices W and V (strides size(., 1) >= length(full(w))) is the `full` of an
+# UnreducedKKTVector; W[:, c] <- alpha K V[:, c] + beta W[:, c] with the products with A, A' and H run once on the block
+# (madqp_kkt_mul_many) -- the block residual P - K W of a many-column solve is mul!(P, kkt, W, -1, 1)
+function mul!(W::AbstractMatrix, kkt::HIPKKTSystem, V::AbstractMatrix, alpha = 1.0, beta = 0.0)
+    check(kkt.ctx, ccall((:madqp_kkt_mul_many, libmadqp), Int32,
+                         (Ptr{Cvoid}, Ref{CState}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64),
+                         kkt.handle, kkt.cstate, dptr(W), size(W, 1), dptr(V), size(V, 1), size(W, 2), alpha, beta))
+    return W
+end
+
+# solve!(kkt, ::AbstractMatrix) with the products with A / A' of its stages, and its refinement residuals, on the block of
+# all columns instead of column by column (madqp_kkt_set_block_products; off by default)
+function block_products!(kkt::HIPKKTSystem, on::Bool)
+    check(kkt.ctx, ccall((:madqp_kkt_set_block_products, libmadqp), Int32, (Ptr{Cvoid}, Int32), kkt.handle, Int32(on)))
+    return kkt
+end
+
 # --------------------------------------------------------------------------- one QP over a P x Q grid of GPUs
 # SURVEY.md 8e / BASELINE configs[4]: every rank runs the SAME MadIPM loop on replicated vectors (identical branches:
 # every scalar is computed from bitwise identical vectors); only this KKT system knows that K = H + Sigma_x + A' Theta A,

@@ -230,6 +230,20 @@ function mul!(w::MadNLP.AbstractKKTVector{T}, kkt::HIPSparseKKTSystem, v::MadNLP
     return w
 end
 
+# the block forms of MadQPHIP.jl for this KKT type: W[:, c] <- alpha K V[:, c] + beta W[:, c] (madqp_kkt_mul_many: with
+# sparse A and H bitwise the column loop over mul!), and the switch of solve!(kkt, ::AbstractMatrix) to block products
+function mul!(W::AbstractMatrix, kkt::HIPSparseKKTSystem, V::AbstractMatrix, alpha = 1.0, beta = 0.0)
+    check(kkt.ctx, ccall((:madqp_kkt_mul_many, libmadqp), Int32,
+                         (Ptr{Cvoid}, Ref{CState}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Float64, Float64),
+                         kkt.handle, kkt.cstate, dptr(W), size(W, 1), dptr(V), size(V, 1), size(W, 2), alpha, beta))
+    return W
+end
+
+function block_products!(kkt::HIPSparseKKTSystem, on::Bool)
+    check(kkt.ctx, ccall((:madqp_kkt_set_block_products, libmadqp), Int32, (Ptr{Cvoid}, Int32), kkt.handle, Int32(on)))
+    return kkt
+end
+
 # --------------------------------------------------------------------------- src/kernels.jl on the device
 # The overrides of MadQPHIP.jl dispatch on its own KKT types; these are the same calls for the sparse types (`state` and
 # the macro `@k` are MadQPHIP's: the full state view of one solver, and check(ccall(name, ctx, state, args...))).

@@ -146,6 +146,7 @@ _SIGNATURES = {
     "madqp_chol_set_solve_many_min": [vp, i64],
     "madqp_chol_solve_many_info": [vp, i64, pi64],
     "madqp_gemv": [vp, i32, i64, i64, f64, vp, i64, vp, f64, vp],
+    "madqp_gemv_many": [vp, i32, i64, i64, i64, f64, vp, i64, vp, i64, f64, vp, i64],
     "madqp_set_aug_diagonal_reg": [vp, pstate, f64, f64],
     "madqp_set_initial_primal_rhs": [vp, pstate],
     "madqp_set_initial_dual_rhs": [vp, pstate],
@@ -184,6 +185,9 @@ _SIGNATURES = {
     "madqp_kkt_factorize": [vp, pi32],
     "madqp_kkt_solve": [vp, pstate, vp],
     "madqp_kkt_solve_many": [vp, pstate, vp, i64, i64],
+    "madqp_kkt_mul_many": [vp, pstate, vp, i64, vp, i64, i64, f64, f64],
+    "madqp_kkt_set_block_products": [vp, i32],
+    "madqp_kkt_many_info": [vp, i64, pi64],
     "madqp_kkt_set_refine": [vp, C.c_int32],
     "madqp_kkt_mul": [vp, pstate, vp, vp, f64, f64],
     "madqp_kkt_mul_solved": [vp, pstate, vp, vp, f64, f64],

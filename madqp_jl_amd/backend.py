@@ -216,6 +216,11 @@ class HipBackend:
     def gemv(self, trans, rows, cols, alpha, A, lda, x, beta, y):
         self._ck(self.lib.madqp_gemv(self.ctx, trans, rows, cols, alpha, ptr(A), lda, ptr(x), beta, ptr(y)))
 
+    def gemv_many(self, trans, rows, cols, nrhs, alpha, A, lda, X, ldx, beta, Y, ldy):
+        """``Y[:, c] = alpha op(A) X[:, c] + beta Y[:, c]`` for ``c < nrhs`` (``madqp_gemv_many``): column c of X at
+        ``X + c ldx``, of Y at ``Y + c ldy``; A is read once per 128 columns."""
+        self._ck(self.lib.madqp_gemv_many(self.ctx, trans, rows, cols, nrhs, alpha, ptr(A), lda, ptr(X), ldx, beta, ptr(Y), ldy))
+
     # ---- src/kernels.jl ----
     def set_aug_diagonal_reg(self, st, del_w, del_c):
         self._ck(self.lib.madqp_set_aug_diagonal_reg(self.ctx, C.byref(st.cstruct), del_w, del_c))
@@ -446,6 +451,22 @@ class HipBackend:
     def kkt_mul(self, h, st, w, v, alpha, beta, solved=False):
         f = self.lib.madqp_kkt_mul_solved if solved else self.lib.madqp_kkt_mul
         self._ck(f(h, C.byref(st.cstruct), ptr(w), ptr(v), alpha, beta))
+
+    def kkt_mul_many(self, h, st, W, V, alpha, beta):
+        """Row c of ``W`` <- alpha K (row c of ``V``) + beta (row c of ``W``); both ``(nrhs, ld)`` blocks, ld = the row stride."""
+        nrhs = W.shape[0]
+        ld = lambda T: T.stride(0) if nrhs > 1 else T.shape[1]
+        self._ck(self.lib.madqp_kkt_mul_many(h, C.byref(st.cstruct), ptr(W), ld(W), ptr(V), ld(V), nrhs, alpha, beta))
+
+    def kkt_set_block_products(self, h, on):
+        self._ck(self.lib.madqp_kkt_set_block_products(h, 1 if on else 0))
+
+    def kkt_many_info(self, h, nrhs):
+        """``(path, passes over A, passes over H, workspace_doubles)`` of a ``kkt_solve_many`` with ``nrhs`` right-hand sides:
+        path 0 the column loop, 1 the block products."""
+        out = (C.c_int64 * 4)()
+        self._ck(self.lib.madqp_kkt_many_info(h, int(nrhs), out))
+        return tuple(out)
 
     def kkt_jtprod(self, h, out, y):
         self._ck(self.lib.madqp_kkt_jtprod(h, ptr(out), ptr(y)))

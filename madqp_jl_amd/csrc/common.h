@@ -190,6 +190,13 @@ int32_t madqp_chol_factor_batched(madqp_ctx* ctx, double* A, int64_t lda, int64_
 int32_t madqp_gemv_impl(madqp_ctx* ctx, int32_t trans, int64_t rows, int64_t cols, double alpha,
                         const double* A, int64_t lda, const double* x, double beta, double* y,
                         int prof_cls);
+// gemv_many.hip: the same product on nrhs columns (X + c ldx -> Y + c ldy), A read once per MADQP_GEMV_MANY_GROUP columns.
+// work: at least madqp_gemv_many_workspace(..) doubles for the partial sums of the k ranges, or nullptr = the context's
+constexpr int64_t MADQP_GEMV_MANY_GROUP = 128;  // MANY_TC of many_plan.inc
+int64_t madqp_gemv_many_workspace(int32_t trans, int64_t rows, int64_t cols, int64_t nrhs);
+int32_t madqp_gemv_many_impl(madqp_ctx* ctx, int32_t trans, int64_t rows, int64_t cols, int64_t nrhs, double alpha,
+                             const double* A, int64_t lda, const double* X, int64_t ldx, double beta, double* Y, int64_t ldy,
+                             double* work, int prof_cls);
 
 // y(n) = alpha H x + beta y for a symmetric H (row r at H + r*ldh) from its LOWER triangle only: half the bytes of the
 // general product (gemv.hip)
@@ -208,6 +215,10 @@ struct Csr {
 };
 int32_t madqp_spmv_csr(madqp_ctx* ctx, int64_t rows, const Csr& a, double alpha, const double* x, double beta, double* y,
                        int prof_cls);
+// the same on nrhs columns, bitwise the column loop; the CSR arrays are read once per MADQP_SPMM_GROUP columns
+constexpr int MADQP_SPMM_GROUP = 32;
+int32_t madqp_spmm_csr(madqp_ctx* ctx, int64_t rows, const Csr& a, double alpha, const double* X, int64_t ldx, double beta,
+                       double* Y, int64_t ldy, int64_t nrhs, int prof_cls);
 // C = base + diag(dvec) + V diag(w) V' (lower triangle) from the rows of V (v) and the rows of V' (vt); the base dense
 // (base, ldbase), a symmetric matrix with both triangles in CSR (b), or none
 int32_t madqp_sparse_gram(madqp_ctx* ctx, int64_t n, const Csr& v, const Csr& vt, const double* w, const double* base,

@@ -67,6 +67,11 @@ struct madqp_kkt {
     // madqp_kkt_solve_many: the work vectors t, u, tn, b of its columns, one grow-only buffer (kkt_many_work)
     double* many = nullptr;
     int64_t many_cap = 0;
+    // products on a block of vectors (apply_A_many / apply_At_many / apply_H_many): the partial sums of the dense kernel's k
+    // ranges (mw) and the A V block of madqp_kkt_mul_many (mu), grow-only; block: madqp_kkt_set_block_products
+    double *mw = nullptr, *mu = nullptr;
+    int64_t mw_cap = 0, mu_cap = 0;
+    bool block = false;
     // fused per-variable passes of the condensed mode (solve_pre_kernel / solve_post_kernel / resid_tail_kernel below):
     // where each variable sits in the two bound lists (-1: not there), built when the lists are first seen (grow-only
     // buffers, allocated with rs at the first fused pass), and the reduced right-hand side of the slacks kept between the
@@ -412,6 +417,48 @@ static int32_t apply_H(madqp_kkt* k, double alpha, const double* x, double beta,
     ProfScope ps(ctx, MADQP_PROF_VEC);
     LAUNCH(hdiag_mul_kernel, k->nx, k->nx, alpha, k->hdiag, x, beta, y);
     return MADQP_OK;
+}
+
+// The three operators on a block of nrhs vectors (column c of X at X + c ldx, of Y at Y + c ldy), dispatched as above.  The
+// CSR forms are bitwise the column loop over the one-vector operator (madqp_spmm_csr), and so is the diagonal H; the dense
+// forms read the matrix once per MADQP_GEMV_MANY_GROUP columns (madqp_gemv_many_impl; the dense H is full symmetric storage
+// and goes through the same kernel).  The partial sums of the dense kernel live in k->mem and grow at the first call that
+// needs more.
+static int32_t dense_many(madqp_kkt* k, int32_t trans, int64_t rows, int64_t cols, int64_t nrhs, double alpha, const double* A,
+                          int64_t lda, const double* X, int64_t ldx, double beta, double* Y, int64_t ldy) {
+    const int64_t need = madqp_gemv_many_workspace(trans, rows, cols, nrhs);
+    if (need)
+        if (int32_t r = k->mem.grow(&k->mw, &k->mw_cap, need, "block products: partial sums")) return r;
+    return madqp_gemv_many_impl(k->ctx, trans, rows, cols, nrhs, alpha, A, lda, X, ldx, beta, Y, ldy, k->mw, MADQP_PROF_GEMV);
+}
+static int32_t apply_A_many(madqp_kkt* k, double alpha, const double* X, int64_t ldx, double beta, double* Y, int64_t ldy,
+                            int64_t nrhs) {
+    if (k->a.ptr) return madqp_spmm_csr(k->ctx, k->m, k->a, alpha, X, ldx, beta, Y, ldy, nrhs, MADQP_PROF_GEMV);
+    if (k->A) return dense_many(k, 0, k->m, k->nx, nrhs, alpha, k->A, k->lda, X, ldx, beta, Y, ldy);
+    return dense_many(k, 1, k->nx, k->m, nrhs, alpha, k->At, k->ldat, X, ldx, beta, Y, ldy);
+}
+static int32_t apply_At_many(madqp_kkt* k, double alpha, const double* X, int64_t ldx, double beta, double* Y, int64_t ldy,
+                             int64_t nrhs) {
+    if (k->a.ptr) return madqp_spmm_csr(k->ctx, k->nx, k->at, alpha, X, ldx, beta, Y, ldy, nrhs, MADQP_PROF_GEMV);
+    if (k->A) return dense_many(k, 1, k->m, k->nx, nrhs, alpha, k->A, k->lda, X, ldx, beta, Y, ldy);
+    return dense_many(k, 0, k->nx, k->m, nrhs, alpha, k->At, k->ldat, X, ldx, beta, Y, ldy);
+}
+static int32_t apply_H_many(madqp_kkt* k, double alpha, const double* X, int64_t ldx, double beta, double* Y, int64_t ldy,
+                            int64_t nrhs) {
+    madqp_ctx* ctx = k->ctx;
+    if (!kkt_has_H(k)) return MADQP_OK;
+    ARG_TRY(ctx, beta == 0.0 || beta == 1.0);
+    if (k->H) return dense_many(k, 0, k->nx, k->nx, nrhs, alpha, k->H, k->ldh, X, ldx, beta, Y, ldy);
+    if (k->h.ptr) return madqp_spmm_csr(ctx, k->nx, k->h, alpha, X, ldx, beta, Y, ldy, nrhs, MADQP_PROF_GEMV);
+    ProfScope ps(ctx, MADQP_PROF_VEC);
+    for (int64_t c = 0; c < nrhs; ++c) LAUNCH(hdiag_mul_kernel, k->nx, k->nx, alpha, k->hdiag, X + c * ldx, beta, Y + c * ldy);
+    return MADQP_OK;
+}
+// passes over the arrays of A (or A') / of H that ONE product on nrhs columns makes: per column, or per group of the block form
+static int64_t kkt_passes(int64_t nrhs, bool block, bool csr) {
+    if (!block || nrhs < 2) return nrhs;
+    const int64_t g = csr ? MADQP_SPMM_GROUP : MADQP_GEMV_MANY_GROUP;
+    return (nrhs + g - 1) / g;
 }
 
 extern "C" int32_t madqp_kkt_destroy(madqp_kkt* k) {
@@ -934,27 +981,52 @@ static double* kkt_factor_rhs(const madqp_kkt* k, const madqp_state* st, double*
 }
 
 // The middle of a solve, two functions per form around the factor solve: on entry of `before` w holds the reduced
-// right-hand side [r1; r2; ..], on return of `after` dx (with ds) in wx and dy in wy.
-static int32_t kkt_normal_before(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk) {  // src/KKT/normalkkt.jl:185-201
+// right-hand side [r1; r2; ..], on return of `after` dx (with ds) in wx and dy in wy.  Each is three pieces in order -- the
+// vector passes in front of the form's product with A or A' (part KKT_HEAD), the product (KKT_PRODUCT), the vector passes
+// behind it (KKT_TAIL) -- so that a many-column solve can run the product of all columns as one block between them
+// (kkt_stage_product / kkt_solve_many_once).  A one-vector solve asks for all three.
+enum { KKT_HEAD = 1, KKT_PRODUCT = 2, KKT_TAIL = 4, KKT_ALL = 7 };
+// the product of a stage: y <- op x + beta y on the vectors of one column (op: 0 none, 1 A, 2 A')
+struct KktProduct {
+    int op;
+    const double* x;
+    double beta;
+    double* y;
+};
+static int32_t kkt_run_product(madqp_kkt* k, const KktProduct& p) {
+    return p.op == 1 ? apply_A(k, 1.0, p.x, p.beta, p.y) : p.op == 2 ? apply_At(k, 1.0, p.x, p.beta, p.y) : MADQP_OK;
+}
+static KktProduct kkt_before_product(const madqp_kkt* k, const madqp_state* st, double* w, const KktWork& wk) {
+    if (k->mode == KKT_NORMAL) return KktProduct{1, wk.tn, 0.0, wk.u};                   // A r1
+    if (k->mode == KKT_CONDENSED && k->m) return KktProduct{2, wk.u, 1.0, w};              // rhs_x = r1_x + A' (theta t)
+    return KktProduct{0, nullptr, 0.0, nullptr};
+}
+static KktProduct kkt_after_product(const madqp_kkt* k, const madqp_state* st, double* w, const KktWork& wk) {
+    if (k->mode == KKT_NORMAL) return KktProduct{2, w + st->n, 0.0, wk.tn};               // A' dy
+    if (k->mode == KKT_CONDENSED && k->m) return KktProduct{1, w, 0.0, wk.u};              // A dx
+    return KktProduct{0, nullptr, 0.0, nullptr};
+}
+static int32_t kkt_normal_before(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk, int parts) {  // src/KKT/normalkkt.jl:185-201
     int32_t r = 0;
     madqp_ctx* ctx = k->ctx;
     const double* sig = k->hdiag ? k->sg : st->pr_diag;  // H + Sigma
-    {
+    if (parts & KKT_HEAD) {
         ProfScope ps(ctx, MADQP_PROF_VEC);
         if (st->n) LAUNCH(div_kernel, st->n, st->n, wx, sig, wk.tn);  // r1 = (H + Sigma)^-1 wx
     }
-    if ((r = apply_A(k, 1.0, wk.tn, 0.0, wk.u))) return r;
-    if (k->m) {
+    if ((parts & KKT_PRODUCT) && (r = kkt_run_product(k, kkt_before_product(k, st, wx, wk)))) return r;
+    if ((parts & KKT_TAIL) && k->m) {
         ProfScope ps(ctx, MADQP_PROF_VEC);
         LAUNCH(normal_rhs_kernel, k->m, k->m, k->d_slot, wk.u, wk.tn + k->nx, wy, wy);  // A r1 - r2
     }
     return MADQP_OK;  // the factor: wy = dy
 }
-static int32_t kkt_normal_after(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk) {
+static int32_t kkt_normal_after(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk, int parts) {
     int32_t r = 0;
     madqp_ctx* ctx = k->ctx;
     const double* sig = k->hdiag ? k->sg : st->pr_diag;
-    if ((r = apply_At(k, 1.0, wy, 0.0, wk.tn))) return r;
+    if ((parts & KKT_PRODUCT) && (r = kkt_run_product(k, kkt_after_product(k, st, wx, wk)))) return r;
+    if (!(parts & KKT_TAIL)) return MADQP_OK;
     ProfScope ps(ctx, MADQP_PROF_VEC);
     if (k->ns) LAUNCH(jt_slack_kernel, k->ns, k->ns, k->d_ind_ineq, wy, wk.tn + k->nx, 1.0, 0.0);
     if (st->n) LAUNCH(normal_back_kernel, st->n, st->n, wk.tn, sig, wx);
@@ -979,21 +1051,24 @@ static int32_t kkt_augmented_after(madqp_kkt* k, const madqp_state* st, double* 
     }
     return MADQP_OK;
 }
-static int32_t kkt_condensed_before(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk) {
+static int32_t kkt_condensed_before(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk, int parts) {
     madqp_ctx* ctx = k->ctx;
     if (k->m) {
-        {
+        if (parts & KKT_HEAD) {
             ProfScope ps(ctx, MADQP_PROF_VEC);
             LAUNCH(condense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, wx, wy, wk.t, wk.u);
         }
-        if (int32_t r = apply_At(k, 1.0, wk.u, 1.0, wx)) return r;  // rhs_x = r1_x + A' (theta t)
+        if (parts & KKT_PRODUCT)
+            if (int32_t r = kkt_run_product(k, kkt_before_product(k, st, wx, wk))) return r;
     }
     return MADQP_OK;  // the factor: wx = dx
 }
-static int32_t kkt_condensed_after(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk) {
+static int32_t kkt_condensed_after(madqp_kkt* k, const madqp_state* st, double* wx, double* wy, const KktWork& wk, int parts) {
     madqp_ctx* ctx = k->ctx;
     if (k->m) {
-        if (int32_t r = apply_A(k, 1.0, wx, 0.0, wk.u)) return r;
+        if (parts & KKT_PRODUCT)
+            if (int32_t r = kkt_run_product(k, kkt_after_product(k, st, wx, wk))) return r;
+        if (!(parts & KKT_TAIL)) return MADQP_OK;
         ProfScope ps(ctx, MADQP_PROF_VEC);
         LAUNCH(decondense_kernel, k->m, k->m, k->nx, k->d_slot, st->pr_diag, k->theta, wk.t, wk.u, wx, wy);
     }
@@ -1001,28 +1076,29 @@ static int32_t kkt_condensed_after(madqp_kkt* k, const madqp_state* st, double* 
 }
 
 // The three stages of a solve.  Before the factor solve: reduce_rhs! and the first half of the form's middle -- the K2.5
-// object with its sign-flipped first and last step.
-static int32_t kkt_solve_before(madqp_kkt* k, const madqp_state* st, double* w, const KktWork& wk) {
+// object with its sign-flipped first and last step.  parts: see KKT_HEAD above (reduce_rhs! belongs to the head,
+// finish_aug_solve! to the tail; the augmented forms have no product: their middle is head and tail at once).
+static int32_t kkt_solve_before(madqp_kkt* k, const madqp_state* st, double* w, const KktWork& wk, int parts = KKT_ALL) {
     int32_t r = 0;
     madqp_ctx* ctx = k->ctx;
-    if (k->scaled) {  // r1 = p_x + p_zl / l_diag + p_zu / u_diag (signs of src/kernels.jl:157-158)
+    if ((parts & KKT_HEAD) && k->scaled) {  // r1 = p_x + p_zl / l_diag + p_zu / u_diag (signs of src/kernels.jl:157-158)
         ProfScope ps(ctx, MADQP_PROF_VEC);
         if (st->nlb) LAUNCH(k25_reduce_kernel, st->nlb, *st, w);
         if (st->nub) LAUNCH(k25_reduce_ub_kernel, st->nub, *st, w);
-    } else if ((r = madqp_reduce_rhs(ctx, st, w))) {
+    } else if ((parts & KKT_HEAD) && (r = madqp_reduce_rhs(ctx, st, w))) {
         return r;
     }
-    return k->mode == KKT_NORMAL      ? kkt_normal_before(k, st, w, w + st->n, wk)
-           : k->mode == KKT_AUGMENTED ? kkt_augmented_before(k, st, w, w + st->n, wk)
-                                      : kkt_condensed_before(k, st, w, w + st->n, wk);
+    return k->mode == KKT_NORMAL      ? kkt_normal_before(k, st, w, w + st->n, wk, parts)
+           : k->mode == KKT_AUGMENTED ? ((parts & KKT_HEAD) ? kkt_augmented_before(k, st, w, w + st->n, wk) : MADQP_OK)
+                                      : kkt_condensed_before(k, st, w, w + st->n, wk, parts);
 }
 // after it: the second half of the middle and finish_aug_solve!
-static int32_t kkt_solve_after(madqp_kkt* k, const madqp_state* st, double* w, const KktWork& wk) {
+static int32_t kkt_solve_after(madqp_kkt* k, const madqp_state* st, double* w, const KktWork& wk, int parts = KKT_ALL) {
     madqp_ctx* ctx = k->ctx;
-    const int32_t r = k->mode == KKT_NORMAL      ? kkt_normal_after(k, st, w, w + st->n, wk)
-                      : k->mode == KKT_AUGMENTED ? kkt_augmented_after(k, st, w, w + st->n, wk)
-                                                 : kkt_condensed_after(k, st, w, w + st->n, wk);
-    if (r) return r;
+    const int32_t r = k->mode == KKT_NORMAL      ? kkt_normal_after(k, st, w, w + st->n, wk, parts)
+                      : k->mode == KKT_AUGMENTED ? ((parts & KKT_TAIL) ? kkt_augmented_after(k, st, w, w + st->n, wk) : MADQP_OK)
+                                                 : kkt_condensed_after(k, st, w, w + st->n, wk, parts);
+    if (r || !(parts & KKT_TAIL)) return r;
     if (k->scaled) {
         ProfScope ps(ctx, MADQP_PROF_VEC);
         if (std::max(st->nlb, st->nub) > 0) LAUNCH(k25_finish_kernel, std::max(st->nlb, st->nub), *st, w);
@@ -1046,7 +1122,9 @@ static int32_t kkt_solve_once(madqp_kkt* k, const madqp_state* st, double* w) {
 // The same three stages with the middle one shared: stage 1 for every column, ONE madqp_chol_solve_many on the column-major
 // matrix that the columns' factor right-hand sides form where they stand (dy / dx inside W with leading dimension ldw; the
 // augmented form's b vectors in a block of their own), stage 3 for every column.  The per-column passes are the kernels of
-// the one-vector solve launched on offset pointers, the products with A / A' stay mat-vecs per column.
+// the one-vector solve launched on offset pointers.  The products with A / A' are mat-vecs per column too, unless
+// madqp_kkt_set_block_products is on: then the product of each stage runs once on the block of all columns
+// (apply_A_many / apply_At_many) between the heads and the tails of the columns' stage.
 // column c of the work blocks: [t | u | tn | b], each a block of nrhs columns at a stride of whole 256 bytes
 static int64_t kkt_pad32(int64_t v) { return (v + 31) / 32 * 32; }
 // the stride of the augmented form's b block: the order of the factorised matrix (kkt_form.inc), padded
@@ -1067,13 +1145,36 @@ static int32_t kkt_solve_many_once(madqp_kkt* k, const madqp_state* st, double* 
     const int64_t per = 2 * kkt_pad32(k->m) + (k->mode == KKT_NORMAL ? kkt_pad32(st->n) : 0) + kkt_many_sb(k);
     if ((r = k->mem.grow(&k->many, &k->many_cap, nrhs * per, "madqp_kkt_solve_many: work vectors of the columns"))) return r;
     k->u_is_A_of = nullptr;
-    for (int64_t c = 0; c < nrhs; ++c)
-        if ((r = kkt_solve_before(k, st, W + c * ldw, kkt_many_work(k, st, nrhs, c)))) return r;
+    // a stage of every column: whole per column, or heads, ONE product on the block, tails (the operands of the columns'
+    // products sit at one stride each: ldw inside W, the strides of the work blocks)
+    const KktWork w0 = kkt_many_work(k, st, nrhs, 0), w1 = kkt_many_work(k, st, nrhs, 1);
+    auto stage = [&](bool before) -> int32_t {
+        auto run = [&](int64_t c, int parts) {
+            return before ? kkt_solve_before(k, st, W + c * ldw, kkt_many_work(k, st, nrhs, c), parts)
+                          : kkt_solve_after(k, st, W + c * ldw, kkt_many_work(k, st, nrhs, c), parts);
+        };
+        const KktProduct p0 = before ? kkt_before_product(k, st, W, w0) : kkt_after_product(k, st, W, w0);
+        const KktProduct p1 = before ? kkt_before_product(k, st, W + ldw, w1) : kkt_after_product(k, st, W + ldw, w1);
+        int32_t rr = 0;
+        if (!k->block || !p0.op) {
+            for (int64_t c = 0; c < nrhs; ++c)
+                if ((rr = run(c, KKT_ALL))) return rr;
+            return MADQP_OK;
+        }
+        for (int64_t c = 0; c < nrhs; ++c)
+            if ((rr = run(c, KKT_HEAD))) return rr;
+        const int64_t ldx = p1.x - p0.x, ldy = p1.y - p0.y;
+        if ((rr = p0.op == 1 ? apply_A_many(k, 1.0, p0.x, ldx, p0.beta, p0.y, ldy, nrhs)
+                             : apply_At_many(k, 1.0, p0.x, ldx, p0.beta, p0.y, ldy, nrhs)))
+            return rr;
+        for (int64_t c = 0; c < nrhs; ++c)
+            if ((rr = run(c, KKT_TAIL))) return rr;
+        return MADQP_OK;
+    };
+    if ((r = stage(true))) return r;
     const int64_t ldb = k->mode == KKT_AUGMENTED ? kkt_many_sb(k) : ldw;
-    if ((r = madqp_chol_solve_many(k->chol, kkt_factor_rhs(k, st, W, kkt_many_work(k, st, nrhs, 0)), ldb, nrhs))) return r;
-    for (int64_t c = 0; c < nrhs; ++c)
-        if ((r = kkt_solve_after(k, st, W + c * ldw, kkt_many_work(k, st, nrhs, c)))) return r;
-    return MADQP_OK;
+    if ((r = madqp_chol_solve_many(k->chol, kkt_factor_rhs(k, st, W, w0), ldb, nrhs))) return r;
+    return stage(false);
 }
 
 extern "C" int32_t madqp_kkt_solve_many(madqp_kkt* k, const madqp_state* st, double* W, int64_t ldw, int64_t nrhs) {
@@ -1096,8 +1197,9 @@ extern "C" int32_t madqp_kkt_solve_many(madqp_kkt* k, const madqp_state* st, dou
     for (int32_t it = 0; it < k->refine; ++it) {
         for (int64_t c = 0; c < nrhs; ++c) {
             if ((r = madqp_copy(ctx, len, rf_p + c * stride, rf_r + c * stride))) return r;
-            if ((r = madqp_kkt_mul(k, st, rf_r + c * stride, W + c * ldw, -1.0, 1.0))) return r;  // r = p - K w
+            if (!k->block && (r = madqp_kkt_mul(k, st, rf_r + c * stride, W + c * ldw, -1.0, 1.0))) return r;  // r = p - K w
         }
+        if (k->block && (r = madqp_kkt_mul_many(k, st, rf_r, stride, W, ldw, nrhs, -1.0, 1.0))) return r;  // R = P - K W
         if ((r = kkt_solve_many_once(k, st, rf_r, stride, nrhs))) return r;
         for (int64_t c = 0; c < nrhs; ++c)
             if ((r = madqp_axpy(ctx, len, 1.0, rf_r + c * stride, W + c * ldw))) return r;  // w += K^-1 r
@@ -1121,6 +1223,8 @@ extern "C" int32_t madqp_kkt_jtprod(madqp_kkt* k, double* out, const double* y) 
 
 static int32_t kkt_mul_impl(madqp_kkt* k, const madqp_state* st, double* w, const double* v, double alpha, double beta,
                             bool v_is_last_solution);
+static int32_t kkt_mul_tail(madqp_kkt* k, const madqp_state* st, double* w, const double* v, double alpha, double beta,
+                            const double* u);
 extern "C" int32_t madqp_kkt_mul(madqp_kkt* k, const madqp_state* st, double* w, const double* v,
                                  double alpha, double beta) {
     return kkt_mul_impl(k, st, w, v, alpha, beta, false);
@@ -1135,18 +1239,27 @@ static int32_t kkt_mul_impl(madqp_kkt* k, const madqp_state* st, double* w, cons
     if (r) return r;
     madqp_ctx* ctx = k->ctx;
     ARG_TRY(ctx, w && v);
-    const int64_t nx = k->nx, n = st->n;
+    const int64_t n = st->n;
     const bool have_Av = v_is_last_solution && k->m && k->u_is_A_of == v;  // the solve's own A dx, same kernel and operands
     k->u_is_A_of = nullptr;
     // wx = alpha A_full' vy + beta wx  (+ alpha H vx)
     if ((r = apply_At(k, alpha, v + n, beta, w))) return r;
     if ((r = apply_H(k, alpha, v, 1.0, w))) return r;
+    if (k->m && !have_Av && (r = apply_A(k, 1.0, v, 0.0, k->u))) return r;
+    return kkt_mul_tail(k, st, w, v, alpha, beta, k->u);
+}
+// The per-variable passes of w = alpha K v + beta w behind the three matrix products: w[0 .. nx) holds
+// alpha (A' vy + H vx) + beta wx, u = A vx.
+static int32_t kkt_mul_tail(madqp_kkt* k, const madqp_state* st, double* w, const double* v, double alpha, double beta,
+                            const double* u) {
+    int32_t r = 0;
+    madqp_ctx* ctx = k->ctx;
+    const int64_t nx = k->nx, n = st->n;
     if (kkt_fusable(k)) {  // the five per-variable passes that follow, in one (resid_tail_kernel)
-        if (!have_Av && (r = apply_A(k, 1.0, v, 0.0, k->u))) return r;
         if ((r = ensure_pos(k, st))) return r;
         const int64_t L = std::max(std::max(st->n, st->m), std::max(st->nlb, st->nub));
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        LAUNCH(resid_tail_kernel, L, *st, w, v, alpha, beta, nx, k->d_slot, k->d_ind_ineq, k->u, k->pos_lb, k->pos_ub);
+        LAUNCH(resid_tail_kernel, L, *st, w, v, alpha, beta, nx, k->d_slot, k->d_ind_ineq, u, k->pos_lb, k->pos_ub);
         return MADQP_OK;
     }
     if (k->ns) {
@@ -1155,9 +1268,8 @@ static int32_t kkt_mul_impl(madqp_kkt* k, const madqp_state* st, double* w, cons
     }
     // wy = alpha A_full vx + beta wy
     if (k->m) {
-        if (!have_Av && (r = apply_A(k, 1.0, v, 0.0, k->u))) return r;
         ProfScope ps(ctx, MADQP_PROF_VEC);
-        LAUNCH(mul_rows_kernel, k->m, k->m, k->d_slot, k->u, v + nx, w + n, alpha, beta);
+        LAUNCH(mul_rows_kernel, k->m, k->m, k->d_slot, u, v + nx, w + n, alpha, beta);
     }
     if (k->scaled) {  // mul!(w, ::ScaledSparseKKTSystem, v): zl dx + l_diag dzl, zu dx - u_diag dzu
         ProfScope ps(ctx, MADQP_PROF_VEC);
@@ -1167,6 +1279,51 @@ static int32_t kkt_mul_impl(madqp_kkt* k, const madqp_state* st, double* w, cons
         return MADQP_OK;
     }
     return madqp_kktmul(ctx, st, w, v, alpha, beta);
+}
+
+// mul! for nrhs pairs of columns: the three matrix products once on the block (apply_*_many), the per-variable tail per
+// column on offset pointers.  The A V block is the object's (k->mu, a column per 256-byte stride).
+extern "C" int32_t madqp_kkt_mul_many(madqp_kkt* k, const madqp_state* st, double* W, int64_t ldw, const double* V, int64_t ldv,
+                                      int64_t nrhs, double alpha, double beta) {
+    int32_t r = check_kkt_state(k, st);
+    if (r) return r;
+    madqp_ctx* ctx = k->ctx;
+    const int64_t len = st->n + st->m + st->nlb + st->nub, n = st->n;
+    ARG_TRY(ctx, nrhs >= 0 && ldw >= len && ldv >= len);
+    if (nrhs == 0) return MADQP_OK;
+    ARG_TRY(ctx, W && V && W != V);
+    if (nrhs == 1) return madqp_kkt_mul(k, st, W, V, alpha, beta);
+    const int64_t sm = kkt_pad32(k->m);
+    if ((r = k->mem.grow(&k->mu, &k->mu_cap, nrhs * sm, "madqp_kkt_mul_many: the A V block"))) return r;
+    k->u_is_A_of = nullptr;
+    if ((r = apply_At_many(k, alpha, V + n, ldv, beta, W, ldw, nrhs))) return r;
+    if ((r = apply_H_many(k, alpha, V, ldv, 1.0, W, ldw, nrhs))) return r;
+    if (k->m && (r = apply_A_many(k, 1.0, V, ldv, 0.0, k->mu, sm, nrhs))) return r;
+    for (int64_t c = 0; c < nrhs; ++c)
+        if ((r = kkt_mul_tail(k, st, W + c * ldw, V + c * ldv, alpha, beta, k->mu + c * sm))) return r;
+    return MADQP_OK;
+}
+
+extern "C" int32_t madqp_kkt_set_block_products(madqp_kkt* k, int32_t on) {
+    if (!k) return MADQP_ERR_ARG;
+    ARG_TRY(k->ctx, on == 0 || on == 1);
+    k->block = on != 0;
+    return MADQP_OK;
+}
+
+// what madqp_kkt_solve_many of nrhs columns would run as (include/madqp.h)
+extern "C" int32_t madqp_kkt_many_info(madqp_kkt* k, int64_t nrhs, int64_t* out_host) {
+    if (!k) return MADQP_ERR_ARG;
+    ARG_TRY(k->ctx, out_host && nrhs >= 0);
+    const bool block = k->block && nrhs >= 2;
+    const int64_t stage_products = (k->mode == KKT_NORMAL || (k->mode == KKT_CONDENSED && k->m)) ? 2 : 0;  // one per stage
+    const int64_t mul_products = 1 + (k->m ? 1 : 0);                                                        // A' and A of a residual
+    const int64_t steps = std::max<int32_t>(k->refine, 0);
+    out_host[0] = block ? 1 : 0;
+    out_host[1] = (stage_products + steps * mul_products) * kkt_passes(nrhs, block, k->a.ptr != nullptr);
+    out_host[2] = !kkt_has_H(k) ? 0 : steps * (k->hdiag ? nrhs : kkt_passes(nrhs, block, k->h.ptr != nullptr));
+    out_host[3] = k->many_cap + k->rf_cap + k->mw_cap + k->mu_cap;
+    return MADQP_OK;
 }
 
 // objective pieces into 2 slots (q'x and x'Hx; obj = c0 + s0 + s1/2), gradient and constraint values into st

@@ -32,6 +32,44 @@ __global__ __launch_bounds__(256) void spmv_csr_kernel(int64_t rows, const int64
     if (r < rows && sub == 0) y[r] = (beta == 0.0) ? alpha * acc : alpha * acc + beta * y[r];
 }
 
+// The same product on a block of vectors, Y[:, c] = alpha M X[:, c] + beta Y[:, c]: the quarter wave of a row keeps CG
+// columns' sums at once, so the row pointers, indices and values are read once per group of CG columns (blockIdx.y)
+// instead of once per column.  Every (row, column) sum is spmv_csr_kernel's: the same entries per lane in the same order,
+// the same multiply and add, the same shuffle reduction and the same last line -- bitwise the column loop over it.
+template <int CG>
+__global__ __launch_bounds__(256) void spmm_csr_kernel(int64_t rows, const int64_t* __restrict__ rowptr,
+                                                       const int64_t* __restrict__ col, const double* __restrict__ val,
+                                                       double alpha, const double* __restrict__ X, int64_t ldx, double beta,
+                                                       double* __restrict__ Y, int64_t ldy, int64_t nrhs) {
+    const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4;
+    const int sub = threadIdx.x & 15;
+    const int64_t c0 = (int64_t)blockIdx.y * CG;
+    const int nc = (int)(nrhs - c0 < CG ? nrhs - c0 : CG);
+    double acc[CG];
+#pragma unroll
+    for (int c = 0; c < CG; ++c) acc[c] = 0.0;
+    if (r < rows) {
+        const int64_t e = rowptr[r + 1];
+        for (int64_t p = rowptr[r] + sub; p < e; p += 16) {
+            const double v = val[p];
+            const double* __restrict__ x = X + col[p] + c0 * ldx;
+#pragma unroll
+            for (int c = 0; c < CG; ++c)
+                if (c < nc) acc[c] += v * x[c * ldx];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < CG; ++c) {
+        double a = acc[c];
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) a += __shfl_down(a, off, 16);
+        if (c < nc && r < rows && sub == 0) {
+            double* y = Y + r + (c0 + c) * ldy;
+            *y = (beta == 0.0) ? alpha * a : alpha * a + beta * *y;
+        }
+    }
+}
+
 // Column j of the lower triangle of C = base + diag(dvec) + V diag(w) V' is owned by one workgroup:
 //   C[j:n, j] <- base[j:n, j] (+ dvec[j] on the diagonal), one contiguous, coalesced run of the column-major
 //   matrix; then for every stored entry (j, k) of row j of V, in ascending k, the column k of V (= row k of V',
@@ -154,6 +192,24 @@ int32_t madqp_spmv_csr(madqp_ctx* ctx, int64_t rows, const Csr& a, double alpha,
     ProfScope ps(ctx, prof_cls);
     const unsigned grid = (unsigned)((rows * 16 + 255) / 256);
     hipLaunchKernelGGL(spmv_csr_kernel, dim3(grid), dim3(256), 0, ctx->stream, rows, a.ptr, a.col, a.val, alpha, x, beta, y);
+    LAUNCH_CHECK(ctx);
+    return MADQP_OK;
+}
+
+// Y[:, c] = alpha M X[:, c] + beta Y[:, c], c < nrhs (column c of X at X + c ldx, of Y at Y + c ldy): bitwise the loop over
+// madqp_spmv_csr, the CSR arrays read ceil(nrhs / MADQP_SPMM_GROUP) times
+int32_t madqp_spmm_csr(madqp_ctx* ctx, int64_t rows, const Csr& a, double alpha, const double* X, int64_t ldx, double beta,
+                       double* Y, int64_t ldy, int64_t nrhs, int prof_cls) {
+    if (rows == 0 || nrhs == 0) return MADQP_OK;
+    ARG_TRY(ctx, a.ptr && X && Y && nrhs > 0);
+    ProfScope ps(ctx, prof_cls);
+    const unsigned gx = (unsigned)((rows * 16 + 255) / 256);
+    if (nrhs <= 8)  // fewer sums to carry: the same arithmetic
+        hipLaunchKernelGGL(spmm_csr_kernel<8>, dim3(gx, 1), dim3(256), 0, ctx->stream, rows, a.ptr, a.col, a.val, alpha, X, ldx,
+                           beta, Y, ldy, nrhs);
+    else
+        hipLaunchKernelGGL(spmm_csr_kernel<MADQP_SPMM_GROUP>, dim3(gx, (unsigned)((nrhs + MADQP_SPMM_GROUP - 1) / MADQP_SPMM_GROUP)),
+                           dim3(256), 0, ctx->stream, rows, a.ptr, a.col, a.val, alpha, X, ldx, beta, Y, ldy, nrhs);
     LAUNCH_CHECK(ctx);
     return MADQP_OK;
 }

@@ -398,6 +398,12 @@ class HIPDistributedCondensedKKTSystem2D:
 
         raise ValueError(GRID_REFUSAL)
 
+    def mul_many(self, W, V, alpha=1.0, beta=0.0):  # (the block interfaces are one family: refused alike)
+        self.solve_many(W)
+
+    def set_block_products(self, on):
+        self.solve_many(None)
+
     def mul(self, w, v, alpha=1.0, beta=0.0):
         self.be._ck(self.be.lib.madqp_dkkt_mul(self._h, C.byref(self.st.cstruct), w.data_ptr(), v.data_ptr(), alpha, beta))
         return w

@@ -245,6 +245,27 @@ class HIPCondensedKKTSystem:
         self.be.kkt_mul(self._h, self.st, w, v, alpha, beta)
         return w
 
+    def mul_many(self, W, V, alpha=1.0, beta=0.0):
+        """``mul`` for every pair of rows of ``W`` and ``V`` (``madqp_kkt_mul_many``): both contiguous 2-D float64 device
+        tensors ``(nrhs, >= n + m + nlb + nub)`` as :meth:`solve_many` takes them, row c of ``W`` <- alpha K (row c of ``V``) +
+        beta (row c of ``W``).  The products with A, A' and H run once on the block.  Anything else is refused before a
+        device call."""
+        st = self.st
+        ntot = st.n + st.m + st.nlb + st.nub
+        nrhs = check_rhs_block(W, ntot, self.be.device)
+        if check_rhs_block(V, ntot, self.be.device, "V") != nrhs:
+            raise ValueError(f"V: {nrhs} rows as W, not {V.shape[0]}")
+        if nrhs and W.data_ptr() == V.data_ptr():
+            raise ValueError("W and V: two different blocks")
+        if nrhs:
+            self.be.kkt_mul_many(self._h, st, W, V, alpha, beta)
+        return W
+
+    def set_block_products(self, on):
+        """``solve_many`` runs the products with A / A' of its stages, and the residuals of its refinement steps, on the
+        block of all right-hand sides (``madqp_kkt_set_block_products``) instead of column by column.  Off by default."""
+        self.be.kkt_set_block_products(self._h, bool(on))
+
     def mul_solved(self, w, v, alpha=1.0, beta=0.0):
         """``mul`` for the residual check of solve_system! (src/linear_solver.jl:26-31): ``v`` is what the last
         ``solve`` returned, unmodified -- the condensed solve's own ``A dx`` is taken instead of a second pass over A

@@ -15,6 +15,13 @@ time: the launches and the factor bytes of the info call, bytes / time against 8
 column-wise relative difference between the two paths.  ``min_nrhs``: the smallest measured nrhs from which on the blocked
 median beats the looped one by more than the spread in every case -- the default written into chol.hip.
 
+``--kkt`` measures ``madqp_kkt_solve_many`` instead, with block products (``madqp_kkt_set_block_products``) off and on,
+alternating in the same windows, for nrhs = 2 .. 128 and 0 and 1 refinement steps, on the dense condensed and the dense
+normal object at n_x = 5 000, m = 2 000 (one seeded A) and the packed-band normal equations of
+``tools/bench_sparse.py --cont N`` (``--cont``, default 300):
+
+    python tools/bench_solve_many.py --kkt --out profiles/kkt_many.json
+
 ``--tiny`` runs the same program on small shapes (a rehearsal of the tool, not a measurement).  No GPU: the tool fails."""
 import argparse
 import json
@@ -133,14 +140,146 @@ def cutover(cases):
     return best
 
 
+# ---- --kkt: madqp_kkt_solve_many with block products off and on ------------------------------------------------------------
+def seed_state(be, st, seed):
+    """iterates well inside their bounds, multipliers of order one (the state of tests/test_gpu_solve_many.py)"""
+    gen = torch.Generator(device=be.device)
+    gen.manual_seed(seed)
+    rnd = lambda k: torch.rand(k, dtype=torch.float64, device=be.device, generator=gen)
+    x = torch.randn(st.n, dtype=torch.float64, device=be.device, generator=gen)
+    st.x.copy_(x)
+    st.xl.copy_(x - (0.5 + rnd(st.n)))
+    st.xu.copy_(x + (0.5 + rnd(st.n)))
+    st.zl.copy_(0.3 + rnd(st.n))
+    st.zu.copy_(0.3 + rnd(st.n))
+    st.y.copy_(torch.randn(st.m, dtype=torch.float64, device=be.device, generator=gen))
+
+
+def dense_kkt_case(be, form, nx, m):
+    """(object, keep-alive) of the dense condensed or normal form on one seeded A; every row an inequality, every slack and
+    half of the variables bounded"""
+    A = torch.empty((m, nx), dtype=torch.float64, device=be.device)
+    be.gen_normal(M.stream_key(22, 0), 0, A)
+    A *= 1.0 / math.sqrt(nx)
+    lb = list(range(0, nx, 2)) + list(range(nx, nx + m))
+    ub = list(range(1, nx, 3)) + list(range(nx, nx + m))
+    st = be.new_state(nx + m, m, lb, ub)
+    if form == "condensed":
+        H = torch.empty((nx, nx), dtype=torch.float64, device=be.device)
+        be.gen_wigner(M.stream_key(22, 1), nx, 1.0 / math.sqrt(nx), H)
+        kkt, keep, del_c = M.HIPCondensedKKTSystem(be, st, nx, list(range(m)), H, A), (H, A), -1.0
+    else:
+        At = A.T.contiguous()
+        kkt, keep, del_c = M.HIPNormalKKTSystem(be, st, nx, list(range(m)), None, At), (At,), 0.0
+    kkt.initialize()
+    seed_state(be, st, 23)
+    kkt.set_aug_diagonal_reg(1.0, del_c)
+    kkt.factorize_wrapper()
+    assert kkt.linear_solver.is_factorized()
+    return kkt, keep
+
+
+def sparse_kkt_case(be, cont):
+    """the packed-band normal equations of ``tools/bench_sparse.py --cont N`` after the first iteration of a solve: the
+    driver's own object, state and factor"""
+    from madqp_jl_amd import preprocess as P
+
+    qp = P.to_device(P.boundary_control_qp(cont), be)
+    s = M.MPCSolver(qp, be, kkt_system="normal", regularization=M.FixedRegularization(1e-8, 0.0), driver="native", max_iter=1,
+                    kkt_bandwidth="auto", kkt_storage="packed")
+    s.solve()
+    assert s.kkt.linear_solver.is_factorized()
+    return s.kkt, (s, qp)
+
+
+def kkt_window(kkt, W0, W, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        W.copy_(W0)
+        kkt.solve_many(W)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def measure_kkt(be, name, kkt, seconds, repeats, refine):
+    st = kkt.st
+    ntot = st.n + st.m + st.nlb + st.nub
+    kkt.set_refine(refine)
+    cells = []
+    for nrhs in NRHS[1:]:
+        W0 = torch.empty((nrhs, ntot), dtype=torch.float64, device=be.device)
+        be.gen_normal(M.stream_key(24, nrhs), 0, W0)
+        W = torch.empty_like(W0)
+        modes = {"loop": False, "block": True}
+        out, info, reps, times = {}, {}, {}, {"loop": [], "block": []}
+        for p, on in modes.items():
+            kkt.set_block_products(on)
+            kkt_window(kkt, W0, W, 2)  # warm-up of the shape (workspace, tile tables)
+            info[p] = be.kkt_many_info(kkt._h, nrhs)
+            out[p] = W.clone()
+            reps[p] = max(1, math.ceil(seconds * 1e3 / kkt_window(kkt, W0, W, 2)))
+        for _ in range(repeats):  # alternating
+            for p, on in modes.items():
+                kkt.set_block_products(on)
+                times[p].append(kkt_window(kkt, W0, W, reps[p]))
+        cell = {"nrhs": nrhs}
+        for p in modes:
+            t = np.array(times[p])
+            cell[p] = {"ms_median": float(np.median(t)), "ms_min": float(t.min()), "ms_max": float(t.max()),
+                       "ms_spread": float(t.max() - t.min()), "calls_per_window": reps[p], "path": info[p][0],
+                       "passes_over_A": info[p][1], "passes_over_H": info[p][2], "workspace_doubles": info[p][3]}
+        cell["max_rel_diff"] = float(((out["loop"] - out["block"]).norm(dim=1) / out["loop"].norm(dim=1)).max())
+        cell["speedup"] = cell["loop"]["ms_median"] / cell["block"]["ms_median"]
+        cells.append(cell)
+        print(f"{name} refine={refine} nrhs={nrhs}: " + ", ".join(f"{p} {cell[p]['ms_median']:.3f} ms (spread {cell[p]['ms_spread']:.3f})"
+                                                                   for p in modes) + f", loop / block {cell['speedup']:.2f}", flush=True)
+    kkt.set_block_products(False)
+    kkt.set_refine(0)
+    # the crossing point: the smallest measured nrhs from which on block beats loop by more than the spread; None: never
+    cross = None
+    for cell in reversed(cells):
+        if cell["loop"]["ms_median"] - cell["block"]["ms_median"] <= max(cell["loop"]["ms_spread"], cell["block"]["ms_spread"]):
+            break
+        cross = cell["nrhs"]
+    return {"case": name, "ntot": ntot, "refine": refine, "block_wins_from": cross, "cells": cells}
+
+
+def main_kkt(a, be):
+    nx, m, cont = (600, 250, 12) if a.tiny else (5000, 2000, a.cont)
+    cases = []
+    for name, make in ((f"dense-condensed-{nx}x{m}", lambda: dense_kkt_case(be, "condensed", nx, m)),
+                       (f"dense-normal-{nx}x{m}", lambda: dense_kkt_case(be, "normal", nx, m)),
+                       (f"sparse-normal-packed-cont{cont}", lambda: sparse_kkt_case(be, cont))):
+        kkt, keep = make()
+        for refine in (0, 1):
+            cases.append(measure_kkt(be, name, kkt, a.window, a.repeats, refine))
+        if not name.startswith("sparse"):
+            kkt.close()  # (the sparse object is its driver's)
+        del kkt, keep
+        torch.cuda.empty_cache()
+    res = {"tool": "tools/bench_solve_many.py --kkt", "device": torch.cuda.get_device_name(0), "tiny": a.tiny,
+           "window_s": a.window, "repeats": a.repeats, "cases": cases}
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    print(json.dumps([{k: v for k, v in c.items() if k != "cells"} for c in cases]))
+    be.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="write the JSON here (default: stdout only)")
     ap.add_argument("--window", type=float, default=0.5, help="seconds per timed window")
     ap.add_argument("--repeats", type=int, default=3, help="windows per path and cell")
     ap.add_argument("--tiny", action="store_true", help="small shapes: a rehearsal of the tool, not a measurement")
+    ap.add_argument("--kkt", action="store_true", help="madqp_kkt_solve_many with block products off and on (-> profiles/kkt_many.json)")
+    ap.add_argument("--cont", type=int, default=300, help="with --kkt: the N of the boundary-control QP of the sparse case")
     a = ap.parse_args()
     be = M.HipBackend(0)
+    if a.kkt:
+        return main_kkt(a, be)
     shapes = [("mid-5000-padded", 5000, True), ("mid-12800-padded", 12800, True), ("large-50000-unpadded", 50000, False)]
     band = ("band-90000-bw600-packed", 90000, 600)
     if a.tiny:
